@@ -5,12 +5,15 @@ SURVEY.md section 8(d).  One step = one full iteration of the reference loop (tr
 LR update, render (HexPlane + MLP deformation -> rasterizer), L1 + plane regularisers, backward, densification
 statistics, Adam on every Gaussian parameter and the deformation field.
 
-    python bench.py --gpus N --steps K --warmup W
-prints ONE JSON line (rank 0).  N > 1: one process per GPU -- started by `python -m torch.distributed.run`, or, when no
-launcher set RANK / WORLD_SIZE, by this script itself (launch.py: the parent spawns N ranks before anything touches the GPU
-and relays rank 0's line).  --shard camera (default): every rank renders a different camera of the same step and the parameter
-gradients are all-reduced over RCCL (weak scaling: per-GPU work fixed); --shard tile-row: one camera split by tile rows
-(strong scaling).
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline; --full adds every
+other reading (steady-state leg, instance counts and pairs, live roofline, SSIM and render-FPS legs, the other configurations,
+the CPU baseline).  --dump-outputs DIR writes what the timed path computes in its last steps (the loss, the model they leave and
+Adam's first moments; the steps are taken again from the seeded model, so that every run has the same inputs) as .npy.
+N > 1: one process per GPU -- started by `python -m torch.distributed.run`, or, when no launcher set RANK / WORLD_SIZE, by this
+script itself (launch.py: the parent spawns N ranks before anything touches the GPU and relays rank 0's line).  --shard camera
+(default): every rank renders a different camera of the same step and the parameter gradients are all-reduced over RCCL (weak
+scaling: per-GPU work fixed); --shard tile-row: one camera split by tile rows (strong scaling).
 """
 import argparse
 import importlib
@@ -207,6 +210,16 @@ EXPLAIN = {
     "value": "training steps per second over exactly --steps steps after --warmup, whole job (camera-batch shard: summed over ranks); full "
              "iteration in the timed region: LR -> render (field, projection, binning, compositing) -> L1 (+ plane regularisers) -> backward "
              "-> densification statistics -> Adam; inputs resident in HBM; verified applied by Trainer.drain() before the clock stops",
+    "--full": "a plain run measures the headline alone (setup, --warmup steps, --steps timed steps); every key below that names a "
+              "leg, instance count, pair count, roofline or CPU baseline comes from --full, which runs those readings as well",
+    "--dump-outputs": "DIR/<name>.npy after the timed steps: the timed path's last two steps (same iterations, cameras and sync mode) "
+                      "taken again from the seeded model, whose inputs are the same in every run.  The timed steps' own model is not "
+                      "written: their gradients are float-atomic sums whose order changes from run to run, and under Adam (eps 1e-15) two "
+                      "runs drift apart step by step.  So loss (float64) is that replay's, not config.final_loss.  Written: the model the "
+                      "steps leave -- xyz, features_dc, features_rest, opacity, scaling, rotation, xyz_gradient_accum, denom, max_radii2D "
+                      "(a fixed seeded sample of 65536 rows when the model is larger), deformation.<tensor> (a fixed seeded sample of "
+                      "65536 elements of larger tensors) -- and adam_exp_avg.<same name> for every parameter: Adam's first moment, "
+                      "which carries the gradients' magnitudes; float32 otherwise",
     "config.instances_R": "the reference's instance count (every tile of every splat's rectangle), mean over the cameras of the timed steps",
     "config.instances_binned": "what the default binning keeps: instances that can reach alpha >= 1/255 in their tile",
     "config.pairs_Q": Q_IS,
@@ -253,9 +266,9 @@ def compact_line(full):
     c = full["config"]
     cfg = {k: c[k] for k in ("workload", "gaussians", "frames", "width", "height", "step_path", "lambda_dssim", "parallelism",
                              "ranks_seen", "host_sync", "gaussians_at_end", "steps_replayed_after_overflow") if k in c}
-    cfg["instances_R"] = _r(c.get("instances_R"), 6)
-    cfg["instances_binned"] = _r(c.get("instances_binned"), 6)
-    cfg["final_loss"] = _r(c.get("final_loss"), 5)
+    for k, n in (("instances_R", 6), ("instances_binned", 6), ("final_loss", 5)):
+        if k in c:                       # (the instance counts: --full only)
+            cfg[k] = _r(c[k], n)
     q = (c.get("pairs_Q") or {}).get("processed")
     if q:
         cfg["pairs_Q"] = {k: _r(v, 4) for k, v in q.items()}
@@ -319,6 +332,94 @@ def compact_line(full):
 
 def mean_q(rows):
     return {k: sum(r[k] for r in rows) / len(rows) for k in rows[0]} if rows else None
+
+
+DUMP_ROWS = 65536            # Gaussians sampled for --dump-outputs (a fixed, seeded sample once the model is larger)
+DUMP_FIELD_ELEMS = 1 << 16   # elements sampled from each deformation-field tensor larger than this
+DUMP_SEED = 6666
+
+
+def replay_last_steps(build, steps, dev=None, sync_mode="async", attach=None):
+    """--dump-outputs: the timed path's last steps -- (iteration, camera index) pairs, same trainer configuration and sync mode --
+    taken again from the seeded model `build()` makes, which is the same in every run with the same arguments.  (The timed
+    steps' own model is not: a step sums its gradients with float atomics, in a different order on every run, and Adam's eps of
+    1e-15 turns a last-bit difference of a near-zero gradient into a different step of that element, so two runs drift apart
+    step by step.)  Returns the model and the loss of the last step, every step applied."""
+    import torch
+    DGR = importlib.import_module("iclr2025_3d-mom_amd.diff_gaussian_rasterization")
+    scene, g, trainer, op = build()
+    if attach is not None:
+        attach(trainer)
+    DGR.set_sync_mode("exact")                  # the first step sizes the binning buffers, as in the timed run
+    loss = None
+    try:
+        for n, (it, ci) in enumerate(steps):
+            cam = trainer.cams[ci]
+            if dev is not None:
+                cam.device_tensors(dev)
+            loss = trainer.step(it, cams=[cam])
+            if n == 0 and sync_mode == "async" and trainer.fused is None:
+                DGR.set_sync_mode("async", capacity_hint=int(DGR.last_num_rendered() * 1.6) + 65536)
+        trainer.drain()
+    finally:
+        DGR.set_sync_mode("exact")
+    if dev is not None and dev.type == "cuda":
+        torch.cuda.synchronize()
+    if hasattr(loss, "tensor"):
+        loss = loss.tensor()
+    if trainer.fused is not None:
+        trainer.fused.gather_moments()          # (sharded Adam: every rank's slice of the moments)
+    return g, loss
+
+
+def dump_outputs(out_dir, g, loss):
+    """--dump-outputs: what a caller of the timed path holds after a step -- the loss it returned and the model it updated in
+    place (the six Gaussian parameters, the densification statistics, every deformation-field tensor) and Adam's first moment of
+    every parameter, which carries the gradients' magnitudes -- as float32 / float64 .npy files.  Rows of the per-Gaussian arrays
+    and elements of large field tensors are a fixed, seeded sample, so the files stay below 64 MB at every config and two builds
+    can be compared array for array."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    P = int(g.get_xyz.shape[0])
+    rows = None
+    if P > DUMP_ROWS:
+        rows = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(P, DUMP_ROWS, replace=False)))
+    arrays = {"loss": torch.as_tensor(loss).detach().double().reshape(-1)}
+    per_gaussian = {"xyz": g._xyz, "features_dc": g._features_dc, "features_rest": g._features_rest, "opacity": g._opacity,
+                    "scaling": g._scaling, "rotation": g._rotation, "xyz_gradient_accum": g.xyz_gradient_accum, "denom": g.denom,
+                    "max_radii2D": g.max_radii2D}
+    state = g.optimizer.state
+
+    def exp_avg(p):
+        st = state.get(p) if isinstance(p, torch.nn.Parameter) else None
+        return st["exp_avg"] if st and "exp_avg" in st else None
+
+    for k, t in per_gaussian.items():
+        for name, v in ((k, t), ("adam_exp_avg." + k, exp_avg(t))):
+            if v is not None:
+                v = v.detach()
+                arrays[name] = v if rows is None else v[rows.to(v.device)]
+    params = dict(g._deformation.named_parameters())
+    for k, t in g._deformation.state_dict().items():
+        if not torch.is_floating_point(t):
+            continue
+        for name, v in (("deformation." + k, t), ("adam_exp_avg.deformation." + k, exp_avg(params.get(k)))):
+            if v is None:
+                continue
+            v = v.detach()
+            if v.numel() > DUMP_FIELD_ELEMS:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).choice(v.numel(), DUMP_FIELD_ELEMS, replace=False))
+                v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+            arrays[name] = v
+    total = 0
+    for k, t in arrays.items():
+        a = t.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        total += a.nbytes
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+    return sorted(arrays)
 
 
 def render_fps(scene, g, pp, background, delta_scale, passes=8):
@@ -601,6 +702,13 @@ def parse_args(argv=None):
                     help="skip via_render_api and other_configs (profiling runs: their kernels would mix into the per-kernel averages)")
     ap.add_argument("--steady-steps", type=int, default=200, help="steps of the steady-state leg (SURVEY 8d: >= 200)")
     ap.add_argument("--steady-warmup", type=int, default=50, help="warm-up of the steady-state leg (SURVEY 8d: 50)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every other reading: steady-state leg, instance counts and pairs, live roofline, SSIM "
+                         "and render-FPS legs, the other configurations, the CPU baseline (--no-extra / --no-side-legs / "
+                         "--no-cpu-baseline select among them); a plain run measures the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computes in its last two steps (the loss, the model and "
+                         "Adam's first moments they leave; the steps taken again from the seeded model) to DIR/<name>.npy")
     ap.add_argument("--explain", action="store_true", help="print what every key of the JSON line means, and exit")
     ap.add_argument("--path", default="fused", choices=["fused", "autograd", "autograd-per-op"],
                     help="fused: explicit launch sequence (fused_step.py); autograd: render() + loss.backward(), the way the "
@@ -666,15 +774,21 @@ def main():
     npix = cfg["W"] * cfg["H"]
 
     def cam_of(i):
+        return cams[cam_index(i)]
+
+    def cam_index(i):
         # every rank takes a different camera of the cycle (camera-batch shard); N=1 walks all F+5 cameras.  The walk is STRIDED
         # (17 is coprime to the 13 / 65 / 125 / 245 cameras of the configs): any K consecutive steps sample the whole set evenly, as the
         # reference's random draw does (train_4DGS.py:172-187) -- in list order a 20-step window sat on the five hemisphere views and the
         # first frames, whose steps take 0.92-1.09 ms against 0.87 for the average camera (tools/probe/per_camera.py)
         j = (i * world + rank) if a.shard == "camera" else i
-        return cams[(CAMERA_STRIDE * j) % len(cams)]
+        return (CAMERA_STRIDE * j) % len(cams)
+
+    def iteration_of(i):
+        return it0 + 1 + (i if a.with_densify else i % 90)
 
     def one(i):
-        return trainer.step(it0 + 1 + (i if a.with_densify else i % 90), cams=[cam_of(i)])
+        return trainer.step(iteration_of(i), cams=[cam_of(i)])
 
     def instances_of(i):
         """Instance count R of the camera step i draws (read once, outside any timed region)."""
@@ -685,14 +799,14 @@ def main():
     R = DGR.last_num_rendered() if trainer.fused is None else int(trainer.fused.nr_host[0])
     if a.sync_mode == "async" and trainer.fused is None:
         DGR.set_sync_mode("async", capacity_hint=int(R * 1.6) + 65536)
-    # per-camera instance counts (R is data dependent: SURVEY 8d asks for it with every timing).  One untimed pass over the
+    # --full: per-camera instance counts (R is data dependent: SURVEY 8d asks for it with every timing).  One untimed pass over the
     # cameras this rank will draw; each step's count is read after a synchronisation.
     # R is the REFERENCE's instance count -- every tile of every splat's rectangle (duplicateWithKeys) -- which is what the
     # algorithmic bytes are defined on; the default binning drops the instances that cannot contribute, and that smaller
     # count is reported beside it (instances_binned).  So: two passes, the first with keep_all_tiles.
     r_of_cam, binned_of_cam = {}, {}
     q_of_cam = {True: {}, False: {}}
-    if trainer.fused is not None:
+    if a.full and trainer.fused is not None:
         for keep_all, table in ((True, r_of_cam), (False, binned_of_cam)):
             trainer.fused.keep_all_tiles = keep_all
             trainer.fused.exact_next()
@@ -756,7 +870,7 @@ def main():
     scale = world if a.shard == "camera" else 1
     nxt = 1 + len(cams)
     steady = None
-    if not a.no_extra:
+    if a.full and not a.no_extra:
         # SURVEY 8(d)'s reading of the metric: >= 200 steps after 50 warm-up.  It runs BEFORE the headline region, so the
         # headline's K steps are measured on a warm device whatever --steps / --warmup the caller chose.
         for i in range(a.steady_warmup):
@@ -773,26 +887,24 @@ def main():
     nxt += a.warmup
     dt, loss, r_mean = timed(nxt, a.steps)
     nxt += a.steps
+    last_step = nxt - 1
     assert torch.isfinite(loss).all(), "loss is not finite"
     headline_binned, headline_q = binned_mean[0], dict(q_mean)
-    # the live roofline's launch durations: a leg of its own, straight after the headline region (same device state), every launch of
-    # the kernel bracketed by HIP events on its launch stream -- one full cycle over the cameras, so the sample is the workload's mix
-    n_roof = len(cams)
-    dt_roof, loss_r, r_mean_roof = timed(nxt, n_roof, profile_kernel=a.roofline_kernel)
-    nxt += n_roof
-    roof_binned = binned_mean[0]
-    assert torch.isfinite(loss_r).all(), "loss is not finite (roofline leg)"
-    binned_mean[0] = headline_binned
+    if a.full:
+        # the live roofline's launch durations: a leg of its own, straight after the headline region (same device state), every launch
+        # of the kernel bracketed by HIP events on its launch stream -- one full cycle over the cameras, so the sample is the workload's mix
+        n_roof = len(cams)
+        dt_roof, loss_r, r_mean_roof = timed(nxt, n_roof, profile_kernel=a.roofline_kernel)
+        nxt += n_roof
+        roof_binned = binned_mean[0]
+        assert torch.isfinite(loss_r).all(), "loss is not finite (roofline leg)"
+        binned_mean[0] = headline_binned
     out = {
         "metric": metric_name(), "value": a.steps * scale / dt,
         "unit": "steps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps,
         "higher_is_better": True, "scaling": "weak" if a.shard == "camera" else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": cfg["name"], "gaussians": cfg["P"], "frames": cfg["F"], "width": cfg["W"],
-                   "height": cfg["H"], "instances_R": r_mean,
-                   "instances_R_is": "the reference's count (every tile of every splat's rectangle), mean over the cameras of the timed steps",
-                   "instances_binned": binned_mean[0],
-                   "instances_binned_is": "what the default binning keeps: instances that can reach alpha >= 1/255 in their tile",
-                   "pairs_Q": {"processed": headline_q[False], "reference_lists": headline_q[True], "what": Q_IS},
+                   "height": cfg["H"],
                    "sh_degree": 3, "step_path": a.path, "batch_size": 1,
                    "lambda_dssim": a.lambda_dssim, "parallelism": ((f"camera-batch x{world}" + (" sharded-adam" if getattr(trainer.dist, "shard_adam", False) else "")
                                     if a.shard == "camera" else f"tile-row x{world}")
@@ -800,11 +912,18 @@ def main():
                    "ranks_seen": ranks_seen, "host_sync": a.sync_mode, "final_loss": float(loss), "densify_in_window": bool(a.with_densify),
                    "gaussians_at_end": int(g.get_xyz.shape[0]), "steps_replayed_after_overflow": int(trainer.replayed),
                    "inputs": "camera matrices and ground-truth images pre-staged in HBM before the timed region"},
-        "roofline_step": step_roofline(cfg["P"], binned_mean[0] or r_mean, r_mean, npix, dt / a.steps, a.lambda_dssim),
     }
+    if a.full:
+        out["config"].update({
+            "instances_R": r_mean,
+            "instances_R_is": "the reference's count (every tile of every splat's rectangle), mean over the cameras of the timed steps",
+            "instances_binned": binned_mean[0],
+            "instances_binned_is": "what the default binning keeps: instances that can reach alpha >= 1/255 in their tile",
+            "pairs_Q": {"processed": headline_q[False], "reference_lists": headline_q[True], "what": Q_IS}})
+        out["roofline_step"] = step_roofline(cfg["P"], binned_mean[0] or r_mean, r_mean, npix, dt / a.steps, a.lambda_dssim)
     if steady is not None:
         out["steady"] = steady
-    if rank == 0:
+    if rank == 0 and a.full:
         traffic, tnote = measured_traffic(a.roofline_kernel, cfg)
         sq, sqnote = sq_counters(a.roofline_kernel, cfg)
         out["roofline"] = prof.roofline(a.roofline_kernel, cfg["P"], roof_binned or r_mean_roof, npix, traffic=traffic, R_ref=r_mean_roof, sq=sq)
@@ -862,6 +981,28 @@ def main():
                 out["other_configs"]["c5_cold_allocator"] = cold
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
+    if a.dump_outputs:
+        # the timed path's last two steps (iterations, cameras, sync mode) taken again from the seeded model: replay_last_steps
+        last_two = [(iteration_of(i), cam_index(i)) for i in (last_step - 1, last_step)]
+        import gc
+        scene = g = trainer = cams = None       # (the timed model is done with)
+        gc.collect()
+        torch.cuda.empty_cache()
+
+        def build():
+            st = build_state(cfg, dev, fused=(a.path == "fused"), lambda_dssim=a.lambda_dssim, gc_freeze=True)
+            if a.path == "autograd-per-op":
+                st[2].pipe.per_op_autograd = True
+            return st
+
+        def attach(tr):
+            par.attach(tr, rank, world, mode=a.shard, shard_adam=a.shard_adam or None)
+
+        g, loss_d = replay_last_steps(build, last_two, dev, a.sync_mode, attach if (world > 1 or force_dist) else None)
+        assert torch.isfinite(loss_d).all(), "loss is not finite (--dump-outputs)"
+        if rank == 0:
+            dump_outputs(a.dump_outputs, g, loss_d)
+    if rank == 0:
         sys.stdout.flush()
         full = json.dumps(out)
         print("BENCH_FULL " + full, file=sys.stderr)

@@ -101,3 +101,64 @@ def test_the_compact_line_carries_every_leg_as_numbers_and_fits_the_drivers_tail
     assert abs(rl["frac"] - rl["achieved"] / rl["peak"]) < 1e-3 and rl["step"]["frac"] < 1
     assert {"value", "unit", "cores", "kind", "sample"} <= set(line["cpu_baseline"])
     assert set(bench.EXPLAIN) >= {"config.legs", "roofline", "cpu_baseline"}
+
+
+def test_a_plain_run_is_the_headline_alone_and_full_is_opt_in():
+    a = bench.parse_args([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out", "--steps", "7", "--warmup", "3"])
+    assert a.full is True and a.dump_outputs == "out" and (a.steps, a.warmup) == (7, 3)
+    # the line of a plain run (no instance counts, no legs, no roofline) compacts without inventing any of them
+    plain = {k: 1.0 for k in ("value", "ms_per_step")}
+    plain.update(metric=bench.metric_name(), unit="steps/s", n_gpus=1, steps=7, warmup=3, higher_is_better=True, scaling="weak",
+                 vs_baseline=None, dtype="f32", data="synthetic", config={"workload": "w", "final_loss": 0.5})
+    line = bench.compact_line(plain)
+    assert line["config"] == {"workload": "w", "final_loss": 0.5} and line["roofline"] is None and "cpu_baseline" not in line
+
+
+def test_dump_outputs_writes_the_replayed_last_steps_and_a_fixed_sample_of_the_model(tmp_path, monkeypatch):
+    """--dump-outputs on a small model (CPU oracle in place of the kernels): replay_last_steps takes the given (iteration,
+    camera) steps from the seeded model -- the same model and loss as stepping a freshly built one by hand -- and dump_outputs
+    writes float32 / float64 .npy files of it, Adam's first moments included, with the same seeded rows and field elements every
+    time and under the 64 MB cap."""
+    monkeypatch.setattr(bench, "DUMP_ROWS", 1000)
+    monkeypatch.setattr(bench, "DUMP_FIELD_ELEMS", 5000)
+    cfg = dict(P=3000, F=8, W=64, H=48, time_res=8, name="tiny")
+    steps = [(5010, 3), (5011, 7)]
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)              # (torch's CPU reductions split over threads differently from run to run)
+    try:
+        _replay_and_dump(cfg, steps, tmp_path)
+    finally:
+        torch.set_num_threads(threads)
+
+
+def _replay_and_dump(cfg, steps, tmp_path):
+    import numpy as np
+    from oracle import cpu_backend
+    with cpu_backend.installed():
+        g, loss = bench.replay_last_steps(lambda: bench.build_state(cfg, "cpu"), steps, sync_mode="exact")
+        names = bench.dump_outputs(str(tmp_path / "a"), g, loss)
+        g_b, loss_b = bench.replay_last_steps(lambda: bench.build_state(cfg, "cpu"), steps, sync_mode="exact")
+        assert bench.dump_outputs(str(tmp_path / "b"), g_b, loss_b) == names
+        scene, g_h, trainer, op = bench.build_state(cfg, "cpu")
+        for it, ci in steps:
+            loss_h = trainer.step(it, cams=[trainer.cams[ci]])
+    assert float(loss_h) == float(loss)
+    assert {"loss", "xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation", "xyz_gradient_accum", "denom",
+            "max_radii2D", "adam_exp_avg.xyz", "adam_exp_avg.opacity", "adam_exp_avg.rotation"} <= set(names)
+    assert any(n.startswith("deformation.") for n in names) and any(n.startswith("adam_exp_avg.deformation.") for n in names)
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+        total += x.nbytes
+        if "deformation." in n:
+            assert x.size <= 5000, n
+    assert total <= 64 << 20
+    loss_a = np.load(tmp_path / "a" / "loss.npy")
+    assert loss_a.dtype == np.float64 and loss_a.shape == (1,) and abs(loss_a[0] - float(loss)) <= 1e-6 * abs(float(loss))
+    rows = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(3000, 1000, replace=False))
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "xyz.npy"), g_h._xyz.detach().numpy()[rows])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "adam_exp_avg.xyz.npy"),
+                                  g_h.optimizer.state[g_h._xyz]["exp_avg"].numpy()[rows])

@@ -20,6 +20,13 @@ def load(name):
     return np.load(os.path.join(G, name))
 
 
+def assert_adam_step_close(actual, desired, lr, err_msg=""):
+    """An Adam step divides by the sqrt of the second moment, and torch takes that sqrt from MKL, whose last bit depends on
+    the processor: the result agrees with the reference's to two units in the last place of the parameter and of the step
+    (whose size is lr at most in a first step)."""
+    np.testing.assert_allclose(actual, desired, rtol=2.0 ** -22, atol=lr * 2.0 ** -22, err_msg=err_msg)
+
+
 class HP:
     net_width = 64; timebase_pe = 4; defor_depth = 0; posebase_pe = 10; scale_rotation_pe = 2; opacity_pe = 2
     timenet_width = 64; timenet_output = 32; bounds = 1.6; plane_tv_weight = 0.0001; time_smoothness_weight = 0.01
@@ -149,7 +156,9 @@ def test_g6_sh_and_covariance_incl_rasterizer_oracle():
     for deg in range(4):
         np.testing.assert_allclose(sh_utils.eval_sh(deg, torch.tensor(d["sh"]), torch.tensor(d["dirs"])).numpy(),
                                    d[f"rgb{deg}"], rtol=2e-6, atol=2e-7)
-    np.testing.assert_allclose(gen.build_rotation(torch.tensor(d["rotation"])).numpy(), d["rotmat"], rtol=1e-6, atol=1e-7)
+    # the quaternion is normalised with torch's sqrt (MKL: its last bit depends on the processor), and an entry such as
+    # 1 - 2 (y^2 + z^2) carries that into an absolute error of a few units in the last place of 1.0, whatever its own size
+    np.testing.assert_allclose(gen.build_rotation(torch.tensor(d["rotation"])).numpy(), d["rotmat"], rtol=1e-6, atol=2.0 ** -21)
     L = gen.build_scaling_rotation(0.7 * torch.tensor(d["scaling"]), torch.tensor(d["rotation"]))
     np.testing.assert_allclose(gen.strip_symmetric(L @ L.transpose(1, 2)).numpy(), d["cov"], rtol=1e-5, atol=1e-7)
     # the C rasterizer oracle's SH -> RGB (forward.cu:20-71) against the reference's own eval_sh
@@ -220,8 +229,10 @@ def test_g8_densify_prune_reset_match_reference():
         for k in ("_xyz", "_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity"):
             getattr(gm, k).grad = torch.tensor(d["grad" + k])
         gm.optimizer.step()
+        lr = {g["params"][0].data_ptr(): g["lr"] for g in gm.optimizer.param_groups}
         for k in ("_xyz", "_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity"):
-            np.testing.assert_array_equal(getattr(gm, k).detach().numpy(), d["after_step" + k])
+            p = getattr(gm, k)
+            assert_adam_step_close(p.detach().numpy(), d["after_step" + k], lr[p.data_ptr()], err_msg=k)
         gm.add_densification_stats(torch.tensor(d["vsp"]), torch.tensor(d["vis"]))
         np.testing.assert_array_equal(gm.xyz_gradient_accum.numpy(), d["accum"])
         np.testing.assert_array_equal(gm.denom.numpy(), d["denom"])

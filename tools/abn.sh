@@ -4,7 +4,7 @@ k=$1; shift
 for i in 1 2; do
   for lib in libmom4d.so "$@"; do
     [ "$lib" = libmom4d.so ] && path=iclr2025_3d-mom_amd/lib/libmom4d.so || path=iclr2025_3d-mom_amd/lib/var/$lib.so
-    MOM4D_LIB=$path MOM4D_LIB_LAX=1 python bench.py --no-cpu-baseline --no-extra --steps 300 --warmup 50 --roofline-kernel $k 2>/dev/null | python -c "
+    MOM4D_LIB=$path MOM4D_LIB_LAX=1 python bench.py --full --no-cpu-baseline --no-extra --steps 300 --warmup 50 --roofline-kernel $k 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d.get('roofline') or {}

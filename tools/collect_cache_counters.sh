@@ -9,7 +9,7 @@ root=$PWD
 out=$root/gpurun_out/$pre
 mkdir -p $out $root/profiles
 cd /tmp && export TMPDIR=/tmp
-args="--config $cfg --steps 8 --warmup 4 --no-cpu-baseline --no-extra"
+args="--full --config $cfg --steps 8 --warmup 4 --no-cpu-baseline --no-extra"
 i=0
 for set in "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_PENDING_STALL_CYCLES_sum" \
            "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum" \

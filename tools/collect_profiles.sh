@@ -12,8 +12,8 @@ root=$PWD
 out=$root/gpurun_out/$pre
 mkdir -p $out $root/profiles
 cd /tmp && export TMPDIR=/tmp
-if [ "$cfg" = "c2" ]; then main_args="--no-cpu-baseline --no-side-legs"; pmc_args="--steps 20 --warmup 5 --no-cpu-baseline --no-extra"
-else main_args="--config $cfg --no-cpu-baseline --no-extra --steps 40 --warmup 10"; pmc_args="--config $cfg --steps 12 --warmup 6 --no-cpu-baseline --no-extra"; fi
+if [ "$cfg" = "c2" ]; then main_args="--full --no-cpu-baseline --no-side-legs"; pmc_args="--full --steps 20 --warmup 5 --no-cpu-baseline --no-extra"
+else main_args="--full --config $cfg --no-cpu-baseline --no-extra --steps 40 --warmup 10"; pmc_args="--full --config $cfg --steps 12 --warmup 6 --no-cpu-baseline --no-extra"; fi
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o run -- python3 $root/bench.py $main_args > $out/bench_default.json 2> $out/stats.err
 cp $(find $out/stats -name "*kernel_stats.csv" | head -1) $out/${pre}_kernel_stats.csv
 for c in FETCH_SIZE WRITE_SIZE; do

@@ -7,7 +7,7 @@ out=$PWD/${2:-gpurun_out/dist_trace}
 root=$PWD
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-args="--no-extra --no-cpu-baseline --steps 150 --warmup 30"
+args="--full --no-extra --no-cpu-baseline --steps 150 --warmup 30"
 rocprofv3 --kernel-trace --output-format csv -d $out/plain -o run -- python3 $root/bench.py $args > /dev/null 2> $out/plain.err
 export RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 LOCAL_WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 MOM_FORCE_DIST=1
 rocprofv3 --kernel-trace --output-format csv -d $out/dist -o run -- python3 $root/bench.py --shard $mode $args > /dev/null 2> $out/dist.err

@@ -5,7 +5,7 @@ Collect on the GPU box (program directly after `--`, counters in their own run):
 
     rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY \
         SQ_ACTIVE_INST_ANY --output-format csv -d gpurun_out/pmc_mfma -- python3 bench.py --steps 20 --warmup 5 \
-        --no-cpu-baseline --no-extra
+        --full --no-cpu-baseline --no-extra
 
 then here:
 

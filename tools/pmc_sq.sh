@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for ctrs in "$@"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $out/pass$i -o run -- python3 $root/bench.py --no-extra --no-cpu-baseline --steps 20 --warmup 5 > $out/pass$i.json 2> $out/pass$i.err
+  rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $out/pass$i -o run -- python3 $root/bench.py --full --no-extra --no-cpu-baseline --steps 20 --warmup 5 > $out/pass$i.json 2> $out/pass$i.err
   f=$(find $out/pass$i -name "*counter_collection.csv" | head -1)
   cp "$f" $out/pass${i}_counter_collection.csv
   rm -rf $out/pass$i

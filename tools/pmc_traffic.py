@@ -4,9 +4,9 @@ Collect on the GPU box (two SEPARATE passes: FETCH_SIZE takes 3 of the 4 TCC slo
 directly after `--`:
 
     rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- \
-        python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline
+        python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
     rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -- \
-        python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline
+        python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
 
 then here:
 

@@ -5,7 +5,7 @@ tag=$1; shift
 out=$PWD/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out -o run -- python3 $OLDPWD/bench.py --no-extra --no-cpu-baseline "$@" > $out/bench.json 2> $out/err.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out -o run -- python3 $OLDPWD/bench.py --full --no-extra --no-cpu-baseline "$@" > $out/bench.json 2> $out/err.log
 f=$(find $out -name "*kernel_stats.csv" | head -1)
 cp "$f" $out/kernel_stats.csv 2>/dev/null
 python3 - "$out/kernel_stats.csv" <<'PY'
