@@ -25,7 +25,7 @@ class MomError(RuntimeError):
 
 GACC_FLOATS = int(os.environ.get("MOM_GACC_FLOATS", "12"))         # (the override: only for A/B builds with -DMOM_GACC_FLOATS=16)
 # MOM_GACC_FLOATS: floats per Gaussian of the backward's accumulator record
-ABI_VERSION = 7          # MOM_ABI_VERSION of the include/mom4d.h this mirror was written against
+ABI_VERSION = 8          # MOM_ABI_VERSION of the include/mom4d.h this mirror was written against
 
 
 class MomRasterArgs(C.Structure):
@@ -44,7 +44,8 @@ class MomRasterArgs(C.Structure):
                 ("accum_cleared", C.c_int),
                 ("l1_partials", C.c_void_p),                        # per-tile sums of the L1 epilogue instead of two contended atomics
                 ("status_post", C.c_void_p), ("status_serial", C.c_uint),   # the frame's status bits, posted to pinned host memory
-                ("l1_grad_scale", C.c_float)]                       # 0 (= 1) or a factor on the L1 epilogue's gradient (camera-batch shard: 1 / world)
+                ("l1_grad_scale", C.c_float),                       # 0 (= 1) or a factor on the L1 epilogue's gradient (camera-batch shard: 1 / world)
+                ("params_raw", C.c_int)]                            # !=0: scales / rotations / opacities are raw; the kernels activate them
 
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
@@ -54,7 +55,9 @@ class MomRasterArgs(C.Structure):
 class MomRasterGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D",
                                           "dL_dsh", "dL_dsh_rest", "dL_dscales", "dL_drotations", "act_rotations_raw",
-                                          "dL_dscales_copy", "dL_drotations_copy")]
+                                          "dL_dscales_copy", "dL_drotations_copy",
+                                          # densification statistics epilogue of the projection backward (all three or none)
+                                          "stats_max_radii2D", "stats_grad_accum", "stats_denom", "stats_skip_if_nonzero")]
 
 
 class MomRasterLayout(C.Structure):

@@ -215,6 +215,9 @@ __device__ __forceinline__ float mom_quat_norm(float x, float y, float z, float 
     return fmaxf(sqrtf(x * x + y * y + z * z + w * w), 1e-12f);
 }
 __device__ __forceinline__ float mom_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+// |g[:2]| of a screen-space gradient, the increment of the densification statistics (scene/gaussian_model.py:713-715): one
+// expression for mom_densify_stats and the projection backward's statistics epilogue, so that both accumulate the same bits
+__device__ __forceinline__ float mom_grad_norm2d(float gx, float gy) { return sqrtf(gx * gx + gy * gy); }
 
 __device__ __forceinline__ int mom_lane() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 #endif

@@ -311,7 +311,7 @@ densify_stats_kernel(int P, const int* __restrict__ radii, const float* __restri
     if (r <= 0) return;
     max_radii2D[i] = fmaxf(max_radii2D[i], (float)r);
     const float gx = vsp_grad[3 * i], gy = vsp_grad[3 * i + 1];
-    grad_accum[i] += sqrtf(gx * gx + gy * gy);
+    grad_accum[i] += mom_grad_norm2d(gx, gy);
     denom[i] += 1.0f;
 }
 }  // namespace

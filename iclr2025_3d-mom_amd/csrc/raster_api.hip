@@ -20,6 +20,7 @@ static int check_args(const MomRasterArgs* a)
     if (!a || a->struct_size != sizeof(MomRasterArgs)) return MOM_EINVAL;   // a binder built against another header: refuse
     if (a->P < 0 || a->W <= 0 || a->H <= 0) return MOM_EINVAL;
     if (a->tile_row0 < 0 || a->tile_row1 < a->tile_row0 || a->tile_row1 > (a->H + MOM_TILE - 1) / MOM_TILE) return MOM_EINVAL;
+    if (a->params_raw && (a->cov3D_precomp || !a->scales || !a->rotations)) return MOM_EINVAL;   // activations of inputs that are not there
     if (a->P == 0) return MOM_OK;
     if (!a->means3D || !a->opacities || !a->viewmatrix || !a->projmatrix || !a->campos || !a->background) return MOM_EINVAL;
     if (!a->shs && !a->colors_precomp) return MOM_EINVAL;  // rasterizer_impl.cu:243-246
@@ -36,6 +37,10 @@ static int check_grads(const MomRasterArgs* a, const MomRasterGrads* gr)
     if (a->shs_rest && !gr->dL_dsh_rest) return MOM_EINVAL;
     if (a->scales && (!gr->dL_dscales || !gr->dL_drotations)) return MOM_EINVAL;
     if (gr->act_rotations_raw && (!a->scales || !a->rotations || a->cov3D_precomp)) return MOM_EINVAL;   // activations of inputs that are not there
+    if (gr->act_rotations_raw && a->params_raw) return MOM_EINVAL;          // two claims about what the rasterizer's inputs are
+    const int n_stats = (gr->stats_max_radii2D != nullptr) + (gr->stats_grad_accum != nullptr) + (gr->stats_denom != nullptr);
+    if (n_stats != 0 && n_stats != 3) return MOM_EINVAL;
+    if (gr->stats_skip_if_nonzero && n_stats == 0) return MOM_EINVAL;
     return MOM_OK;
 }
 

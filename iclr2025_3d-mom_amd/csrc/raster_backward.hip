@@ -55,13 +55,20 @@ struct BwdArgs {
     int colors_from_sh;
     float *dmeans2D, *dcolors, *dopacity, *dmeans3D, *dcov3D, *dsh, *dsh_rest, *dscales, *drot;
     float *dscales2, *drot2;     // MomRasterGrads.dL_dscales_copy / dL_drotations_copy: second destinations of the same values (or null)
+    // MomRasterGrads.stats_*: the densification statistics of mom_densify_stats, updated in place from this kernel's radius and
+    // dL/d mean2D (all three accumulators or none); st_skip as that function's skip_if_nonzero
+    float *st_maxr, *st_accum, *st_denom;
+    const uint32_t* st_skip;
 };
 
 // STAGED (DC and rest stored apart, an odd row length): the workgroup's higher-order SH rows are copied to LDS with
 // coalesced loads, every thread reads its row there, writes the row's GRADIENT over it once it is done reading, and the
 // workgroup stores the gradient rows with coalesced writes.  In place, a thread's 180-byte row makes every load and
 // every store instruction touch 64 different cache lines.
-template <bool STAGED>
+// RAW (MomRasterArgs.params_raw): MomRasterArgs.scales / rotations hold the raw parameters.  exp(scale) and the normalised quaternion
+// are recomputed here as the forward (and mom_activations_forward) made them, the activated opacity is the one in the forward's record,
+// and the scale / rotation / opacity gradients go out through the activations as with act_rotations_raw.
+template <bool STAGED, bool RAW>
 __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdArgs a)
 {
     extern __shared__ float s_sh[];
@@ -119,6 +126,18 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdArgs a)
     // (outputs only, not `asm volatile`: that counts as a possible store and turns the uniform matrix loads below into vector loads)
     asm("" : "+v"(in_radius), "+v"(ga[0]), "+v"(ga[1]), "+v"(ga[2]), "+v"(ga[3]), "+v"(ga[4]), "+v"(ga[5]), "+v"(ga[6]), "+v"(ga[7]), "+v"(ga[8]), "+v"(ga[9]), "+v"(in_co.x), "+v"(in_co.y), "+v"(in_co.z), "+v"(in_co.w));
     asm("" : "+v"(in_m[0]), "+v"(in_m[1]), "+v"(in_m[2]), "+v"(in_c3[0]), "+v"(in_c3[1]), "+v"(in_c3[2]), "+v"(in_c3[3]), "+v"(in_c3[4]), "+v"(in_c3[5]), "+v"(in_q[0]), "+v"(in_q[1]), "+v"(in_q[2]), "+v"(in_q[3]), "+v"(in_s[0]), "+v"(in_s[1]), "+v"(in_s[2]), "+v"(in_cl), "+v"(in_qraw.x), "+v"(in_qraw.y), "+v"(in_qraw.z), "+v"(in_qraw.w));
+    if (RAW) {
+        in_qraw = make_float4(in_q[0], in_q[1], in_q[2], in_q[3]);
+        // (opaque copies: the normalisation's backward below squares them again, contracted as act_rotations_raw's code is; were they
+        // the same values as in_q, the compiler would share the products with mom_quat_norm's uncontracted ones and round otherwise)
+        asm("" : "+v"(in_qraw.x), "+v"(in_qraw.y), "+v"(in_qraw.z), "+v"(in_qraw.w));
+        const float n = mom_quat_norm(in_q[0], in_q[1], in_q[2], in_q[3]);
+#pragma unroll
+        for (int i = 0; i < 4; i++) in_q[i] = in_q[i] / n;
+#pragma unroll
+        for (int i = 0; i < 3; i++) in_s[i] = expf(in_s[i]);
+    }
+    const bool through_act = RAW || a.rots_raw != nullptr;
     if (idx < a.P) {
     const float* __restrict__ view = a.view;
     const float* __restrict__ proj = a.proj;
@@ -146,8 +165,14 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdArgs a)
     a.dmeans2D[3 * idx + 0] = ga[0];
     a.dmeans2D[3 * idx + 1] = ga[1];
     a.dmeans2D[3 * idx + 2] = 0.f;
-    // (act_rotations_raw: through the sigmoid, y (1 - y) of the opacity the forward kept in its record -- optim_loss.hip, act_bwd_kernel)
-    a.dopacity[idx] = a.rots_raw ? ga[5] * ((1.0f - in_co.w) * in_co.w) : ga[5];
+    if (a.st_accum && vis && !(a.st_skip && *a.st_skip)) {
+        // densification statistics (mom_densify_stats, optim_loss.hip): the same update from the values just written to dmeans2D
+        a.st_maxr[idx] = fmaxf(a.st_maxr[idx], (float)in_radius);
+        a.st_accum[idx] += mom_grad_norm2d(ga[0], ga[1]);
+        a.st_denom[idx] += 1.0f;
+    }
+    // (act_rotations_raw / RAW: through the sigmoid, y (1 - y) of the opacity the forward kept in its record -- optim_loss.hip, act_bwd_kernel)
+    a.dopacity[idx] = through_act ? ga[5] * ((1.0f - in_co.w) * in_co.w) : ga[5];
     a.dcolors[3 * idx + 0] = ga[6];
     a.dcolors[3 * idx + 1] = ga[7];
     a.dcolors[3 * idx + 2] = ga[8];
@@ -360,7 +385,7 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdArgs a)
     for (int i = 0; i < 3; i++) a.dmeans3D[3 * idx + i] = dmean[i];
 #pragma unroll
     for (int i = 0; i < 6; i++) a.dcov3D[6 * idx + i] = dcov[i];
-    if (a.rots_raw) {
+    if (through_act) {
         // through exp (d = g * exp(raw) = g * scale) and through q / max(|q|, eps) (zero through the clamp, as ATen does): the
         // arithmetic of act_bwd_kernel (optim_loss.hip), operation for operation
 #pragma unroll
@@ -422,13 +447,20 @@ int mom_launch_preprocess_bwd(const MomRasterArgs* a, const int* radii, const Ge
     b.dscales2 = a->scales ? gr->dL_dscales_copy : nullptr;
     b.drot2 = a->scales ? gr->dL_drotations_copy : nullptr;
     b.rots_raw = gr->act_rotations_raw;                      // (raster_api.hip, check_grads: only with scales and rotations present)
+    b.st_maxr = gr->stats_max_radii2D; b.st_accum = gr->stats_grad_accum; b.st_denom = gr->stats_denom;   // (check_grads: all or none)
+    b.st_skip = gr->stats_skip_if_nonzero;
     MomProfScope ps(MOM_P_PRE_BWD, s);
     const int sh_stride = (a->M - 1) * 3;
     const bool staged = b.colors_from_sh && b.shs_rest && b.dsh_rest && (sh_stride & 1) && sh_stride <= 45 &&
                         ((uintptr_t)b.shs_rest & 15) == 0 && ((uintptr_t)b.dsh_rest & 15) == 0;
-    if (staged)
-        hipLaunchKernelGGL(preprocess_bwd_kernel<true>, dim3((a->P + 255) / 256), dim3(256), (size_t)256 * sh_stride * 4, s, b);
+    const dim3 grid((a->P + 255) / 256);
+    if (staged && a->params_raw)
+        hipLaunchKernelGGL((preprocess_bwd_kernel<true, true>), grid, dim3(256), (size_t)256 * sh_stride * 4, s, b);
+    else if (staged)
+        hipLaunchKernelGGL((preprocess_bwd_kernel<true, false>), grid, dim3(256), (size_t)256 * sh_stride * 4, s, b);
+    else if (a->params_raw)
+        hipLaunchKernelGGL((preprocess_bwd_kernel<false, true>), grid, dim3(256), 0, s, b);
     else
-        hipLaunchKernelGGL(preprocess_bwd_kernel<false>, dim3((a->P + 255) / 256), dim3(256), 0, s, b);
+        hipLaunchKernelGGL((preprocess_bwd_kernel<false, false>), grid, dim3(256), 0, s, b);
     return hipGetLastError() == hipSuccess ? MOM_OK : MOM_ELAUNCH;
 }

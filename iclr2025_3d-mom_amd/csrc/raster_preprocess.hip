@@ -61,7 +61,10 @@ struct PreArgs {
 // decisions as a 64-bit mask per Gaussian and the workgroup flushes its histogram with one global atomic per non-empty tile --
 // what tile_hist_kernel did in a launch of its own (27 us at 200 k Gaussians, most of it waiting for the records this kernel
 // still holds in registers).  The caller clears the header and the counters with a fill command in front of this kernel.
-template <bool STAGED, bool HIST>
+// RAW (MomRasterArgs.params_raw): scales / rotations / opacities are the model's raw parameters and the activations of render()
+// (exp, normalize, sigmoid: gaussian_renderer/__init__.py:130-132) are applied here, in registers, with the helpers
+// mom_activations_forward uses (optim_loss.hip, act_fwd_kernel) -- the same bits as that kernel's output fed to this one.
+template <bool STAGED, bool HIST, bool RAW>
 __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreArgs a, int* __restrict__ radii, float4* __restrict__ rec,
                                                             float* __restrict__ cov3Ds, uchar4* __restrict__ clamped,
                                                             uint32_t* __restrict__ zero_words, int n_zero, int sh_floats)
@@ -132,6 +135,14 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreArgs a, int* __r
     asm("" : "+v"(px), "+v"(py), "+v"(pz), "+v"(in_c3[0]), "+v"(in_c3[1]), "+v"(in_c3[2]), "+v"(in_c3[3]), "+v"(in_c3[4]), "+v"(in_c3[5]),
         "+v"(in_s[0]), "+v"(in_s[1]), "+v"(in_s[2]), "+v"(in_q[0]), "+v"(in_q[1]), "+v"(in_q[2]), "+v"(in_q[3]), "+v"(in_col[0]),
         "+v"(in_col[1]), "+v"(in_col[2]), "+v"(in_opacity));
+    if (RAW) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) in_s[i] = expf(in_s[i]);
+        const float n = mom_quat_norm(in_q[0], in_q[1], in_q[2], in_q[3]);
+#pragma unroll
+        for (int i = 0; i < 4; i++) in_q[i] = in_q[i] / n;
+        in_opacity = mom_sigmoid(in_opacity);
+    }
     if (!HIST && idx >= a.P) return;
     const float* __restrict__ view = a.view;
     const float* __restrict__ proj = a.proj;
@@ -289,6 +300,26 @@ __global__ void mark_visible_kernel(int P, const float* __restrict__ means, cons
     present[idx] = vz <= 0.2f ? 0 : 1;
 }
 
+template <typename K>
+int set_lds_limit(K kernel)
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024) != hipSuccess;
+}
+
+template <bool RAW>
+void launch_fwd(bool staged, bool hist, int blocks, size_t lds, hipStream_t s, const PreArgs& p, int* radii, float4* rec, float* cov,
+                uchar4* cl, uint32_t* zero_words, int n_zero, int sh_floats)
+{
+    if (hist && staged)
+        hipLaunchKernelGGL((preprocess_fwd_kernel<true, true, RAW>), dim3(blocks), dim3(256), lds, s, p, radii, rec, cov, cl, zero_words, n_zero, sh_floats);
+    else if (hist)
+        hipLaunchKernelGGL((preprocess_fwd_kernel<false, true, RAW>), dim3(blocks), dim3(256), lds, s, p, radii, rec, cov, cl, zero_words, n_zero, sh_floats);
+    else if (staged)
+        hipLaunchKernelGGL((preprocess_fwd_kernel<true, false, RAW>), dim3(blocks), dim3(256), lds, s, p, radii, rec, cov, cl, zero_words, n_zero, sh_floats);
+    else
+        hipLaunchKernelGGL((preprocess_fwd_kernel<false, false, RAW>), dim3(blocks), dim3(256), 0, s, p, radii, rec, cov, cl, zero_words, n_zero, sh_floats);
+}
+
 }  // namespace
 
 // host launcher (called from raster_api.hip).  hist_counts / hist_reach non-null: the tile histogram rides in the projection kernel
@@ -330,22 +361,16 @@ int mom_launch_preprocess_fwd(const MomRasterArgs* a, const GeomView& g, int* ra
         if (hipMemsetAsync(zero_words, 0, (size_t)n_zero * 4, s) != hipSuccess) return MOM_ELAUNCH;
         static bool attr_set = false;
         if (!attr_set) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_fwd_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    112 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_fwd_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    112 * 1024) != hipSuccess)
+            if (set_lds_limit(preprocess_fwd_kernel<true, true, false>) || set_lds_limit(preprocess_fwd_kernel<false, true, false>) ||
+                set_lds_limit(preprocess_fwd_kernel<true, true, true>) || set_lds_limit(preprocess_fwd_kernel<false, true, true>))
                 return MOM_ELAUNCH;
             attr_set = true;
         }
-        if (staged)
-            hipLaunchKernelGGL((preprocess_fwd_kernel<true, true>), dim3(blocks), dim3(256), lds, s, p, radii, g.rec, cov, cl, zero_words, n_zero, sh_floats);
-        else
-            hipLaunchKernelGGL((preprocess_fwd_kernel<false, true>), dim3(blocks), dim3(256), lds, s, p, radii, g.rec, cov, cl, zero_words, n_zero, sh_floats);
-    } else if (staged) {
-        hipLaunchKernelGGL((preprocess_fwd_kernel<true, false>), dim3(blocks), dim3(256), lds, s, p, radii, g.rec, cov, cl, zero_words, n_zero, sh_floats);
-    } else {
-        hipLaunchKernelGGL((preprocess_fwd_kernel<false, false>), dim3(blocks), dim3(256), 0, s, p, radii, g.rec, cov, cl, zero_words, n_zero, sh_floats);
     }
+    if (a->params_raw)
+        launch_fwd<true>(staged, hist, blocks, lds, s, p, radii, g.rec, cov, cl, zero_words, n_zero, sh_floats);
+    else
+        launch_fwd<false>(staged, hist, blocks, lds, s, p, radii, g.rec, cov, cl, zero_words, n_zero, sh_floats);
     return hipGetLastError() == hipSuccess ? MOM_OK : MOM_ELAUNCH;
 }
 

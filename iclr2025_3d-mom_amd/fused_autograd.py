@@ -160,7 +160,13 @@ def _forward(pc, cam, bg, delta_scale, scaling_modifier, debug):
     a.prefiltered, a.debug = 0, int(bool(debug))
     a.keep_all_tiles = int(RC._state["keep_all_tiles"])       # set_keep_all_tiles(): the reference's lists and num_rendered
     st.keep = (bg, view, proj, campos, keep)
-    nr_dev = b["nr_dev"]
+    _raster_forward(lib, a, st, b["nr_dev"], P, W, H, dev, s)
+    return st
+
+
+def _raster_forward(lib, a, st, nr_dev, P, W, H, dev, s):
+    """Projection, binning and compositing of one render() call into st.color / st.depth / st.radii, with the binning capacity
+    of the rasterizer module's sync mode; leaves st.binning and st.cap for the backward."""
     nr_host = RC.pinned_word()
     N.check(lib.mom_raster_forward_geometry(C.byref(a), st.geom.data_ptr(), st.img.data_ptr(), st.radii.data_ptr(), nr_dev.data_ptr(),
                                             nr_host.data_ptr(), s), "raster_geometry")
@@ -197,7 +203,6 @@ def _forward(pc, cam, bg, delta_scale, scaling_modifier, debug):
         N.check(lib.mom_raster_forward_render(C.byref(a), st.geom.data_ptr(), st.binning.data_ptr(), cap, st.img.data_ptr(),
                                               st.color.data_ptr(), st.depth.data_ptr(), flag.data_ptr(), s), "raster_render")
         state["pending"].append((slot, nr_host, state["serial"]))
-    return st
 
 
 def _field_grads(st, f, direct=True):
@@ -366,6 +371,136 @@ class FusedRenderFunction(torch.autograd.Function):
         # through the graph (fresh buffers: nothing is accumulated in place on this path); inputs that were not asked for get None
         out = [g if n else None for g, n in zip((gxyz, gdc, grest, gsc, grot, gop, *gplanes, *gmlp), needs)]
         return (None, None, None, None, None, None, g2d, *out)
+
+
+# ---------------------------------------------------------------------------------------------------------- coarse stage
+# The coarse stage (train_4DGS.py with stage "coarse": the first 3 000 iterations of every run) renders the Gaussians without the
+# deformation field, so its render() is the rasterizer alone on exp / normalize / sigmoid of the parameters
+# (gaussian_renderer/__init__.py:113,130-132).  As one node: the projection reads the RAW parameters and applies the activations in
+# registers (MomRasterArgs.params_raw), the backward writes the six parameter gradients through them -- no activated copies, no
+# activation nodes, no separate rasterizer node.
+
+def applies_coarse(cam, pc, pipe, stage, override_color, cam_type):
+    """The conditions of applies() without the deformation ones, for stage "coarse"."""
+    if not torch.is_grad_enabled() or stage != "coarse" or override_color is not None or cam_type == "PanopticSports":
+        return False
+    if pipe.compute_cov3D_python or pipe.convert_SHs_python or not hasattr(cam, "device_tensors"):
+        return False
+    if not pc.get_xyz.is_cuda or pc.get_xyz.shape[0] == 0 or ops.BACKEND.name != "hip":
+        return False
+    if getattr(pipe, "per_op_autograd", False):
+        return False
+    return pc._features_rest.shape[1] == 15
+
+
+class _CoarseState:
+    __slots__ = ("pool_key", "bufs", "a", "keep", "P", "color", "depth", "radii", "geom", "img", "binning", "cap")
+
+
+def _forward_coarse(pc, cam, bg, scaling_modifier, debug):
+    lib, s = N.lib(), N.current_stream()
+    st = _CoarseState()
+    dev = pc._xyz.device
+    P = st.P = pc._xyz.shape[0]
+    W, H = int(cam.image_width), int(cam.image_height)
+    view, proj, campos, _ = cam.device_tensors(dev)
+    xyz, scal, rotq, opac = pc._xyz.detach(), pc._scaling.detach(), pc._rotation.detach(), pc._opacity.detach()
+    f_dc, f_rest = pc._features_dc.detach(), pc._features_rest.detach()
+    for t in (xyz, scal, rotq, opac, f_dc, f_rest):
+        if not t.is_contiguous():
+            raise N.MomError("fused render(): the Gaussian parameters must be contiguous")
+    st.pool_key = (P, W, H, dev, s, "coarse")
+    b = st.bufs = _pool_take(st.pool_key)
+    if b is None:
+        b = st.bufs = {"geom": torch.empty(lib.mom_raster_geom_bytes(P), dtype=torch.uint8, device=dev),
+                       "img": torch.empty(lib.mom_raster_image_bytes(W, H), dtype=torch.uint8, device=dev),
+                       "nr_dev": torch.empty(1, dtype=torch.int32, device=dev)}
+    st.color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+    st.depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    st.radii = torch.empty(P, dtype=torch.int32, device=dev)
+    st.geom, st.img = b["geom"], b["img"]
+    a = st.a = N.MomRasterArgs()
+    a.P, a.D, a.M, a.W, a.H = P, pc.active_sh_degree, 16, W, H
+    a.background, a.means3D = bg.data_ptr(), xyz.data_ptr()
+    a.shs, a.shs_rest = f_dc.data_ptr(), f_rest.data_ptr()
+    a.colors_precomp, a.cov3D_precomp = None, None
+    a.params_raw = 1                        # exp / normalize / sigmoid in the projection kernel
+    a.opacities, a.scales, a.rotations = opac.data_ptr(), scal.data_ptr(), rotq.data_ptr()
+    a.viewmatrix, a.projmatrix, a.campos = view.data_ptr(), proj.data_ptr(), campos.data_ptr()
+    a.scale_modifier = float(scaling_modifier)
+    a.tan_fovx, a.tan_fovy = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
+    a.prefiltered, a.debug = 0, int(bool(debug))
+    a.keep_all_tiles = int(RC._state["keep_all_tiles"])
+    st.keep = (bg, view, proj, campos, xyz, scal, rotq, opac, f_dc, f_rest)      # what the pointers in `a` point at
+    _raster_forward(lib, a, st, b["nr_dev"], P, W, H, dev, s)
+    return st
+
+
+def _backward_coarse(st, dcolor, ddepth):
+    lib, s = N.lib(), N.current_stream()
+    P, dev = st.P, st.color.device
+    f = dict(dtype=torch.float32, device=dev)
+    e = lambda *sh: torch.empty(*sh, **f)
+    dcol = dcolor.contiguous().float()
+    ddep = None if ddepth is None else ddepth.contiguous().float()
+    b = st.bufs
+    if "gcol" not in b:
+        b.update(gcol=e(P, 3), gcov=e(P, 6))
+    g2d, gxyz, gdc, grest = e(P, 3), e(P, 3), e(P, 1, 3), e(P, 15, 3)
+    gsc, grot, gop = e(P, 3), e(P, 4), e(P, 1)
+    gr = N.MomRasterGrads()
+    gr.dL_dmeans2D, gr.dL_dcolors, gr.dL_dopacity = g2d.data_ptr(), b["gcol"].data_ptr(), gop.data_ptr()
+    gr.dL_dmeans3D, gr.dL_dcov3D = gxyz.data_ptr(), b["gcov"].data_ptr()
+    gr.dL_dsh, gr.dL_dsh_rest = gdc.data_ptr(), grest.data_ptr()
+    gr.dL_dscales, gr.dL_drotations = gsc.data_ptr(), grot.data_ptr()
+    N.check(lib.mom_raster_backward(C.byref(st.a), st.radii.data_ptr(), st.geom.data_ptr(), st.binning.data_ptr(), st.cap,
+                                    st.img.data_ptr(), dcol.data_ptr(), None if ddep is None else ddep.data_ptr(), C.byref(gr), s),
+            "raster_bwd")
+    _pool_give(st.pool_key, b)
+    st.bufs = None
+    return g2d, gxyz, gdc, grest, gsc, grot, gop
+
+
+class FusedCoarseRenderFunction(torch.autograd.Function):
+    """(image, depth, radii) = coarse-stage render of one camera; inputs after the five plain arguments: the 2-D gradient holder
+    and the six Gaussian parameter tensors."""
+
+    @staticmethod
+    def forward(ctx, pc, cam, bg, scaling_modifier, debug, screenspace, xyz, f_dc, f_rest, scaling, rotation, opacity):
+        st = _forward_coarse(pc, cam, bg, scaling_modifier, debug)
+        ctx.st, ctx.pc = st, pc
+        ctx.mark_non_differentiable(st.radii)
+        return st.color, st.depth, st.radii
+
+    @staticmethod
+    def backward(ctx, dcolor, ddepth, _dradii):
+        st = ctx.st
+        if st is None:
+            raise RuntimeError("render(): a second backward through the same call -- its buffers were released after the first "
+                               "(render again, or set pipe.per_op_autograd = True for retain_graph use)")
+        ctx.st = None
+        pc = ctx.pc
+        params = (pc._xyz, pc._features_dc, pc._features_rest, pc._scaling, pc._rotation, pc._opacity)
+        needs = ctx.needs_input_grad[6:]
+        direct = DIRECT_GRADS and ops.direct_grads_ok(params, needs)
+        g2d, *grads = _backward_coarse(st, dcolor, ddepth)
+        if direct:
+            # (as FusedRenderFunction: the parameter gradients are handed to the parameters, only the 2-D holder goes through the graph)
+            for p, g in zip(params, grads):
+                if p.grad is None:
+                    p.grad = g
+                else:
+                    p.grad.add_(g)
+            opt = getattr(pc, "optimizer", None)
+            if opt is not None and hasattr(opt, "early_hint"):
+                opt.early_hint = None
+            return (None, None, None, None, None, g2d) + (None,) * 6
+        return (None, None, None, None, None, g2d, *[g if n else None for g, n in zip(grads, needs)])
+
+
+def render_coarse(cam, pc, pipe, bg, scaling_modifier, screenspace_points):
+    return FusedCoarseRenderFunction.apply(pc, cam, bg, scaling_modifier, pipe.debug, screenspace_points, pc._xyz,
+                                           pc._features_dc, pc._features_rest, pc._scaling, pc._rotation, pc._opacity)
 
 
 def render(cam, pc, pipe, bg, delta_scale, scaling_modifier, screenspace_points):

@@ -1,5 +1,6 @@
 """Forward-only rendering of one camera as a fixed launch sequence: HexPlane -> deformation MLP -> activations ->
-projection / binning / sort / compositing.  gaussian_renderer.render() takes this path when gradients are disabled and the
+projection / binning / sort / compositing (coarse stage: the projection on the raw parameters, MomRasterArgs.params_raw, and
+nothing in front of it).  gaussian_renderer.render() takes this path when gradients are disabled and the
 model has the shipped configuration (the case of render_4DGS.py and of every evaluation render): the same kernels as the
 fused training step, no SH concatenation (the rasterizer reads the DC and the rest coefficients through two pointers), no
 gradient holder, no per-op allocation of intermediates.  Only the returned image, depth and radii are fresh tensors --
@@ -83,14 +84,34 @@ class FusedRender:
                     raise N.MomError(f"async render(): frame {serial} never posted its status (slot {slot} holds {v:#x})")
         return v & 0xFFFFFFFF
 
-    def render(self, cam, bg, delta_scale, scaling_modifier=1.0, debug=False, order=False):
-        """order: the field's processing order if the caller already has it (FusedRenderPool takes it on the caller's stream)."""
+    def render(self, cam, bg, delta_scale, scaling_modifier=1.0, debug=False, order=False, stage="fine"):
+        """order: the field's processing order if the caller already has it (FusedRenderPool takes it on the caller's stream).
+        stage "coarse": no deformation field; the rasterizer reads the raw parameters and activates them itself."""
         g, lib, s = self.g, self.lib, N.current_stream()
         dev = g._xyz.device
         P = g._xyz.shape[0]
         W, H = int(cam.image_width), int(cam.image_height)
         self._ensure(P, W, H, dev)
         view, proj, campos, _ = cam.device_tensors(dev)
+        if stage == "coarse":
+            pts, sc, rot, op = (t.detach() for t in (g._xyz, g._scaling, g._rotation, g._opacity))
+            for t in (pts, sc, rot, op, g._features_dc, g._features_rest):
+                if not t.is_contiguous():
+                    raise N.MomError("fused render(): the Gaussian parameters must be contiguous")
+        else:
+            self._deform(g, cam, delta_scale, order, P, dev, s)
+            pts, sc, rot, op = self.pts, self.sc, self.rot, self.op
+        a = N.MomRasterArgs()
+        a.P, a.D, a.M, a.W, a.H = P, g.active_sh_degree, 16, W, H
+        a.background, a.means3D = bg.data_ptr(), pts.data_ptr()
+        a.shs, a.shs_rest = g._features_dc.data_ptr(), g._features_rest.data_ptr()
+        a.colors_precomp, a.opacities = None, op.data_ptr()
+        a.scales, a.rotations, a.cov3D_precomp = sc.data_ptr(), rot.data_ptr(), None
+        a.params_raw = int(stage == "coarse")
+        return self._raster(a, cam, view, proj, campos, scaling_modifier, debug, P, W, H, dev, s)
+
+    def _deform(self, g, cam, delta_scale, order, P, dev, s):
+        lib = self.lib
         dn = g._deformation.deformation_net
         field = dn.grid
         xyz, scal, rot, opac = g._xyz.detach(), g._scaling.detach(), g._rotation.detach(), g._opacity.detach()
@@ -115,12 +136,9 @@ class FusedRender:
         ops.field_forward(hp, md, P, xyz, float(cam.time), order, scal, rot, flow, float(delta_scale * cam.frame_num), self.pts,
                           self.sc_d, self.rot_d, None, None, opac, self.sc, self.rot, self.op, s, scratch_feat=self.feat,
                           scratch=self._fscratch)
-        a = N.MomRasterArgs()
-        a.P, a.D, a.M, a.W, a.H = P, g.active_sh_degree, 16, W, H
-        a.background, a.means3D = bg.data_ptr(), self.pts.data_ptr()
-        a.shs, a.shs_rest = g._features_dc.data_ptr(), g._features_rest.data_ptr()
-        a.colors_precomp, a.opacities = None, self.op.data_ptr()
-        a.scales, a.rotations, a.cov3D_precomp = self.sc.data_ptr(), self.rot.data_ptr(), None
+
+    def _raster(self, a, cam, view, proj, campos, scaling_modifier, debug, P, W, H, dev, s):
+        lib = self.lib
         a.viewmatrix, a.projmatrix, a.campos = view.data_ptr(), proj.data_ptr(), campos.data_ptr()
         a.scale_modifier = float(scaling_modifier)
         a.tan_fovx, a.tan_fovy = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
@@ -218,7 +236,7 @@ class FusedRenderPool:
             if v:
                 sl.bad = []
 
-    def render(self, cam, bg, delta_scale, scaling_modifier=1.0, debug=False):
+    def render(self, cam, bg, delta_scale, scaling_modifier=1.0, debug=False, stage="fine"):
         g = self.g
         k = self.count % self.n
         sl, st = self.slots[k], self.streams[k]
@@ -226,7 +244,7 @@ class FusedRenderPool:
         # whatever is created lazily and cached for later frames is created on the CALLER's stream, which the slot's stream then
         # waits for: the camera's device copies, the field's processing order (rebuilt every 64 calls)
         cam.device_tensors(dev)
-        order = g._deformation.deformation_net.grid._processing_order(g._xyz.detach())
+        order = None if stage == "coarse" else g._deformation.deformation_net.grid._processing_order(g._xyz.detach())
         # ... but only if that stream has anything pending: a marker on it per frame puts traffic on its hardware queue, which one of
         # the slots' streams may share (four hardware queues per device: after a training run -- two streams -- a three-slot pool
         # fell from 5700 to 4400 frames/s through such a collision)
@@ -234,7 +252,7 @@ class FusedRenderPool:
         if not cur.query():
             st.wait_stream(cur)
         with torch.cuda.stream(st):
-            color, depth, radii = sl.render(cam, bg, delta_scale, scaling_modifier, debug, order=order)
+            color, depth, radii = sl.render(cam, bg, delta_scale, scaling_modifier, debug, order=order, stage=stage)
             visible = radii > 0
             ev = torch.cuda.Event()
             ev.record(st)

@@ -30,14 +30,16 @@ def render_streams():
 
 
 def _nograd_fast_path_applies(cam, pc, pipe, stage, override_color, cam_type):
-    """Forward-only launch sequence (fused_render.py): no gradients wanted, fine stage, the shipped deformation configuration,
-    SH colours and covariances computed by the rasterizer, an ordinary camera, everything on the GPU."""
-    if torch.is_grad_enabled() or stage != "fine" or override_color is not None or cam_type == "PanopticSports":
+    """Forward-only launch sequence (fused_render.py): no gradients wanted, fine stage with the shipped deformation configuration
+    or coarse stage, SH colours and covariances computed by the rasterizer, an ordinary camera, everything on the GPU."""
+    if torch.is_grad_enabled() or stage not in ("fine", "coarse") or override_color is not None or cam_type == "PanopticSports":
         return False
     if pipe.compute_cov3D_python or pipe.convert_SHs_python or not hasattr(cam, "device_tensors"):
         return False
     if not pc.get_xyz.is_cuda or pc.get_xyz.shape[0] == 0 or ops.BACKEND.name != "hip":
         return False
+    if stage == "coarse":
+        return pc._features_rest.shape[1] == 15
     dn = getattr(pc._deformation, "deformation_net", None)
     return dn is not None and hasattr(dn, "_fusable") and dn._fusable() and pc._features_rest.shape[1] == 15
 
@@ -57,7 +59,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         if pool is None or pool.n != _RENDER_STREAMS:
             from ..fused_render import FusedRenderPool
             pool = pc._fused_render_pool = FusedRenderPool(pc, _RENDER_STREAMS)
-        image, depth, radii, visible, stream, ready = pool.render(viewpoint_camera, bg_color, delta_scale, scaling_modifier, pipe.debug)
+        image, depth, radii, visible, stream, ready = pool.render(viewpoint_camera, bg_color, delta_scale, scaling_modifier, pipe.debug,
+                                                                  stage=stage)
         return {"render": image, "viewspace_points": pool.zero_points(), "visibility_filter": visible, "radii": radii,
                 "depth": depth, "flow_loss": 0, "stream": stream, "ready": ready}
     if _nograd_fast_path_applies(viewpoint_camera, pc, pipe, stage, override_color, cam_type):
@@ -66,7 +69,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
             from ..fused_render import FusedRender
             fr = pc._fused_render = FusedRender(pc)
         image, depth, radii = fr.render(viewpoint_camera, bg_color, delta_scale, scaling_modifier,
-                                        pipe.debug)
+                                        pipe.debug, stage=stage)
         return {"render": image, "viewspace_points": torch.zeros_like(means3D), "visibility_filter": radii > 0, "radii": radii,
                 "depth": depth, "flow_loss": 0}
     # gradient holder for the 2D means (read back by the densification statistics, train_4DGS.py:227-229)
@@ -81,6 +84,11 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         # the op-by-op path below
         image, depth, radii = fused_autograd.render(viewpoint_camera, pc, pipe, bg_color, delta_scale, scaling_modifier,
                                                     screenspace_points)
+        return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
+                "depth": depth, "flow_loss": 0}
+    if fused_autograd.applies_coarse(viewpoint_camera, pc, pipe, stage, override_color, cam_type):
+        # the coarse stage's forward (raw-parameter projection + binning + compositing) as one autograd node, likewise
+        image, depth, radii = fused_autograd.render_coarse(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, screenspace_points)
         return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
                 "depth": depth, "flow_loss": 0}
 

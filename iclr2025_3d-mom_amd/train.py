@@ -27,11 +27,15 @@ class Trainer:
         self.ema_loss, self.ema_psnr = 0.0, 0.0
         self.last = {}
         self.dist = None     # set by parallel.attach(): camera-batch shard, one camera per rank
-        # fused=True: the iteration runs as an explicit launch sequence (fused_step.py) instead of render()+autograd
+        # fused=True: the iteration runs as an explicit launch sequence (fused_step.py; coarse stage: fused_coarse.py) instead of
+        # render()+autograd
         self.fused = None
         if fused and stage == "fine" and opt.batch_size == 1:
             from .fused_step import FusedStep
             self.fused = FusedStep(gaussians, opt, hyper, self.background)
+        elif fused and stage == "coarse" and opt.batch_size == 1:
+            from .fused_coarse import FusedCoarseStep
+            self.fused = FusedCoarseStep(gaussians, opt, hyper, self.background)
         # every fused step since the last verified one: (serial, iteration, camera); and the overflow-word read-backs in flight:
         # (serial of the last step they cover, ring slot, event)
         self._log = deque()
@@ -258,12 +262,19 @@ class Trainer:
             # the reference's step() then skips them: train_4DGS.py:266-297)
             early = None
             self._stats_done = False
-            if iteration < self.opt.iterations and not self._boundary(iteration):
+            coarse = self.stage == "coarse"
+            if iteration < self.opt.iterations and not self._boundary(iteration) and not coarse:
                 early = self._early_adam
                 self._early_iter = iteration
                 g_ = self.g
                 g_.optimizer.ensure_state([g_._features_dc, g_._features_rest, g_._scaling, g_._rotation, g_._opacity])
-            loss, radii, vsp_grad = self.fused.forward_backward(cam, self.delta_scale, early_adam=early)
+            if coarse:
+                # (no deformation backward to hide Adam under; the densification statistics ride in the projection backward)
+                loss, radii, vsp_grad = self.fused.forward_backward(cam, self.delta_scale,
+                                                                    stats=iteration < self.opt.densify_until_iter)
+                self._stats_done = self.fused.stats_done
+            else:
+                loss, radii, vsp_grad = self.fused.forward_backward(cam, self.delta_scale, early_adam=early)
             self.g.optimizer.skip_flag = self._skip = self.fused.flags
             if self.dist is not None:
                 # the step began its all-reduces as each bucket became final (fused_step.py); radii and vsp_grad come

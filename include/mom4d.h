@@ -52,7 +52,7 @@ typedef void* mom_stream_t; /* hipStream_t */
  *   - MomRasterArgs, the struct that changes most often, additionally starts with `struct_size`: every entry point that
  *     takes it returns MOM_EINVAL unless struct_size == sizeof(MomRasterArgs) of the library.
  * (The reference's counterpart is a C++ static-method signature, rasterizer.h:19-87: there the compiler checks it.) */
-#define MOM_ABI_VERSION 7
+#define MOM_ABI_VERSION 8
 /* floats per Gaussian of the compositing backward's accumulator record (mom_raster_layout().geom_gacc); ten are used.  (A build with
  * -DMOM_GACC_FLOATS=16 pads the record to one 64-byte line: a device-scope atomic costs the device by the LINES an instruction
  * touches and 48-byte records straddle 1.5 on average -- but the shipped kernel's atomics hide under its arithmetic, and the larger
@@ -144,6 +144,13 @@ typedef struct MomRasterArgs {
      * shard's loss is the mean over the ranks' cameras (train_4DGS.py:189-229), so every rank's gradient image carries 1 / world: with
      * the factor here there is no scaling pass over the gradient image behind the forward.  The sums are not scaled. */
     float l1_grad_scale;
+    /* !=0: scales, rotations and opacities hold the model's RAW parameters (_scaling, _rotation, _opacity) and the projection applies
+     * render()'s activations itself, in registers -- exp, normalize, sigmoid (gaussian_renderer/__init__.py:130-132 of the coarse
+     * stage, scene/gaussian_model.py:60-75): radii, rectangles, depth keys, conics, colours and the image are bit-identical to
+     * mom_activations_forward followed by a call without the flag, and no activated copies exist in memory.  The backward (same args)
+     * then writes dL_dscales / dL_drotations / dL_dopacity w.r.t. the raw values, as act_rotations_raw does.  Requires scales and
+     * rotations; refused (MOM_EINVAL) with cov3D_precomp, and in the backward together with act_rotations_raw. */
+    int params_raw;
 } MomRasterArgs;
 
 /* Scratch sizing (bytes).  The three buffers play the roles of the reference's
@@ -199,6 +206,15 @@ typedef struct MomRasterGrads {
      * that makes the values, not from two copy launches behind it. */
     float* dL_dscales_copy;
     float* dL_drotations_copy;
+    /* Optional densification statistics epilogue (all three null: off; given in part: MOM_EINVAL).  The projection backward holds every
+     * Gaussian's radius and dL/d mean2D in registers and performs the update of mom_densify_stats on these [P] accumulators in place
+     * (train_4DGS.py:266, scene/gaussian_model.py:713-715 add_densification_stats): for radii[i] > 0, max_radii2D = max(., radius),
+     * xyz_gradient_accum += |dL_dmeans2D[i, :2]|, denom += 1 -- the same bits as that function on the written dL_dmeans2D, without its
+     * launch and its pass.  stats_skip_if_nonzero (device word, may be null; only with the accumulators) as in mom_adam_step. */
+    float* stats_max_radii2D;
+    float* stats_grad_accum;
+    float* stats_denom;
+    const uint32_t* stats_skip_if_nonzero;
 } MomRasterGrads;
 
 /* Backward (Rasterizer::backward, rasterizer_impl.cu:343-444): render backward

@@ -1,0 +1,342 @@
+"""The coarse stage (no deformation field) on its three accelerated paths -- the fused step (fused_coarse.py), render() as one
+autograd node (fused_autograd.render_coarse) and the no-grad fast path -- against the op-by-op autograd path, and the raw-parameter
+projection kernels (MomRasterArgs.params_raw, MomRasterGrads.stats_*) against the activation kernel + the plain projection."""
+import ctypes as C
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+TINY = dict(P=6000, F=4, W=160, H=96, time_res=10, name="tiny")
+C2 = dict(P=200_000, F=60, W=960, H=540, time_res=50, name="c2")
+
+
+def _mods():
+    return (importlib.import_module("iclr2025_3d-mom_amd.arguments"), importlib.import_module("iclr2025_3d-mom_amd.scene"),
+            importlib.import_module("iclr2025_3d-mom_amd.train"), importlib.import_module("iclr2025_3d-mom_amd._native"))
+
+
+def _coarse_state(cfg, fused=False, per_op=False, lambda_dssim=0.0, trained=True, **opt_kw):
+    A, S, T, _ = _mods()
+    args, lp, op, pp, hp = A.default_args(time_resolution=cfg["time_res"])
+    op.lambda_dssim = lambda_dssim
+    for k, v in opt_kw.items():
+        setattr(op, k, v)
+    pp.per_op_autograd = per_op
+    torch.manual_seed(6666)
+    scene = S.SyntheticScene(cfg["P"], cfg["F"], cfg["W"], cfg["H"], seed=6666)
+    g = S.GaussianModel(lp.sh_degree, hp, device=torch.device("cuda"))
+    scene.init_gaussians(g)
+    if trained:
+        scene.make_trained_like(g)
+    trainer = T.Trainer(scene, g, op, hp, pp, stage="coarse", delta_scale=1, sync_every_step=False, fused=fused)
+    return scene, g, trainer
+
+
+# ------------------------------------------------------------------------------------------------ kernels, bit for bit
+def _frame(g, cam, raw, keep_all, D):
+    """Forward + compositing backward through the C ABI.  raw: the projection activates the raw parameters itself; else
+    mom_activations_forward makes activated copies first.  Returns the forward's outputs (as bytes) and what _bwd needs."""
+    _, _, _, N = _mods()
+    lib, s = N.lib(), N.current_stream()
+    dev = g._xyz.device
+    P, W, H = g._xyz.shape[0], int(cam.image_width), int(cam.image_height)
+    f = dict(dtype=torch.float32, device=dev)
+    view, proj, campos, _ = cam.device_tensors(dev)
+    sr, rr, orr = g._scaling.detach(), g._rotation.detach(), g._opacity.detach()
+    sc, rot, op = torch.empty(P, 3, **f), torch.empty(P, 4, **f), torch.empty(P, 1, **f)
+    N.check(lib.mom_activations_forward(P, sr.data_ptr(), rr.data_ptr(), orr.data_ptr(), sc.data_ptr(), rot.data_ptr(),
+                                        op.data_ptr(), s), "act")
+    bg = torch.tensor([0.1, 0.2, 0.3], **f)
+    args = {}
+    for r, (x, y, z) in ((0, (sc, rot, op)), (1, (sr, rr, orr))):
+        a = args[r] = N.MomRasterArgs()
+        a.P, a.D, a.M, a.W, a.H = P, D, 16, W, H
+        a.background, a.means3D = bg.data_ptr(), g._xyz.data_ptr()
+        a.shs, a.shs_rest = g._features_dc.data_ptr(), g._features_rest.data_ptr()
+        a.scales, a.rotations, a.opacities = x.data_ptr(), y.data_ptr(), z.data_ptr()
+        a.viewmatrix, a.projmatrix, a.campos = view.data_ptr(), proj.data_ptr(), campos.data_ptr()
+        a.scale_modifier = 1.0
+        a.tan_fovx, a.tan_fovy = float(np.tan(cam.FoVx * 0.5)), float(np.tan(cam.FoVy * 0.5))
+        a.keep_all_tiles = int(keep_all)
+        a.params_raw = r
+    a = args[int(raw)]
+    geom = torch.empty(lib.mom_raster_geom_bytes(P), dtype=torch.uint8, device=dev)
+    img = torch.empty(lib.mom_raster_image_bytes(W, H), dtype=torch.uint8, device=dev)
+    radii = torch.empty(P, dtype=torch.int32, device=dev)
+    nr_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+    nr_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+    N.check(lib.mom_raster_forward_geometry(C.byref(a), geom.data_ptr(), img.data_ptr(), radii.data_ptr(), nr_dev.data_ptr(),
+                                            nr_host.data_ptr(), s), "geometry")
+    torch.cuda.synchronize()
+    R = int(nr_host[0])
+    cap = R + 64
+    binning = torch.empty(lib.mom_raster_binning_bytes(P, W, H, cap), dtype=torch.uint8, device=dev)
+    color, depth = torch.empty(3, H, W, **f), torch.empty(1, H, W, **f)
+    N.check(lib.mom_raster_forward_render(C.byref(a), geom.data_ptr(), binning.data_ptr(), cap, img.data_ptr(), color.data_ptr(),
+                                          depth.data_ptr(), None, s), "render")
+    torch.manual_seed(1)
+    dcol = torch.randn(3, H, W, **f) * 1e-3
+    N.check(lib.mom_raster_backward_render(C.byref(a), geom.data_ptr(), binning.data_ptr(), cap, img.data_ptr(), dcol.data_ptr(),
+                                           None, s), "backward_render")
+    torch.cuda.synchronize()
+    lay = N.MomRasterLayout()
+    lib.mom_raster_layout(P, W, H, cap, C.byref(lay))
+    gbase = geom[(-geom.data_ptr()) % 256:]
+    ibase = img[(-img.data_ptr()) % 256:]
+    bbase = binning[(-binning.data_ptr()) % 256:]
+    tiles = ((W + 15) // 16) * ((H + 15) // 16)
+    res = {"radii": radii, "rec": gbase[lay.geom_rec:lay.geom_rec + 48 * P], "color": color, "depth": depth,
+           "ranges": ibase[lay.img_ranges:lay.img_ranges + 8 * tiles], "point_list": bbase[lay.bin_point_list:lay.bin_point_list + 4 * R]}
+    fw = {k: v.detach().cpu().numpy().view(np.uint8).copy() for k, v in res.items()}
+    fw["R"] = R
+    return fw, (lib, s, args, radii, geom, rr, P, (sc, rot, op, sr, orr, bg, dcol, binning, img))
+
+
+def _bwd(ctx, raw, stats=None, skip=None):
+    """The projection backward on the frame's compositing record: raw parameters (params_raw), or the activated copies with
+    act_rotations_raw.  Both read the same record, so any difference is the projection backward's own."""
+    lib, s, args, radii, geom, rr, P, _ = ctx
+    _, _, _, N = _mods()
+    f = dict(dtype=torch.float32, device=radii.device)
+    out = {k: torch.empty(*shp, **f) for k, shp in (("g2d", (P, 3)), ("gcol", (P, 3)), ("gop", (P, 1)), ("gxyz", (P, 3)),
+                                                      ("gcov", (P, 6)), ("gdc", (P, 1, 3)), ("grest", (P, 15, 3)),
+                                                      ("gsc", (P, 3)), ("grot", (P, 4)))}
+    gr = N.MomRasterGrads()
+    gr.dL_dmeans2D, gr.dL_dcolors, gr.dL_dopacity = out["g2d"].data_ptr(), out["gcol"].data_ptr(), out["gop"].data_ptr()
+    gr.dL_dmeans3D, gr.dL_dcov3D = out["gxyz"].data_ptr(), out["gcov"].data_ptr()
+    gr.dL_dsh, gr.dL_dsh_rest = out["gdc"].data_ptr(), out["grest"].data_ptr()
+    gr.dL_dscales, gr.dL_drotations = out["gsc"].data_ptr(), out["grot"].data_ptr()
+    if not raw:
+        gr.act_rotations_raw = rr.data_ptr()
+    if stats is not None:
+        gr.stats_max_radii2D, gr.stats_grad_accum, gr.stats_denom = (t.data_ptr() for t in stats)
+        gr.stats_skip_if_nonzero = None if skip is None else skip.data_ptr()
+    N.check(lib.mom_raster_backward_geometry(C.byref(args[int(raw)]), radii.data_ptr(), geom.data_ptr(), C.byref(gr), s), "bwd_geometry")
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy().view(np.uint8).copy() for k, v in out.items()}, out["g2d"]
+
+
+@pytest.mark.parametrize("cfg", [TINY, C2], ids=["tiny", "c2"])
+@pytest.mark.parametrize("D", [0, 3])
+def test_raw_projection_and_its_backward_are_bit_equal_to_the_activation_kernel_path(cfg, D):
+    scene, g, trainer = _coarse_state(cfg)
+    cam = trainer.cams[1]
+    dev = g._xyz.device
+    P = g._xyz.shape[0]
+    ops = importlib.import_module("iclr2025_3d-mom_amd.ops")
+    for keep_all in (False, True):
+        ref, _ = _frame(g, cam, False, keep_all, D)
+        raw, ctx = _frame(g, cam, True, keep_all, D)
+        assert raw["R"] == ref["R"]
+        for k in ref:
+            if k == "R" or (k in ("point_list", "ranges") and not keep_all):
+                continue
+            assert np.array_equal(raw[k], ref[k]), ("forward", k, keep_all, D)
+        radii = ctx[3]
+        assert int((radii > 0).sum()) > 0
+        torch.manual_seed(2)
+        init = (torch.rand(P, device=dev) * 5, torch.rand(P, 1, device=dev), torch.randint(0, 4, (P, 1), device=dev).float())
+        acc = [t.clone() for t in init]
+        gb_ref, g2d = _bwd(ctx, False)
+        gb_raw, _ = _bwd(ctx, True, stats=acc)
+        for k in gb_ref:
+            assert np.array_equal(gb_raw[k], gb_ref[k]), ("backward", k, keep_all, D)
+        # the statistics epilogue == mom_densify_stats on the written screen-space gradient, to the bit
+        want = [t.clone() for t in init]
+        ops.densify_stats(radii, g2d, want[0], want[1], want[2])
+        for x, y in zip(acc, want):
+            assert torch.equal(x, y)
+        # a set skip word: no-op
+        skip = torch.ones(1, dtype=torch.int32, device=dev)
+        acc2 = [t.clone() for t in init]
+        _bwd(ctx, True, stats=acc2, skip=skip)
+        for x, y in zip(acc2, init):
+            assert torch.equal(x, y)
+
+
+# ------------------------------------------------------------------------------------------------ paths against each other
+def _snap(g, opt_state_of=None):
+    out = {"xyz": g._xyz, "f_dc": g._features_dc, "f_rest": g._features_rest, "scaling": g._scaling, "rotation": g._rotation,
+           "opacity": g._opacity, "accum": g.xyz_gradient_accum, "denom": g.denom, "maxr": g.max_radii2D}
+    return {k: v.detach().float().cpu().numpy().copy() for k, v in out.items()}
+
+
+def _untouched(g):
+    """The deformation network, the HexPlane planes and _scene_flow: no gradient, no optimizer state (the reference's coarse stage)."""
+    dn = g._deformation
+    params = list(dn.parameters()) + [g._scene_flow]
+    for p in params:
+        st = g.optimizer.state.get(p, {})
+        assert len(st) == 0, "optimizer state for a parameter the coarse stage does not train"
+
+
+def _run(fused, per_op, steps, lambda_dssim, cfg=TINY, it0=2601):
+    scene, g, trainer = _coarse_state(cfg, fused=fused, per_op=per_op, lambda_dssim=lambda_dssim)
+    assert (trainer.fused is not None) == fused
+    losses = []
+    for i in range(steps):
+        cam = trainer.cams[(3 * i + 1) % len(trainer.cams)]
+        losses.append(float(trainer.step(it0 + i, cams=[cam])))
+    trainer.drain()
+    torch.cuda.synchronize()
+    _untouched(g)
+    moments = {}
+    if steps == 1:
+        for k, p in (("xyz", g._xyz), ("f_dc", g._features_dc), ("f_rest", g._features_rest), ("scaling", g._scaling),
+                     ("rotation", g._rotation), ("opacity", g._opacity)):
+            moments[k] = g.optimizer.state[p]["exp_avg"].detach().cpu().numpy().copy()
+    lr_max = max(grp["lr"] for grp in g.optimizer.param_groups)
+    return losses, _snap(g), moments, lr_max
+
+
+def _close_moments(ma, mf):
+    for k in ma:
+        scale = max(1e-30, float(np.abs(ma[k]).max()))
+        err = float(np.abs(mf[k] - ma[k]).max())
+        assert err <= 5e-5 * scale, ("gradient", k, err, scale)
+
+
+def _close_params(pa, pf, steps, lr_max):
+    for k in pa:
+        a, b = pf[k], pa[k]
+        scale = max(1e-12, float(np.abs(b).max()))
+        diff = np.abs(a - b)
+        tight = 2e-4 * scale + 1e-6
+        assert float((diff > tight).mean()) <= 1e-4, (k, float((diff > tight).mean()))
+        if k not in ("denom", "maxr", "accum"):
+            assert float(diff.max()) <= 2.0 * steps * lr_max * 1.01 + tight, (k, float(diff.max()))
+    np.testing.assert_array_equal(pf["denom"], pa["denom"])
+    np.testing.assert_array_equal(pf["maxr"], pa["maxr"])
+
+
+@pytest.mark.parametrize("lambda_dssim", [0.0, 0.2])
+def test_fused_coarse_step_matches_the_op_by_op_path(lambda_dssim):
+    la, _, ma, _ = _run(False, True, 1, lambda_dssim)
+    lf, _, mf, _ = _run(True, False, 1, lambda_dssim)
+    np.testing.assert_allclose(lf, la, rtol=2e-5)
+    _close_moments(ma, mf)
+    la, pa, _, lr = _run(False, True, 3, lambda_dssim)
+    lf, pf, _, _ = _run(True, False, 3, lambda_dssim)
+    np.testing.assert_allclose(lf, la, rtol=2e-5)
+    _close_params(pa, pf, 3, lr)
+
+
+@pytest.mark.parametrize("cfg", [TINY, C2], ids=["tiny", "c2"])
+def test_one_node_coarse_render_matches_the_op_by_op_path(cfg):
+    """render(stage="coarse") under grad is ONE autograd node; its six parameter gradients and the screen-space gradient equal the
+    op-by-op path's (torch activations + the rasterizer node) at the fused step's tolerance."""
+    R = importlib.import_module("iclr2025_3d-mom_amd.gaussian_renderer")
+    L = importlib.import_module("iclr2025_3d-mom_amd.utils.loss_utils")
+    out = {}
+    for per_op in (True, False):
+        scene, g, trainer = _coarse_state(cfg, per_op=per_op)
+        cam = trainer.cams[1]
+        g.optimizer.zero_grad(set_to_none=True)
+        pkg = R.render(cam, g, trainer.pipe, trainer.background, stage="coarse")
+        node = pkg["render"].grad_fn
+        if not per_op:
+            assert type(node).__name__ == "FusedCoarseRenderFunctionBackward", type(node).__name__
+        gt = cam.device_tensors(g._xyz.device)[3]
+        loss = L.l1_loss(pkg["render"].unsqueeze(0), gt.unsqueeze(0)[:, :3])
+        loss.backward()
+        torch.cuda.synchronize()
+        out[per_op] = {"image": pkg["render"].detach().cpu().numpy(), "radii": pkg["radii"].cpu().numpy(),
+                       "vsp": pkg["viewspace_points"].grad.cpu().numpy(),
+                       **{k: getattr(g, k).grad.cpu().numpy() for k in ("_xyz", "_features_dc", "_features_rest", "_scaling",
+                                                                         "_rotation", "_opacity")}}
+    a, f = out[True], out[False]
+    np.testing.assert_array_equal(f["radii"], a["radii"])
+    assert float(np.abs(f["image"] - a["image"]).mean()) <= 1e-6
+    for k in a:
+        if k in ("image", "radii"):
+            continue
+        scale = max(1e-30, float(np.abs(a[k]).max()))
+        assert float(np.abs(f[k] - a[k]).max()) <= 5e-5 * scale, (k, float(np.abs(f[k] - a[k]).max()), scale)
+
+
+def test_nograd_coarse_frame_matches_the_op_by_op_image():
+    R = importlib.import_module("iclr2025_3d-mom_amd.gaussian_renderer")
+    scene, g, trainer = _coarse_state(TINY, per_op=True)
+    for cam in trainer.cams[:3]:
+        with torch.no_grad():
+            fast = R.render(cam, g, trainer.pipe, trainer.background, stage="coarse")
+        assert "stream" not in fast
+        ref = R.render(cam, g, trainer.pipe, trainer.background, stage="coarse")       # grad on, per-op path
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(fast["radii"].cpu().numpy(), ref["radii"].cpu().numpy())
+        assert float((fast["render"] - ref["render"].detach()).abs().mean()) <= 1e-6
+
+
+# ------------------------------------------------------------------------------------------------ against the oracle
+def test_coarse_half_of_the_g10_curve_on_the_fused_coarse_step():
+    """tests/golden/g10_loss_curve.npz: its first 50 iterations are the coarse stage of config 1 on the CPU oracle path
+    (oracle/make_curve_fixture.run); the same iterations and camera order on Trainer(stage="coarse", fused=True)."""
+    from oracle.make_curve_fixture import CFG, N_COARSE
+    d = np.load(os.path.join(ROOT, "tests", "golden", "g10_loss_curve.npz"))
+    A, S, T, _ = _mods()
+    args, lp, op, pp, hp = A.default_args(time_resolution=CFG["time_res"])
+    op.lambda_dssim = 0.2
+    torch.manual_seed(6666)
+    scene = S.SyntheticScene(CFG["P"], CFG["F"], CFG["W"], CFG["H"], seed=6666)
+    g = S.GaussianModel(lp.sh_degree, hp, device=torch.device("cuda"))
+    scene.init_gaussians(g)
+    coarse = T.Trainer(scene, g, op, hp, pp, stage="coarse", delta_scale=1, sync_every_step=False, fused=True)
+    assert coarse.fused is not None
+    losses, points = [], []
+    for i in range(N_COARSE):
+        cam = coarse.cams[(3 * i + 1) % len(coarse.cams)]
+        losses.append(float(coarse.step(1 + i, cams=[cam])))
+        points.append(g.get_xyz.shape[0])
+    coarse.drain()
+    np.testing.assert_array_equal(points, d["points"][:N_COARSE])
+    ref = d["losses"][:N_COARSE]
+    rel = np.abs(np.array(losses) - ref) / np.abs(ref)
+    assert float(rel[:5].max()) <= 1e-4, rel[:5]
+    assert float(rel.max()) <= 2e-3, (int(rel.argmax()), float(rel.max()))
+    _untouched(g)
+
+
+# ------------------------------------------------------------------------------------------------ densify boundary, overflow replay
+def _window(fused, force=False):
+    scene, g, trainer = _coarse_state(TINY, fused=fused, per_op=not fused, densify_from_iter=50)
+    n0 = g._xyz.shape[0]
+    for i, it in enumerate(range(95, 106)):
+        if force and i == 2:           # iteration 97's buffer is sized from a count of 1: it overflows, 97-99 are replayed at 100
+            fs = trainer.fused
+            torch.cuda.synchronize()
+            fs.HEADROOM, fs.MARGIN = 0.25, 0
+            fs.cap, fs.binning = 1, None
+            fs.nr_host[0] = 1
+        if force and i == 5:
+            fs.HEADROOM, fs.MARGIN = type(fs).HEADROOM, type(fs).MARGIN
+        trainer.step(it, cams=[trainer.cams[(3 * i + 1) % len(trainer.cams)]])
+    trainer.drain()
+    torch.cuda.synchronize()
+    steps = sorted({float(st["step"]) for st in g.optimizer.state.values() if "step" in st})
+    _untouched(g)
+    lr_max = max(grp["lr"] for grp in g.optimizer.param_groups)
+    return _snap(g), g._xyz.shape[0], n0, steps, trainer.replayed, lr_max
+
+
+def test_densify_boundary_and_an_overflow_replay_on_the_fused_coarse_step():
+    pa, na, n0, sa, _, lr = _window(False)
+    pf, nf, _, sf, r0, _ = _window(True)
+    assert na == nf and na != n0, (na, nf, n0)         # iteration 100 densified, identically on both paths
+    assert r0 == 0 and sf == sa
+    _close_params(pa, pf, 11, lr)
+    px, nx, _, sx, r1, _ = _window(True, force=True)
+    assert r1 >= 3 and nx == nf and sx == sf, (r1, nx, nf, sx, sf)
+    np.testing.assert_array_equal(px["denom"], pf["denom"])
+    np.testing.assert_array_equal(px["maxr"], pf["maxr"])
+    for k in ("xyz", "f_dc", "scaling", "rotation", "opacity", "accum"):
+        a, b = px[k], pf[k]
+        scale = max(1e-12, float(np.abs(b).max()))
+        assert float((np.abs(a - b) > 1e-3 * scale + 1e-6).mean()) <= 2e-3, k
