@@ -14,7 +14,6 @@ backward -- the reference's batch loop -- and images may be kept.  Binning capac
 "async" sizes from earlier frames and reports an overflow through the module's sticky flag.
 """
 import ctypes as C
-import math
 
 import torch
 
@@ -71,21 +70,6 @@ class _State:
                  "mlp", "field", "f_dc", "f_rest", "ready", "side")
 
 
-def applies(cam, pc, pipe, stage, override_color, cam_type):
-    """Same conditions as the no-grad fast path: fine stage, the shipped deformation configuration, SH colours and covariances
-    computed by the rasterizer, an ordinary camera, everything on the GPU -- and gradients wanted."""
-    if not torch.is_grad_enabled() or stage != "fine" or override_color is not None or cam_type == "PanopticSports":
-        return False
-    if pipe.compute_cov3D_python or pipe.convert_SHs_python or not hasattr(cam, "device_tensors"):
-        return False
-    if not pc.get_xyz.is_cuda or pc.get_xyz.shape[0] == 0 or ops.BACKEND.name != "hip":
-        return False
-    if getattr(pipe, "per_op_autograd", False):
-        return False
-    dn = getattr(pc._deformation, "deformation_net", None)
-    return dn is not None and hasattr(dn, "_fusable") and dn._fusable() and pc._features_rest.shape[1] == 15
-
-
 def field_params(pc):
     """(planes, MLP tensors) of the deformation field, cached on the model until a parameter object is replaced (walking the
     nn.Module tree costs 70 us per call)."""
@@ -108,59 +92,50 @@ def _forward_desc(pc, field, planes, mlp):
     return c[1], c[2], c[3]
 
 
-def _forward(pc, cam, bg, delta_scale, scaling_modifier, debug):
+def _forward(pc, cam, bg, delta_scale, scaling_modifier, debug, coarse):
+    """coarse: no deformation field -- the projection reads the raw parameters and applies the activations itself."""
     lib, s = N.lib(), N.current_stream()
     st = _State()
     dev = pc._xyz.device
     P = st.P = pc._xyz.shape[0]
     W, H = st.W, st.H = int(cam.image_width), int(cam.image_height)
     view, proj, campos, _ = cam.device_tensors(dev)
-    dn = pc._deformation.deformation_net
-    field = st.field = dn.grid
-    st.planes, st.mlp = field_params(pc)
-    xyz, scal, rotq, opac = pc._xyz.detach(), pc._scaling.detach(), pc._rotation.detach(), pc._opacity.detach()
-    st.f_dc, st.f_rest = pc._features_dc.detach(), pc._features_rest.detach()
-    for t in (xyz, scal, rotq, opac, st.f_dc, st.f_rest):
-        if not t.is_contiguous():
-            raise N.MomError("fused render(): the Gaussian parameters must be contiguous")
-    flow = pc._scene_flow if pc._scene_flow.is_contiguous() else pc._scene_flow.contiguous()
-    st.xyz, st.scal, st.rotq, st.opac, st.flow = xyz, scal, rotq, opac, flow
-    st.cam_time = float(cam.time)
-    st.coef = float(delta_scale * cam.frame_num)
-    st.order = field._processing_order(xyz)
-    st.porders = field._plane_orders(xyz)
-    f = dict(dtype=torch.float32, device=dev)
-    e = lambda *sh: torch.empty(*sh, **f)
-    st.pool_key = (P, W, H, dev, s)
+    st.xyz, st.f_dc, st.f_rest, st.scal, st.rotq, st.opac = ops.gaussian_params(pc, "fused render()")
+    st.planes, st.mlp, st.field, st.ready, st.side = (), (), None, None, None
+    e = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
+    st.pool_key = (P, W, H, dev, s, coarse)
     b = st.bufs = _pool_take(st.pool_key)
     if b is None:
-        b = st.bufs = {"feat": e(P, 64), "a0": e(P, 64), "pts": e(P, 3), "sc_d": e(P, 3), "rot_d": e(P, 4), "sc": e(P, 3),
-                       "rot": e(P, 4), "op": e(P, 1),
-                       "geom": torch.empty(lib.mom_raster_geom_bytes(P), dtype=torch.uint8, device=dev),
+        b = st.bufs = {"geom": torch.empty(lib.mom_raster_geom_bytes(P), dtype=torch.uint8, device=dev),
                        "img": torch.empty(lib.mom_raster_image_bytes(W, H), dtype=torch.uint8, device=dev),
                        "nr_dev": torch.empty(1, dtype=torch.int32, device=dev)}
-    st.feat, st.a0 = b["feat"], b["a0"]
-    st.pts, st.sc_d, st.rot_d = b["pts"], b["sc_d"], b["rot_d"]
-    st.sc, st.rot, st.op = b["sc"], b["rot"], b["op"]
+        if not coarse:
+            b.update(feat=e(P, 64), a0=e(P, 64), pts=e(P, 3), sc_d=e(P, 3), rot_d=e(P, 4), sc=e(P, 3), rot=e(P, 4), op=e(P, 1))
     st.color, st.depth = e(3, H, W), e(1, H, W)
     st.radii = torch.empty(P, dtype=torch.int32, device=dev)
     st.geom, st.img = b["geom"], b["img"]
-    hp, keep, md = _forward_desc(pc, field, st.planes, st.mlp)
-    ops.field_forward(hp, md, P, xyz, st.cam_time, st.order, scal, rotq, flow, st.coef, st.pts, st.sc_d, st.rot_d, st.feat, st.a0,
-                      opac, st.sc, st.rot, st.op, s)
-    a = st.a = N.MomRasterArgs()
-    a.P, a.D, a.M, a.W, a.H = P, pc.active_sh_degree, 16, W, H
-    a.background, a.means3D = bg.data_ptr(), st.pts.data_ptr()
-    a.shs, a.shs_rest = st.f_dc.data_ptr(), st.f_rest.data_ptr()
-    a.colors_precomp, a.opacities = None, st.op.data_ptr()
-    a.scales, a.rotations, a.cov3D_precomp = st.sc.data_ptr(), st.rot.data_ptr(), None
-    a.viewmatrix, a.projmatrix, a.campos = view.data_ptr(), proj.data_ptr(), campos.data_ptr()
-    a.scale_modifier = float(scaling_modifier)
-    a.tan_fovx, a.tan_fovy = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
-    a.prefiltered, a.debug = 0, int(bool(debug))
-    a.keep_all_tiles = int(RC._state["keep_all_tiles"])       # set_keep_all_tiles(): the reference's lists and num_rendered
-    st.keep = (bg, view, proj, campos, keep)
-    _raster_forward(lib, a, st, b["nr_dev"], P, W, H, dev, s)
+    st.keep = (bg, view, proj, campos)      # (with st's own tensors: what the pointers in st.a point at)
+    if coarse:
+        means, sc, rot, op = st.xyz, st.scal, st.rotq, st.opac
+    else:
+        field = st.field = pc._deformation.deformation_net.grid
+        st.planes, st.mlp = field_params(pc)
+        flow = st.flow = pc._scene_flow if pc._scene_flow.is_contiguous() else pc._scene_flow.contiguous()
+        st.cam_time = float(cam.time)
+        st.coef = float(delta_scale * cam.frame_num)
+        st.order = field._processing_order(st.xyz)
+        st.porders = field._plane_orders(st.xyz)
+        st.feat, st.a0 = b["feat"], b["a0"]
+        st.pts, st.sc_d, st.rot_d = b["pts"], b["sc_d"], b["rot_d"]
+        st.sc, st.rot, st.op = b["sc"], b["rot"], b["op"]
+        means, sc, rot, op = st.pts, st.sc, st.rot, st.op
+        hp, keep, md = _forward_desc(pc, field, st.planes, st.mlp)
+        st.keep += (keep,)
+        ops.field_forward(hp, md, P, st.xyz, st.cam_time, st.order, st.scal, st.rotq, flow, st.coef, st.pts, st.sc_d, st.rot_d,
+                          st.feat, st.a0, st.opac, st.sc, st.rot, st.op, s)
+    st.a = ops.raster_args(cam, view, proj, campos, bg, P, pc.active_sh_degree, means, st.f_dc, st.f_rest, op, sc, rot, coarse,
+                           scaling_modifier, debug, RC._state["keep_all_tiles"])   # set_keep_all_tiles(): the reference's lists
+    _raster_forward(lib, st.a, st, b["nr_dev"], P, W, H, dev, s)
     return st
 
 
@@ -253,6 +228,7 @@ def _field_grads(st, f, direct=True):
 
 
 def _backward(st, dcolor, ddepth, direct=True):
+    """(screen-space gradient, the parameter gradients in the order of st's parameters: the six Gaussian ones, planes, MLP)."""
     lib, s = N.lib(), N.current_stream()
     P, dev = st.P, st.color.device
     f = dict(dtype=torch.float32, device=dev)
@@ -260,22 +236,22 @@ def _backward(st, dcolor, ddepth, direct=True):
     dcol = dcolor.contiguous().float()
     ddep = None if ddepth is None else ddepth.contiguous().float()
     b = st.bufs
-    if "gcol" not in b:               # the backward's internal gradients and scratch: made once per pooled set
-        b.update(gcol=e(P, 3), gcov=e(P, 6), dfeat=e(P, 64),
-                 scratch=torch.empty(lib.mom_deform_backward_scratch_bytes(P), dtype=torch.uint8, device=dev))
-    g2d, gcol, gxyz, gcov = e(P, 3), b["gcol"], e(P, 3), b["gcov"]
-    gdc, grest = e(P, 1, 3), e(P, 15, 3)
-    gsc, grot, gop = e(P, 3), e(P, 4), e(P, 1)
-    gr = N.MomRasterGrads()
-    # (scale / rotation / opacity gradients: through their activations inside the projection backward -- act_rotations_raw)
-    gr.dL_dmeans2D, gr.dL_dcolors, gr.dL_dopacity = g2d.data_ptr(), gcol.data_ptr(), gop.data_ptr()
-    gr.dL_dmeans3D, gr.dL_dcov3D = gxyz.data_ptr(), gcov.data_ptr()
-    gr.dL_dsh, gr.dL_dsh_rest = gdc.data_ptr(), grest.data_ptr()
-    gr.dL_dscales, gr.dL_drotations = gsc.data_ptr(), grot.data_ptr()
-    gr.act_rotations_raw = st.rot_d.data_ptr()
+    if "gcol" not in b:               # the backward's internal gradients: made once per pooled set
+        b.update(gcol=e(P, 3), gcov=e(P, 6))
+    g2d, gxyz, gdc, grest, gsc, grot, gop = e(P, 3), e(P, 3), e(P, 1, 3), e(P, 15, 3), e(P, 3), e(P, 4), e(P, 1)
+    gr = ops.raster_grads(g2d, b["gcol"], gop, gxyz, b["gcov"], gdc, grest, gsc, grot)
+    if st.field is not None:
+        # (scale / rotation / opacity gradients: through their activations inside the projection backward -- act_rotations_raw)
+        gr.act_rotations_raw = st.rot_d.data_ptr()
     N.check(lib.mom_raster_backward(C.byref(st.a), st.radii.data_ptr(), st.geom.data_ptr(), st.binning.data_ptr(), st.cap,
                                     st.img.data_ptr(), dcol.data_ptr(), None if ddep is None else ddep.data_ptr(), C.byref(gr), s),
             "raster_bwd")
+    if st.field is None:              # coarse stage: the raw parameters' gradients are complete
+        _pool_give(st.pool_key, b)
+        st.bufs = None
+        return g2d, (gxyz, gdc, grest, gsc, grot, gop)
+    if "dfeat" not in b:              # the deformation backward's intermediate gradient and scratch
+        b.update(dfeat=e(P, 64), scratch=torch.empty(lib.mom_deform_backward_scratch_bytes(P), dtype=torch.uint8, device=dev))
     overlap = ops.API_OVERLAP and direct
     ready = side = None
     if overlap:
@@ -315,7 +291,50 @@ def _backward(st, dcolor, ddepth, direct=True):
     if not overlap:
         _pool_give(st.pool_key, b)
     st.bufs = None
-    return g2d, gxyz, gdc, grest, gsc, grot, gop, gplanes, gmlp, in_place
+    return g2d, (gxyz, gdc, grest, gsc, grot, gop, *gplanes, *gmlp)
+
+
+def _take(ctx):
+    st = ctx.st
+    if st is None:
+        raise RuntimeError("render(): a second backward through the same call -- its buffers were released after the first "
+                           "(render again, or set pipe.per_op_autograd = True for retain_graph use)")
+    ctx.st = None                                  # the call's buffers go back to the allocator after this backward
+    return st
+
+
+def _node_backward(ctx, st, lead, dcolor, ddepth):
+    """Function.backward of one render() node with `lead` plain inputs in front of the 2-D gradient holder."""
+    pc = ctx.pc
+    params = (pc._xyz, pc._features_dc, pc._features_rest, pc._scaling, pc._rotation, pc._opacity, *st.planes, *st.mlp)
+    needs = ctx.needs_input_grad[lead + 1:]
+    direct = DIRECT_GRADS and ops.direct_grads_ok(params, needs)
+    g2d, grads = _backward(st, dcolor, ddepth, direct)
+    if not direct:
+        # through the graph (fresh buffers: nothing is accumulated in place on this path); inputs that were not asked for get None
+        return (None,) * lead + (g2d, *[g if n else None for g, n in zip(grads, needs)])
+    # The parameter gradients are handed to the parameters here (set, or added to what an earlier camera of the batch left)
+    # instead of being returned: 32 AccumulateGrad nodes cost the autograd engine more host time than the whole fine forward.
+    # Only the 2-D gradient holder, a non-leaf, goes back through the graph.
+    fresh = True
+    for p, g in zip(params, grads):
+        if p.grad is None:
+            p.grad = g
+        elif p.grad is not g:                   # (a plane accumulated into in place IS its own gradient)
+            p.grad.add_(g)
+            fresh = False
+    # one camera per optimizer step (the reference's batch_size 1): tell the optimizer when the appearance gradients were final,
+    # so that its step() can start their update underneath the rest of this backward (ops.FusedAdam.step checks that nothing
+    # touched them in between).  A second camera accumulating into them, or a backward without that overlap (the coarse stage
+    # has no deformation backward to hide it under), withdraws the hint.
+    opt = getattr(pc, "optimizer", None)
+    if opt is not None and hasattr(opt, "early_hint"):
+        app = params[1:6]
+        if st.ready is not None and fresh and all(p.grad is g for p, g in zip(app, grads[1:6])):
+            opt.early_hint = (st.ready, st.side, [(p, p.grad, p.grad._version) for p in app])
+        else:
+            opt.early_hint = None
+    return (None,) * lead + (g2d,) + (None,) * len(params)
 
 
 class FusedRenderFunction(torch.autograd.Function):
@@ -325,7 +344,7 @@ class FusedRenderFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pc, cam, bg, delta_scale, scaling_modifier, debug, screenspace, xyz, f_dc, f_rest, scaling, rotation, opacity,
                 *field):
-        st = _forward(pc, cam, bg, delta_scale, scaling_modifier, debug)
+        st = _forward(pc, cam, bg, delta_scale, scaling_modifier, debug, False)
         ctx.st, ctx.pc = st, pc
         dev = st.color.device
         ops._render_pending[dev] = ops._render_pending.get(dev, 0) + 1       # (ops.PlaneRegFunction.backward: who joins its kernel)
@@ -334,168 +353,31 @@ class FusedRenderFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dcolor, ddepth, _dradii):
-        st = ctx.st
-        if st is None:
-            raise RuntimeError("render(): a second backward through the same call -- its buffers were released after the first "
-                               "(render again, or set pipe.per_op_autograd = True for retain_graph use)")
-        ctx.st = None                                  # the call's buffers go back to the allocator after this backward
+        st = _take(ctx)
         dev = st.color.device
         ops._render_pending[dev] = max(0, ops._render_pending.get(dev, 0) - 1)
-        pc = ctx.pc
-        params = (pc._xyz, pc._features_dc, pc._features_rest, pc._scaling, pc._rotation, pc._opacity, *st.planes, *st.mlp)
-        needs = ctx.needs_input_grad[7:]
-        direct = DIRECT_GRADS and ops.direct_grads_ok(params, needs)
-        g2d, gxyz, gdc, grest, gsc, grot, gop, gplanes, gmlp, in_place = _backward(st, dcolor, ddepth, direct)
-        if direct:
-            # The 32 parameter gradients are handed to the parameters here (set, or added to what an earlier camera of the
-            # batch left) instead of being returned: 32 AccumulateGrad nodes cost the autograd engine more host time than the
-            # whole forward.  Only the 2-D gradient holder, a non-leaf, goes back through the graph.
-            fresh = True
-            for p, g in zip(params, (gxyz, gdc, grest, gsc, grot, gop, *gplanes, *gmlp)):
-                if p.grad is None:
-                    p.grad = g
-                elif p.grad is not g:                   # (a plane accumulated into in place IS its own gradient)
-                    p.grad.add_(g)
-                    fresh = False
-            # one camera per optimizer step (the reference's batch_size 1): tell the optimizer when the appearance gradients were
-            # final, so that its step() can start their update underneath the rest of this backward (ops.FusedAdam.step checks that
-            # nothing touched them in between).  A second camera accumulating into them withdraws the hint.
-            opt = getattr(pc, "optimizer", None)
-            if opt is not None and hasattr(opt, "early_hint"):
-                app = (pc._features_dc, pc._features_rest, pc._scaling, pc._rotation, pc._opacity)
-                if st.ready is not None and fresh and all(p.grad is g for p, g in zip(app, (gdc, grest, gsc, grot, gop))):
-                    opt.early_hint = (st.ready, st.side, [(p, p.grad, p.grad._version) for p in app])
-                else:
-                    opt.early_hint = None
-            return (None, None, None, None, None, None, g2d) + (None,) * (6 + len(gplanes) + len(gmlp))
-        # through the graph (fresh buffers: nothing is accumulated in place on this path); inputs that were not asked for get None
-        out = [g if n else None for g, n in zip((gxyz, gdc, grest, gsc, grot, gop, *gplanes, *gmlp), needs)]
-        return (None, None, None, None, None, None, g2d, *out)
+        return _node_backward(ctx, st, 6, dcolor, ddepth)
 
 
-# ---------------------------------------------------------------------------------------------------------- coarse stage
 # The coarse stage (train_4DGS.py with stage "coarse": the first 3 000 iterations of every run) renders the Gaussians without the
 # deformation field, so its render() is the rasterizer alone on exp / normalize / sigmoid of the parameters
 # (gaussian_renderer/__init__.py:113,130-132).  As one node: the projection reads the RAW parameters and applies the activations in
 # registers (MomRasterArgs.params_raw), the backward writes the six parameter gradients through them -- no activated copies, no
 # activation nodes, no separate rasterizer node.
-
-def applies_coarse(cam, pc, pipe, stage, override_color, cam_type):
-    """The conditions of applies() without the deformation ones, for stage "coarse"."""
-    if not torch.is_grad_enabled() or stage != "coarse" or override_color is not None or cam_type == "PanopticSports":
-        return False
-    if pipe.compute_cov3D_python or pipe.convert_SHs_python or not hasattr(cam, "device_tensors"):
-        return False
-    if not pc.get_xyz.is_cuda or pc.get_xyz.shape[0] == 0 or ops.BACKEND.name != "hip":
-        return False
-    if getattr(pipe, "per_op_autograd", False):
-        return False
-    return pc._features_rest.shape[1] == 15
-
-
-class _CoarseState:
-    __slots__ = ("pool_key", "bufs", "a", "keep", "P", "color", "depth", "radii", "geom", "img", "binning", "cap")
-
-
-def _forward_coarse(pc, cam, bg, scaling_modifier, debug):
-    lib, s = N.lib(), N.current_stream()
-    st = _CoarseState()
-    dev = pc._xyz.device
-    P = st.P = pc._xyz.shape[0]
-    W, H = int(cam.image_width), int(cam.image_height)
-    view, proj, campos, _ = cam.device_tensors(dev)
-    xyz, scal, rotq, opac = pc._xyz.detach(), pc._scaling.detach(), pc._rotation.detach(), pc._opacity.detach()
-    f_dc, f_rest = pc._features_dc.detach(), pc._features_rest.detach()
-    for t in (xyz, scal, rotq, opac, f_dc, f_rest):
-        if not t.is_contiguous():
-            raise N.MomError("fused render(): the Gaussian parameters must be contiguous")
-    st.pool_key = (P, W, H, dev, s, "coarse")
-    b = st.bufs = _pool_take(st.pool_key)
-    if b is None:
-        b = st.bufs = {"geom": torch.empty(lib.mom_raster_geom_bytes(P), dtype=torch.uint8, device=dev),
-                       "img": torch.empty(lib.mom_raster_image_bytes(W, H), dtype=torch.uint8, device=dev),
-                       "nr_dev": torch.empty(1, dtype=torch.int32, device=dev)}
-    st.color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
-    st.depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
-    st.radii = torch.empty(P, dtype=torch.int32, device=dev)
-    st.geom, st.img = b["geom"], b["img"]
-    a = st.a = N.MomRasterArgs()
-    a.P, a.D, a.M, a.W, a.H = P, pc.active_sh_degree, 16, W, H
-    a.background, a.means3D = bg.data_ptr(), xyz.data_ptr()
-    a.shs, a.shs_rest = f_dc.data_ptr(), f_rest.data_ptr()
-    a.colors_precomp, a.cov3D_precomp = None, None
-    a.params_raw = 1                        # exp / normalize / sigmoid in the projection kernel
-    a.opacities, a.scales, a.rotations = opac.data_ptr(), scal.data_ptr(), rotq.data_ptr()
-    a.viewmatrix, a.projmatrix, a.campos = view.data_ptr(), proj.data_ptr(), campos.data_ptr()
-    a.scale_modifier = float(scaling_modifier)
-    a.tan_fovx, a.tan_fovy = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
-    a.prefiltered, a.debug = 0, int(bool(debug))
-    a.keep_all_tiles = int(RC._state["keep_all_tiles"])
-    st.keep = (bg, view, proj, campos, xyz, scal, rotq, opac, f_dc, f_rest)      # what the pointers in `a` point at
-    _raster_forward(lib, a, st, b["nr_dev"], P, W, H, dev, s)
-    return st
-
-
-def _backward_coarse(st, dcolor, ddepth):
-    lib, s = N.lib(), N.current_stream()
-    P, dev = st.P, st.color.device
-    f = dict(dtype=torch.float32, device=dev)
-    e = lambda *sh: torch.empty(*sh, **f)
-    dcol = dcolor.contiguous().float()
-    ddep = None if ddepth is None else ddepth.contiguous().float()
-    b = st.bufs
-    if "gcol" not in b:
-        b.update(gcol=e(P, 3), gcov=e(P, 6))
-    g2d, gxyz, gdc, grest = e(P, 3), e(P, 3), e(P, 1, 3), e(P, 15, 3)
-    gsc, grot, gop = e(P, 3), e(P, 4), e(P, 1)
-    gr = N.MomRasterGrads()
-    gr.dL_dmeans2D, gr.dL_dcolors, gr.dL_dopacity = g2d.data_ptr(), b["gcol"].data_ptr(), gop.data_ptr()
-    gr.dL_dmeans3D, gr.dL_dcov3D = gxyz.data_ptr(), b["gcov"].data_ptr()
-    gr.dL_dsh, gr.dL_dsh_rest = gdc.data_ptr(), grest.data_ptr()
-    gr.dL_dscales, gr.dL_drotations = gsc.data_ptr(), grot.data_ptr()
-    N.check(lib.mom_raster_backward(C.byref(st.a), st.radii.data_ptr(), st.geom.data_ptr(), st.binning.data_ptr(), st.cap,
-                                    st.img.data_ptr(), dcol.data_ptr(), None if ddep is None else ddep.data_ptr(), C.byref(gr), s),
-            "raster_bwd")
-    _pool_give(st.pool_key, b)
-    st.bufs = None
-    return g2d, gxyz, gdc, grest, gsc, grot, gop
-
-
 class FusedCoarseRenderFunction(torch.autograd.Function):
     """(image, depth, radii) = coarse-stage render of one camera; inputs after the five plain arguments: the 2-D gradient holder
     and the six Gaussian parameter tensors."""
 
     @staticmethod
     def forward(ctx, pc, cam, bg, scaling_modifier, debug, screenspace, xyz, f_dc, f_rest, scaling, rotation, opacity):
-        st = _forward_coarse(pc, cam, bg, scaling_modifier, debug)
+        st = _forward(pc, cam, bg, None, scaling_modifier, debug, True)
         ctx.st, ctx.pc = st, pc
         ctx.mark_non_differentiable(st.radii)
         return st.color, st.depth, st.radii
 
     @staticmethod
     def backward(ctx, dcolor, ddepth, _dradii):
-        st = ctx.st
-        if st is None:
-            raise RuntimeError("render(): a second backward through the same call -- its buffers were released after the first "
-                               "(render again, or set pipe.per_op_autograd = True for retain_graph use)")
-        ctx.st = None
-        pc = ctx.pc
-        params = (pc._xyz, pc._features_dc, pc._features_rest, pc._scaling, pc._rotation, pc._opacity)
-        needs = ctx.needs_input_grad[6:]
-        direct = DIRECT_GRADS and ops.direct_grads_ok(params, needs)
-        g2d, *grads = _backward_coarse(st, dcolor, ddepth)
-        if direct:
-            # (as FusedRenderFunction: the parameter gradients are handed to the parameters, only the 2-D holder goes through the graph)
-            for p, g in zip(params, grads):
-                if p.grad is None:
-                    p.grad = g
-                else:
-                    p.grad.add_(g)
-            opt = getattr(pc, "optimizer", None)
-            if opt is not None and hasattr(opt, "early_hint"):
-                opt.early_hint = None
-            return (None, None, None, None, None, g2d) + (None,) * 6
-        return (None, None, None, None, None, g2d, *[g if n else None for g, n in zip(grads, needs)])
+        return _node_backward(ctx, _take(ctx), 5, dcolor, ddepth)
 
 
 def render_coarse(cam, pc, pipe, bg, scaling_modifier, screenspace_points):

@@ -7,7 +7,6 @@ gradient holder, no per-op allocation of intermediates.  Only the returned image
 callers keep them.
 """
 import ctypes as C
-import math
 from collections import deque
 
 import torch
@@ -45,7 +44,6 @@ class FusedRender:
         # per-frame status word of the image scratch (header word 1: bit 0 = this frame's binning overflowed): the compositing kernel
         # posts it, with the frame's serial number, into a slot of this pinned ring (MomRasterArgs.status_post) -- no copy command and
         # no event behind an async-mode frame (a blit kernel and a marker were 12 us of the stream per frame)
-        self.hdr = self.img[(-self.img.data_ptr()) % 256:][:8].view(torch.int32)
         self.flag_ring = torch.zeros(self.RING, dtype=torch.int64).pin_memory()
         self._ring_np = self.flag_ring.numpy()      # (a view of the same pinned words: reading one costs 0.1 us, indexing the tensor 2)
         self.pending = deque()               # (frame serial, ring slot), oldest first
@@ -93,28 +91,21 @@ class FusedRender:
         W, H = int(cam.image_width), int(cam.image_height)
         self._ensure(P, W, H, dev)
         view, proj, campos, _ = cam.device_tensors(dev)
-        if stage == "coarse":
-            pts, sc, rot, op = (t.detach() for t in (g._xyz, g._scaling, g._rotation, g._opacity))
-            for t in (pts, sc, rot, op, g._features_dc, g._features_rest):
-                if not t.is_contiguous():
-                    raise N.MomError("fused render(): the Gaussian parameters must be contiguous")
+        xyz, f_dc, f_rest, scal, rotq, opac = ops.gaussian_params(g, "fused render()")
+        coarse = stage == "coarse"
+        if coarse:
+            means, sc, rot, op = xyz, scal, rotq, opac
         else:
-            self._deform(g, cam, delta_scale, order, P, dev, s)
-            pts, sc, rot, op = self.pts, self.sc, self.rot, self.op
-        a = N.MomRasterArgs()
-        a.P, a.D, a.M, a.W, a.H = P, g.active_sh_degree, 16, W, H
-        a.background, a.means3D = bg.data_ptr(), pts.data_ptr()
-        a.shs, a.shs_rest = g._features_dc.data_ptr(), g._features_rest.data_ptr()
-        a.colors_precomp, a.opacities = None, op.data_ptr()
-        a.scales, a.rotations, a.cov3D_precomp = sc.data_ptr(), rot.data_ptr(), None
-        a.params_raw = int(stage == "coarse")
-        return self._raster(a, cam, view, proj, campos, scaling_modifier, debug, P, W, H, dev, s)
+            self._deform(g, cam, delta_scale, order, P, dev, s, xyz, scal, rotq, opac)
+            means, sc, rot, op = self.pts, self.sc, self.rot, self.op
+        a = ops.raster_args(cam, view, proj, campos, bg, P, g.active_sh_degree, means, f_dc, f_rest, op, sc, rot, coarse,
+                            scaling_modifier, debug, RC._state["keep_all_tiles"])
+        return self._raster(a, P, W, H, dev, s)
 
-    def _deform(self, g, cam, delta_scale, order, P, dev, s):
+    def _deform(self, g, cam, delta_scale, order, P, dev, s, xyz, scal, rot, opac):
         lib = self.lib
         dn = g._deformation.deformation_net
         field = dn.grid
-        xyz, scal, rot, opac = g._xyz.detach(), g._scaling.detach(), g._rotation.detach(), g._opacity.detach()
         flow = g._scene_flow if g._scene_flow.is_contiguous() else g._scene_flow.contiguous()
         if order is False:
             order = field._processing_order(xyz)
@@ -137,13 +128,8 @@ class FusedRender:
                           self.sc_d, self.rot_d, None, None, opac, self.sc, self.rot, self.op, s, scratch_feat=self.feat,
                           scratch=self._fscratch)
 
-    def _raster(self, a, cam, view, proj, campos, scaling_modifier, debug, P, W, H, dev, s):
+    def _raster(self, a, P, W, H, dev, s):
         lib = self.lib
-        a.viewmatrix, a.projmatrix, a.campos = view.data_ptr(), proj.data_ptr(), campos.data_ptr()
-        a.scale_modifier = float(scaling_modifier)
-        a.tan_fovx, a.tan_fovy = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
-        a.prefiltered, a.debug = 0, int(bool(debug))
-        a.keep_all_tiles = int(RC._state["keep_all_tiles"])
         a.forward_only = 1               # no backward follows: cov3D / clamped / final_T / n_contrib are not written
         color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)

@@ -1,7 +1,7 @@
-"""One fine-stage training iteration as an explicit sequence of ~25 libmom4d launches -- no autograd graph, no
-per-op tensor allocation, no host synchronisation.
+"""The training iteration as an explicit sequence of libmom4d launches -- no autograd graph, no per-op tensor allocation, no host
+synchronisation.  FusedStep is the fine stage's, FusedCoarseStep the coarse stage's; _Step holds what they share.
 
-It computes exactly what `train.Trainer.step` computes through `render()` + `loss.backward()` (the reference's
+FusedStep computes exactly what `train.Trainer.step` computes through `render()` + `loss.backward()` (the reference's
 train_4DGS.py:149-297 with batch_size 1, stage "fine", L1 (+ lambda_dssim SSIM) loss, the shipped deformation config) and leaves the
 same `.grad` tensors behind, so the optimizer step, the densification statistics and everything downstream are shared
 with the autograd path.  `tests/test_fused_step_gpu.py` checks the two paths against each other.
@@ -10,56 +10,49 @@ Order of launches: hexplane_fwd -> deform_fwd -> activations_fwd -> preprocess /
 render_bwd / preprocess_bwd -> activations_bwd -> deform_bwd (dx, dw) -> hexplane_bwd -> plane_reg -> adam.
 """
 import ctypes as C
-import math
 import os
 
 import torch
 
 from . import _native as N
 from . import ops
-from .diff_gaussian_rasterization import _C as RC
-
-# The L1 epilogue of the compositing forward leaves one pair of sums per tile (MomRasterArgs.l1_partials) instead of adding 2040
-# workgroups' pairs into one line; MOM_L1_PARTIALS=0 is the A/B switch (render_fwd 135 -> 127 us with HIP events around it).
-L1_PARTIALS = os.environ.get("MOM_L1_PARTIALS", "1") != "0"
 
 
-class FusedStep:
+class _Step:
+    """What both steps share: the per-frame buffers, the sticky overflow word and what train.Trainer's overflow / replay protocol
+    reads of it (flags, flag_ring, post_flag, next_tag, exact_next), the binning capacity, the full-image SSIM term and the loss
+    value.  A subclass makes its per-Gaussian buffers in _per_gaussian and runs its iteration in forward_backward."""
+
+    RING = 64
+    keep_all_tiles = False            # True: bin whole rectangles like the reference (MomRasterArgs.keep_all_tiles; measurement only)
+    HEADROOM, MARGIN = 1.5, 65536     # binning capacity = HEADROOM x an earlier frame's instance count + MARGIN
+
     def __init__(self, gaussians, opt, hyper, background):
         self.g, self.opt, self.hyper, self.bg = gaussians, opt, hyper, background
-        dn = gaussians._deformation.deformation_net
-        if not dn._fusable():
-            raise N.MomError("FusedStep needs the shipped deformation configuration (W=64, D=0, no_do, no_dshs)")
         self.P = -1
         self.lib = N.lib()
         self.last = {}
-        self.dist = None      # parallel.DistContext (camera-batch shard): set by parallel.attach()
+        self.dist = None      # parallel.DistContext (fine step: camera-batch or tile-row shard): set by parallel.attach()
+        self.next_tag = 1     # what a step leaves in the overflow word if its binning overflows (Trainer numbers the steps)
+        self.cap = 0
+        self._resize_next = False
+        self._key = self._frame = None
 
-    # ------------------------------------------------------------------ buffers (re-made when P changes)
     def _rows(self, P):
-        """Rows of the per-Gaussian buffers a tile-row shard gathers: world x S (DistContext.slice_rows), else P."""
-        dc = self.dist
-        return dc.world * dc.slice_rows(P) if (dc is not None and dc.mode == "tile-row") else P
+        return P
 
     def _ensure(self, P, W, H, dev):
-        """The step's buffers.  Per-Gaussian storage is CAPACITY based: a densify / prune round changes P by a few percent every
-        hundred iterations (train_4DGS.py:264-290), and re-making fifty buffers each time sent the step after every round back to
-        the driver for fresh memory (tools/probe/c5_leg.py: the first round of a process cost 148 ms instead of 13 and the steps
-        behind it ran at 59 instead of 94 per second until the new pages had been touched).  Storage is re-made only when the
-        model outgrows it (then with a quarter of headroom) or shrinks below half of it; otherwise the attributes below are
-        re-sliced views of the same memory."""
+        """The step's buffers: the per-frame ones when the frame changes, the per-Gaussian ones (_per_gaussian) when P does."""
         pad = self._rows(P)
         key = (P, W, H, pad, dev)
-        if key == getattr(self, "_key", None):
+        if key == self._key:
             return
         self._key = key
-        self.P, self._wh, self._pad = P, (W, H), pad
-        f = dict(dtype=torch.float32, device=dev)
-        e = lambda *s: torch.empty(*s, **f)
-        cap = getattr(self, "_rows_cap", 0)
-        same_frame = getattr(self, "_store_for", None) == (W, H, dev)
-        if not same_frame:
-            self._store_for = (W, H, dev)
+        self.P, self._wh = P, (W, H)
+        new_frame = self._frame != (W, H, dev)
+        if new_frame:
+            self._frame = (W, H, dev)
+            e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
             self.color, self.depth, self.dimg = e(3, H, W), e(1, H, W), e(3, H, W)
             self.img = torch.empty(self.lib.mom_raster_image_bytes(W, H), dtype=torch.uint8, device=dev)
             self.nr_dev = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -70,20 +63,137 @@ class FusedStep:
             # later one are no-ops ON THE DEVICE (mom_adam_step / mom_densify_stats skip_if_nonzero) until the host -- which
             # runs several steps ahead and reads the word through flag_ring a few steps later -- clears it and replays the
             # skipped iterations with an exactly sized buffer (train.Trainer._recover).  Nothing truncated ever reaches the model.
-            # (the word itself lives behind the radii, below: one integer bucket for a camera-batch shard's max-all-reduce)
+            # (the word itself lives behind the radii: _set_bucket)
             self.flag_ring = torch.zeros(self.RING, dtype=torch.int32).pin_memory()
-            self.next_tag = 1
-            # loss accumulators live in spare words of the image scratch's header, which the rasterizer forward clears at the
-            # start of every step together with its tile counters: no memset of their own (mom_l1_loss_acc / mom_plane_regulation_acc)
-            hdr_f = self.img[(-self.img.data_ptr()) % 256:][:256].view(torch.float32)
-            self.sums, self.regval = hdr_f[8:10], hdr_f[10:11]
-            # the compositing forward's L1 epilogue leaves one pair of sums per TILE here (MomRasterArgs.l1_partials) instead of 2040
-            # workgroups adding into self.sums: added up only when somebody reads the loss (LazyLoss / _TileSums)
-            self.l1_part = torch.empty(((W + 15) // 16) * ((H + 15) // 16), 2, dtype=torch.float32, device=dev)
+            # L1 sums in spare words of the image scratch's header, which the rasterizer forward clears at the start of every step
+            # together with its tile counters: no memset of their own (mom_l1_loss_acc; the tile-row shard's logged loss)
+            self.sums = self.img[(-self.img.data_ptr()) % 256:][:256].view(torch.float32)[8:10]
+            # the compositing forward's L1 epilogue leaves one pair of sums per TILE here (MomRasterArgs.l1_partials): added up
+            # only when somebody reads the loss (LazyLoss / _TileSums)
+            self.l1_part = e(((W + 15) // 16) * ((H + 15) // 16), 2)
             self.ssim_dm = None                  # SSIM term: made on first use (lambda_dssim may be switched on later)
             self.binning = None
-        if not same_frame or pad > cap or 2 * pad < cap:
-            grew = same_frame and cap and pad > cap
+        self._per_gaussian(P, pad, dev, new_frame)
+        # the step after a change of P sizes its binning buffer from its own count (one sync); the buffer itself is kept if it fits
+        self.cap = 0
+        self._resize_next = False
+
+    def _set_bucket(self, ibucket):
+        """ibucket = [radii (P) | overflow word]: contiguous, so that a camera-batch shard agrees on both with ONE max-all-reduce.
+        The word is sticky across steps: its value moves with it when P (and so its position) changes.  A new bucket comes zeroed."""
+        old = getattr(self, "flags", None)
+        P = ibucket.numel() - 1
+        self.ibucket = ibucket
+        self.radii, self.flags = ibucket[:P], ibucket[P:]
+        if old is not None and old.device == ibucket.device and old.data_ptr() != self.flags.data_ptr():
+            self.flags.copy_(old)
+
+    def _begin(self, cam):
+        """(P, W, H, device) of this iteration, with the buffers made for them."""
+        g = self.g
+        dev = g._xyz.device
+        P = g._xyz.shape[0]
+        W, H = int(cam.image_width), int(cam.image_height)
+        self._ensure(P, W, H, dev)
+        if self._resize_next:                   # after a tile-row re-split, an overflow, or on request (exact_next)
+            self.cap, self._resize_next = 0, False
+        return P, W, H, dev
+
+    def exact_next(self):
+        """Size the binning buffer of the next step from that step's own instance count (one host sync): it cannot overflow."""
+        self._resize_next = True
+
+    def post_flag(self, slot):
+        """Copy the overflow word to ring slot `slot` behind everything enqueued so far; the returned event tells when the
+        slot is valid.  The word holds 0 or the tag of the FIRST step that overflowed since it was cleared."""
+        self.flag_ring[slot:slot + 1].copy_(self.flags, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return ev
+
+    def gather_moments(self):
+        """Before an iteration that reads or restructures the optimizer state (FusedStep: sharded Adam).  Here the state is whole."""
+
+    def _raster_forward(self, a, P, W, H, dev, s):
+        """Projection + binning, then the compositing into color / depth, its overflow into the sticky word.  Async: the binning
+        capacity comes from an earlier iteration's instance count (cap == 0: from this frame's own, one sync)."""
+        lib = self.lib
+        # an earlier iteration's instance count (whichever copy landed last: a sizing hint, read without blocking)
+        prev_R = int(self.nr_host[0])
+        N.check(lib.mom_raster_forward_geometry(C.byref(a), self.geom.data_ptr(), self.img.data_ptr(), self.radii.data_ptr(),
+                                                self.nr_dev.data_ptr(), self.nr_host.data_ptr(), s), "raster_geometry")
+        if self.cap == 0:                       # first call: size exactly (one sync)
+            torch.cuda.current_stream().synchronize()
+            prev_R = int(self.nr_host[0])
+        want = max(prev_R, int(prev_R * self.HEADROOM) + self.MARGIN)
+        if self.binning is None or want > self._bin_cap or want < self._bin_cap // 4:
+            self._bin_cap = want
+            self.binning = torch.empty(lib.mom_raster_binning_bytes(P, W, H, want), dtype=torch.uint8, device=dev)
+        self.cap = self._bin_cap          # the capacity every launch of this step is told (cap == 0 above: "size exactly")
+        N.check(lib.mom_raster_forward_render(C.byref(a), self.geom.data_ptr(), self.binning.data_ptr(), self.cap,
+                                              self.img.data_ptr(), self.color.data_ptr(), self.depth.data_ptr(),
+                                              self.flags.data_ptr(), s), "raster_render")
+
+    def _ssim_win(self):
+        """The SSIM window; the derivative maps and the map sum (mom_ssim_forward) are made on first use."""
+        if self.ssim_dm is None:
+            (W, H), dev = self._wh, self.color.device
+            self.ssim_dm = torch.empty((3, 3, H, W), dtype=torch.float32, device=dev)
+            self.ssim_sum = torch.empty(N.SSIM_SUM_SLOTS, dtype=torch.float64, device=dev)   # [0] = the sum
+        return ops._ssim_window()
+
+    def _ssim_full(self, gt, lam, s):
+        """loss += lambda_dssim * (1 - ssim(image, gt))  (train_4DGS.py:222-223) over the whole image: its gradient is added
+        into dimg, the map's sum is left in ssim_sum."""
+        win, (W, H), n = self._ssim_win(), self._wh, self.color.numel()
+        N.check(self.lib.mom_ssim_forward(3, H, W, win, self.color.data_ptr(), gt.data_ptr(), self.ssim_dm.data_ptr(),
+                                          self.ssim_sum.data_ptr(), s), "ssim_fwd")
+        N.check(self.lib.mom_ssim_backward(3, H, W, win, self.color.data_ptr(), gt.data_ptr(), self.ssim_dm.data_ptr(),
+                                           -lam / n, None, self.dimg.data_ptr(), s), "ssim_bwd")
+
+    def _set_grads(self):
+        """.grad of the six Gaussian parameters = the step's own gradient buffers (they persist across steps)."""
+        g = self.g
+        for p, gbuf in ((g._xyz, self.gxyz), (g._features_dc, self.gdc), (g._features_rest, self.grest), (g._scaling, self.gsc),
+                        (g._rotation, self.grot), (g._opacity, self.gop)):
+            p.grad = gbuf
+
+    def _loss(self, l1, reg, lam, n):
+        """(loss, radii, screen-space gradient) of the step; the loss is formed when read (LazyLoss).  l1: a device scalar, or
+        None for the per-tile sums the compositing epilogue left."""
+        sums = _TileSums(self.l1_part) if l1 is None else self.sums
+        loss = LazyLoss(sums if l1 is None else None, l1, reg, self.ssim_sum if lam != 0 else None, lam, n)
+        self.last = {"loss": loss, "mse_sum": _Lazy(sums, 1), "n": n}       # float(last["mse_sum"]): formed when read
+        return loss, self.radii, self.g2d
+
+
+class FusedStep(_Step):
+    """One fine-stage iteration (module docstring)."""
+
+    def __init__(self, gaussians, opt, hyper, background):
+        dn = gaussians._deformation.deformation_net
+        if not dn._fusable():
+            raise N.MomError("FusedStep needs the shipped deformation configuration (W=64, D=0, no_do, no_dshs)")
+        super().__init__(gaussians, opt, hyper, background)
+
+    # ------------------------------------------------------------------ buffers (re-made when P changes)
+    def _rows(self, P):
+        """Rows of the per-Gaussian buffers a tile-row shard gathers: world x S (DistContext.slice_rows), else P."""
+        dc = self.dist
+        return dc.world * dc.slice_rows(P) if (dc is not None and dc.mode == "tile-row") else P
+
+    def _per_gaussian(self, P, pad, dev, new_frame):
+        """Per-Gaussian storage is CAPACITY based: a densify / prune round changes P by a few percent every
+        hundred iterations (train_4DGS.py:264-290), and re-making fifty buffers each time sent the step after every round back to
+        the driver for fresh memory (tools/probe/c5_leg.py: the first round of a process cost 148 ms instead of 13 and the steps
+        behind it ran at 59 instead of 94 per second until the new pages had been touched).  Storage is re-made only when the
+        model outgrows it (then with a quarter of headroom) or shrinks below half of it; otherwise the attributes below are
+        re-sliced views of the same memory."""
+        self._pad = pad
+        e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        cap = getattr(self, "_rows_cap", 0)
+        if new_frame or pad > cap or 2 * pad < cap:
+            grew = not new_frame and cap and pad > cap
             cap = self._rows_cap = pad + pad // 4 if grew else pad
             st = self._store = {name: e(cap, cols) for name, cols, _ in self._ROW_BUFFERS}
             st["radii"] = torch.zeros(cap + 1, dtype=torch.int32, device=dev)      # + the sticky overflow word behind the P radii
@@ -92,22 +202,11 @@ class FusedStep:
             st["loc"] = (e(cap, 3), e(cap, 4))
             self.geom = torch.empty(self.lib.mom_raster_geom_bytes(cap), dtype=torch.uint8, device=dev)
             self.dh_scratch = torch.empty(self.lib.mom_deform_backward_scratch_bytes(cap), dtype=torch.uint8, device=dev)
-        # the step after a change of P sizes its binning buffer from its own count (one sync); the buffer itself is kept if it fits
-        self.cap = 0
-        self._resize_next = False
         st = self._store
         # (the gathered buffers of a tile-row shard carry world x S >= P rows; every kernel reads the first P)
         for name, _, padded in self._ROW_BUFFERS:
             setattr(self, name, st[name][:pad if padded else P])
-        # [radii (P) | overflow word]: contiguous, so that a camera-batch shard agrees on both with ONE max-all-reduce.  The word is
-        # sticky across steps: its value moves with it when P (and so its position) changes
-        old_flags = getattr(self, "flags", None)
-        self.ibucket = st["radii"][:P + 1]
-        self.radii, self.flags = self.ibucket[:P], self.ibucket[P:]
-        if old_flags is not None and old_flags.device == self.flags.device and old_flags.data_ptr() != self.flags.data_ptr():
-            self.flags.copy_(old_flags)
-        elif old_flags is None or old_flags.device != self.flags.device:
-            self.flags.zero_()
+        self._set_bucket(st["radii"][:P + 1])
         # parameter gradients (persist across steps; .grad points at them).  They live in two flat buckets so that a
         # multi-GPU run all-reduces them in place, without packing: `early` (final once the activation backward has run:
         # SH, scaling, rotation, opacity = 56 floats per Gaussian) and `late` (xyz + the deformation field, final only
@@ -171,24 +270,9 @@ class FusedStep:
             return                       # the model was restructured since the last step: its state is whole (the round gathered first)
         dc.gather_moments(self.g.optimizer, self._app_params(), self._cut, self._chunk)
 
-    RING = 64
     OVERLAP_DW = os.environ.get("MOM_OVERLAP_DW", "1") != "0"     # the MLP weight-gradient kernel on a second stream, beside the HexPlane backward
     EARLY_ADAM = os.environ.get("MOM_EARLY_ADAM", "1") != "0"     # the appearance parameters' Adam on that stream, beside the MLP backward
     side = None
-    keep_all_tiles = False            # True: bin whole rectangles like the reference (MomRasterArgs.keep_all_tiles; measurement only)
-    HEADROOM, MARGIN = 1.5, 65536     # binning capacity = HEADROOM x an earlier frame's instance count + MARGIN
-
-    def exact_next(self):
-        """Size the binning buffer of the next step from that step's own instance count (one host sync): it cannot overflow."""
-        self._resize_next = True
-
-    def post_flag(self, slot):
-        """Copy the overflow word to ring slot `slot` behind everything enqueued so far; the returned event tells when the
-        slot is valid.  The word holds 0 or the tag of the FIRST step that overflowed since it was cleared."""
-        self.flag_ring[slot:slot + 1].copy_(self.flags, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return ev
 
     def _hex_scratch_for(self, hp, rows, dev):
         """Scratch of the two-pass HexPlane backward for `rows` points (common-factor rows + the time lines): kept while it is
@@ -242,23 +326,17 @@ class FusedStep:
         """early_adam: callable(list of parameters) or None -- see EARLY_ADAM below; the caller promises that its optimizer step
         for this iteration follows with nothing in between that reads or replaces those parameters."""
         g, lib, s = self.g, self.lib, N.current_stream()
-        dev = g._xyz.device
-        P = g._xyz.shape[0]
-        W, H = int(cam.image_width), int(cam.image_height)
-        self._ensure(P, W, H, dev)
+        P, W, H, dev = self._begin(cam)
         sharded = bool(self._chunk) and early_adam is not None and self.EARLY_ADAM     # this iteration takes the sharded-Adam path
         if self._chunk:
             self._rehome()
-        if self._resize_next:                   # after a tile-row re-split, an overflow, or on request (exact_next)
-            self.cap, self._resize_next = 0, False
         view, proj, campos, gt = cam.device_tensors(dev)
         dn = g._deformation.deformation_net
         field = dn.grid
         planes, mlp = self._deform_grads()
-        xyz, scal, rot, opac = g._xyz.detach(), g._scaling.detach(), g._rotation.detach(), g._opacity.detach()
+        xyz, f_dc, f_rest, scal, rot, opac = ops.gaussian_params(g, "FusedStep")
         flow = g._scene_flow if g._scene_flow.is_contiguous() else g._scene_flow.contiguous()
-        for t in (xyz, scal, rot, opac, g._features_dc, g._features_rest):
-            assert t.is_contiguous()
+        lam = float(self.opt.lambda_dssim)
         time = float(cam.time)
         order = field._processing_order(xyz)
         optr = None if order is None else order.data_ptr()
@@ -361,33 +439,20 @@ class FusedStep:
             lines_kept = ops.field_forward(hp, md, P, xyz, time, order, scal, rot, flow, coef, self.pts, self.sc_d, self.rot_d, self.feat, self.a0,
                               opac, self.sc, self.rot, self.op, s)
         # ---- rasterizer forward (async: capacity from the previous iterations, checked below)
-        a = N.MomRasterArgs()
-        a.P, a.D, a.M, a.W, a.H = P, g.active_sh_degree, 16, W, H
+        a = ops.raster_args(cam, view, proj, campos, self.bg, P, g.active_sh_degree, self.pts, f_dc, f_rest, self.op, self.sc, self.rot,
+                            False, 1.0, False, self.keep_all_tiles)
         a.accum_cleared = 1                     # on the second stream, above
-        a.background, a.means3D = self.bg.data_ptr(), self.pts.data_ptr()
-        a.shs, a.shs_rest = g._features_dc.data_ptr(), g._features_rest.data_ptr()
-        a.colors_precomp, a.opacities = None, self.op.data_ptr()
-        a.scales, a.rotations, a.cov3D_precomp = self.sc.data_ptr(), self.rot.data_ptr(), None
-        a.viewmatrix, a.projmatrix, a.campos = view.data_ptr(), proj.data_ptr(), campos.data_ptr()
-        a.scale_modifier = 1.0
-        a.tan_fovx, a.tan_fovy = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
-        a.prefiltered, a.debug = 0, 0
-        a.keep_all_tiles = int(self.keep_all_tiles)
-        # L1 (its gradient image and its sums) in the compositing kernel's epilogue.  A tile-row shard too, unless its forward renders a
-        # halo (SSIM term): the kernel runs this rank's tiles only, leaves one pair of sums per tile, and the rank adds up ITS rows
+        # L1 (its gradient image and its sums) in the compositing kernel's epilogue, one pair of sums per tile.  A tile-row shard too,
+        # unless its forward renders a halo (SSIM term): the kernel runs this rank's tiles only, and the rank adds up ITS rows
         tr_rows = dc is not None and dc.mode == "tile-row"
         l1_scaled = False
-        fuse_l1 = not tr_rows or (L1_PARTIALS and float(self.opt.lambda_dssim) == 0)
+        fuse_l1 = not tr_rows or lam == 0
         if fuse_l1:
-            a.l1_target, a.l1_grad = gt.data_ptr(), self.dimg.data_ptr()
+            a.l1_target, a.l1_grad, a.l1_partials = gt.data_ptr(), self.dimg.data_ptr(), self.l1_part.data_ptr()
             # camera-batch shard: the batch loss is the mean over the ranks' cameras, every gradient carries 1 / world (below)
             # -- in the epilogue itself when the loss is L1 alone (with the SSIM term the whole gradient image is scaled once, below)
-            l1_scaled = dc is not None and dc.mode == "camera" and float(self.opt.lambda_dssim) == 0
+            l1_scaled = dc is not None and dc.mode == "camera" and lam == 0
             a.l1_grad_scale = 1.0 / dc.world if l1_scaled else 0.0
-            if L1_PARTIALS or tr_rows:
-                a.l1_partials = self.l1_part.data_ptr()
-            else:
-                a.l1_sums = self.sums.data_ptr()
         a.overflow_tag = self.next_tag          # what this step leaves in the sticky word if its binning overflows (Trainer numbers the steps)
         rows = fwd_rows = None
         if dc is not None and dc.mode == "tile-row":
@@ -397,24 +462,10 @@ class FusedStep:
             # exchanged (the neighbour composites the same rows to the same bits).  The backward covers the own rows only.
             gy = (H + 15) // 16
             rows = dc.rows(gy)
-            halo = 1 if (float(self.opt.lambda_dssim) != 0 and rows[1] > rows[0]) else 0
+            halo = 1 if (lam != 0 and rows[1] > rows[0]) else 0
             fwd_rows = (max(rows[0] - halo, 0), min(rows[1] + halo, gy))
             a.tile_row0, a.tile_row1 = fwd_rows
-        # an earlier iteration's instance count (whichever copy landed last: a sizing hint, read without blocking)
-        prev_R = int(self.nr_host[0])
-        N.check(lib.mom_raster_forward_geometry(C.byref(a), self.geom.data_ptr(), self.img.data_ptr(), self.radii.data_ptr(),
-                                                self.nr_dev.data_ptr(), self.nr_host.data_ptr(), s), "raster_geometry")
-        if self.cap == 0:                       # first call: size exactly (one sync)
-            torch.cuda.current_stream().synchronize()
-            prev_R = int(self.nr_host[0])
-        want = max(prev_R, int(prev_R * self.HEADROOM) + self.MARGIN)
-        if self.binning is None or want > self._bin_cap or want < self._bin_cap // 4:
-            self._bin_cap = want
-            self.binning = torch.empty(lib.mom_raster_binning_bytes(P, W, H, want), dtype=torch.uint8, device=dev)
-        self.cap = self._bin_cap          # the capacity every launch of this step is told (cap == 0 above: "size exactly")
-        N.check(lib.mom_raster_forward_render(C.byref(a), self.geom.data_ptr(), self.binning.data_ptr(), self.cap,
-                                              self.img.data_ptr(), self.color.data_ptr(), self.depth.data_ptr(),
-                                              self.flags.data_ptr(), s), "raster_render")
+        self._raster_forward(a, P, W, H, dev, s)
         early_works = []                        # camera-batch shard: what the early Adam launch must see reduced (below)
         if dc is not None and dc.mode != "camera":
             early_works.append(dc.start(self.flags, "max"))         # every rank skips (and later replays) the same steps
@@ -429,22 +480,15 @@ class FusedStep:
         # tile-row shard: the ranks' deformation gradients are SUMMED (each holds its slice's share); the regulariser's gradient,
         # which every rank computes in full, must enter that sum once
         reg_scale = 1.0 / dc.world if dc is not None else 1.0
-        lam = float(self.opt.lambda_dssim)
         if lam != 0:
             # loss += lambda_dssim * (1 - ssim(image, gt))  (train_4DGS.py:222-223): its gradient is added into dimg
-            win = ops._ssim_window()
-            if self.ssim_dm is None:         # derivative maps and the map sum (mom_ssim_forward)
-                self.ssim_dm = torch.empty((3, 3, H, W), dtype=torch.float32, device=dev)
-                self.ssim_sum = torch.empty(N.SSIM_SUM_SLOTS, dtype=torch.float64, device=dev)   # [0] = the sum
             if rows is None:
-                N.check(lib.mom_ssim_forward(3, H, W, win, self.color.data_ptr(), gt.data_ptr(), self.ssim_dm.data_ptr(),
-                                             self.ssim_sum.data_ptr(), s), "ssim_fwd")
-                N.check(lib.mom_ssim_backward(3, H, W, win, self.color.data_ptr(), gt.data_ptr(), self.ssim_dm.data_ptr(),
-                                              -lam / n, None, self.dimg.data_ptr(), s), "ssim_bwd")
+                self._ssim_full(gt, lam, s)
             elif rows[1] > rows[0]:
                 # the slab this rank rendered (own rows + halo), as a pitched view of the full buffers: map rows of the own
                 # tile rows count toward the sum; derivative maps are kept 5 rows beyond them (up to the image's own edges,
                 # where zero padding is the reference's behaviour) and are zero elsewhere
+                win = self._ssim_win()
                 ys0, ys1 = fwd_rows[0] * 16, min(H, fwd_rows[1] * 16)
                 y0, y1 = rows[0] * 16, min(H, rows[1] * 16)
                 off = ys0 * W * 4
@@ -455,18 +499,15 @@ class FusedStep:
                                                    self.ssim_dm.data_ptr() + off, -lam / n, None, self.dimg.data_ptr() + off, s),
                         "ssim_bwd_slab")
             else:
+                self._ssim_win()
                 self.ssim_sum.zero_()
         if dc is not None and dc.mode == "camera" and not (fuse_l1 and l1_scaled):
             self.dimg.mul_(inv_world)            # (L1 alone: the forward's epilogue wrote the gradient image with the factor in it)
         # ---- rasterizer backward
         ops.stream_wait_mark(s, ops.MARK_BUCKET)      # the gradient bucket is cleared and holds the regulariser's share
-        gr = N.MomRasterGrads()
+        gr = ops.raster_grads(self.g2d, self.gcol, self.gop, self.gxyz, self.gcov, self.gdc, self.grest, self.gsc, self.grot)
         # scale / rotation / opacity gradients leave the projection backward already through exp / normalize / sigmoid
         # (MomRasterGrads.act_rotations_raw): no activation-backward launch behind it
-        gr.dL_dmeans2D, gr.dL_dcolors, gr.dL_dopacity = self.g2d.data_ptr(), self.gcol.data_ptr(), self.gop.data_ptr()
-        gr.dL_dmeans3D, gr.dL_dcov3D = self.gxyz.data_ptr(), self.gcov.data_ptr()
-        gr.dL_dsh, gr.dL_dsh_rest = self.gdc.data_ptr(), self.grest.data_ptr()
-        gr.dL_dscales, gr.dL_drotations = self.gsc.data_ptr(), self.grot.data_ptr()
         gr.act_rotations_raw = self.rot_d.data_ptr()
         if dc is not None and dc.mode == "camera":
             # the deformation backward still reads this rank's own d_sc / d_rot while the bucket that holds them is being reduced in
@@ -633,25 +674,86 @@ class FusedStep:
             dc.start(self._dg_all[:4 + self._dg_n], "sum")
             dc.finish()
         # ---- hand the gradients to the parameters
-        for p, gbuf in ((g._xyz, self.gxyz), (g._features_dc, self.gdc), (g._features_rest, self.grest), (g._scaling, self.gsc),
-                        (g._rotation, self.grot), (g._opacity, self.gop)):
-            p.grad = gbuf
+        self._set_grads()
         for p, gbuf in zip(planes, self._dg_planes):
             p.grad = gbuf
         for p, gbuf in zip(mlp, self._dg_mlp):
             p.grad = gbuf
         if rows is None:
-            l1 = None                        # formed lazily from self.sums (LazyLoss): no kernels for a value nobody may read
+            l1 = None                        # formed lazily from the per-tile sums (LazyLoss): no kernels for a value nobody may read
         else:
             # the image holds this rank's rows only: the logged values are the sums over the ranks, reduced above
             self.sums.copy_(self._tr_sums[:2])
             if lam != 0:
                 self.ssim_sum[:1].copy_(self._tr_sums[2:3])
             l1 = self._tr_sums[0] / n
-        sums = _TileSums(self.l1_part) if (fuse_l1 and L1_PARTIALS and rows is None) else self.sums
-        loss = LazyLoss(sums if l1 is None else None, l1, reg, self.ssim_sum if lam != 0 else None, lam, n)
-        self.last = {"loss": loss, "mse_sum": _Lazy(sums, 1), "n": n}       # float(last["mse_sum"]): formed when read
-        return loss, self.radii, self.g2d
+        return self._loss(l1, reg, lam, n)
+
+
+class FusedCoarseStep(_Step):
+    """One coarse-stage training iteration as an explicit launch sequence -- no autograd graph, no activated copies of the parameters.
+
+    The coarse stage (train_4DGS.py:149-297 with stage "coarse", the first 3 000 iterations of every run) renders the Gaussians
+    WITHOUT the deformation field: the rasterizer's inputs are the model's own parameters through exp / normalize / sigmoid
+    (gaussian_renderer/__init__.py:113,130-132).  So the step is the rasterizer and the loss alone:
+
+        projection on the raw parameters (MomRasterArgs.params_raw) -> binning -> compositing forward with the L1 epilogue
+        (+ SSIM when lambda_dssim != 0) -> compositing backward -> projection backward, which writes the six parameter gradients
+        through the activations and, below densify_until_iter, the densification statistics (MomRasterGrads.stats_*).
+
+    It leaves `.grad` on _xyz, _features_dc, _features_rest, _scaling, _rotation and _opacity only: the deformation network, the
+    HexPlane planes and _scene_flow keep None, so optimizer.step() skips them exactly as torch Adam does in the reference's coarse
+    stage.  The overflow word and the rest of _Step behave as in FusedStep, so the overflow / replay machinery of train.Trainer
+    runs unchanged.  `tests/test_coarse_stage_gpu.py` checks this step against the op-by-op autograd path."""
+
+    def __init__(self, gaussians, opt, hyper, background):
+        super().__init__(gaussians, opt, hyper, background)
+        self.stats_done = False       # whether the last step's projection backward updated the densification statistics
+
+    def _per_gaussian(self, P, pad, dev, new_frame):
+        """Made anew for every P."""
+        e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        self._set_bucket(torch.zeros(P + 1, dtype=torch.int32, device=dev))
+        self.geom = torch.empty(self.lib.mom_raster_geom_bytes(P), dtype=torch.uint8, device=dev)
+        # the six parameter gradients (persist across steps; .grad points at them) + the screen-space gradient and the internal ones
+        self._grads = e(59 * P)
+        cut = [0, 3 * P, 6 * P, 51 * P, 54 * P, 58 * P, 59 * P]
+        seg = lambda i: self._grads[cut[i]:cut[i + 1]]
+        self.gxyz, self.gdc, self.grest = seg(0).view(P, 3), seg(1).view(P, 1, 3), seg(2).view(P, 15, 3)
+        self.gsc, self.grot, self.gop = seg(3).view(P, 3), seg(4).view(P, 4), seg(5).view(P, 1)
+        self.g2d, self.gcol, self.gcov = e(P, 3), e(P, 3), e(P, 6)
+
+    def forward_backward(self, cam, delta_scale=1, early_adam=None, stats=False):
+        """One coarse iteration up to (not including) the optimizer step.  stats: update the densification statistics in the
+        projection backward (the caller's iteration is below densify_until_iter).  early_adam is ignored: there is no deformation
+        backward to hide Adam under.  Returns (loss, radii, screen-space gradient) like FusedStep.forward_backward."""
+        g, lib, s = self.g, self.lib, N.current_stream()
+        P, W, H, dev = self._begin(cam)
+        view, proj, campos, gt = cam.device_tensors(dev)
+        xyz, f_dc, f_rest, scal, rot, opac = ops.gaussian_params(g, "FusedCoarseStep")
+        # the raw parameters: the projection applies exp / normalize / sigmoid itself (gaussian_renderer/__init__.py:130-132)
+        a = ops.raster_args(cam, view, proj, campos, self.bg, P, g.active_sh_degree, xyz, f_dc, f_rest, opac, scal, rot, True, 1.0,
+                            False, self.keep_all_tiles)
+        a.l1_target, a.l1_grad, a.l1_partials = gt.data_ptr(), self.dimg.data_ptr(), self.l1_part.data_ptr()
+        a.overflow_tag = self.next_tag
+        self._raster_forward(a, P, W, H, dev, s)
+        lam = float(self.opt.lambda_dssim)
+        if lam != 0:
+            self._ssim_full(gt, lam, s)
+        gr = ops.raster_grads(self.g2d, self.gcol, self.gop, self.gxyz, self.gcov, self.gdc, self.grest, self.gsc, self.grot)
+        if stats:
+            # train_4DGS.py:266 in the projection backward's epilogue; a step whose binning overflowed leaves them alone (the replay
+            # makes them), as mom_densify_stats does with the same word
+            for t in (g.max_radii2D, g.xyz_gradient_accum, g.denom):
+                if t.numel() != P or not t.is_contiguous() or t.dtype != torch.float32:
+                    raise N.MomError("FusedCoarseStep: the densification accumulators must be contiguous float32, one per Gaussian")
+            gr.stats_max_radii2D, gr.stats_grad_accum = g.max_radii2D.data_ptr(), g.xyz_gradient_accum.data_ptr()
+            gr.stats_denom, gr.stats_skip_if_nonzero = g.denom.data_ptr(), self.flags.data_ptr()
+        N.check(lib.mom_raster_backward(C.byref(a), self.radii.data_ptr(), self.geom.data_ptr(), self.binning.data_ptr(),
+                                        self.cap, self.img.data_ptr(), self.dimg.data_ptr(), None, C.byref(gr), s), "raster_bwd")
+        self.stats_done = bool(stats)
+        self._set_grads()
+        return self._loss(None, None, lam, self.color.numel())
 
 
 class _TileSums:

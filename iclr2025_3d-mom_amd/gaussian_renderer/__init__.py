@@ -29,19 +29,20 @@ def render_streams():
     return _RENDER_STREAMS
 
 
-def _nograd_fast_path_applies(cam, pc, pipe, stage, override_color, cam_type):
-    """Forward-only launch sequence (fused_render.py): no gradients wanted, fine stage with the shipped deformation configuration
-    or coarse stage, SH colours and covariances computed by the rasterizer, an ordinary camera, everything on the GPU."""
-    if torch.is_grad_enabled() or stage not in ("fine", "coarse") or override_color is not None or cam_type == "PanopticSports":
+def _fused_path_applies(cam, pc, pipe, stage, override_color, cam_type):
+    """Whether this frame can take a fused launch sequence (fused_render.py without gradients, fused_autograd.py with them): fine
+    stage with the shipped deformation configuration or coarse stage, SH colours and covariances computed by the rasterizer, an
+    ordinary camera, everything on the GPU.  (Grad mode and pipe.per_op_autograd are for the caller to check.)"""
+    if stage not in ("fine", "coarse") or override_color is not None or cam_type == "PanopticSports":
         return False
     if pipe.compute_cov3D_python or pipe.convert_SHs_python or not hasattr(cam, "device_tensors"):
         return False
-    if not pc.get_xyz.is_cuda or pc.get_xyz.shape[0] == 0 or ops.BACKEND.name != "hip":
+    if not pc.get_xyz.is_cuda or pc.get_xyz.shape[0] == 0 or ops.BACKEND.name != "hip" or pc._features_rest.shape[1] != 15:
         return False
     if stage == "coarse":
-        return pc._features_rest.shape[1] == 15
+        return True
     dn = getattr(pc._deformation, "deformation_net", None)
-    return dn is not None and hasattr(dn, "_fusable") and dn._fusable() and pc._features_rest.shape[1] == 15
+    return dn is not None and hasattr(dn, "_fusable") and dn._fusable()
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, stage="fine",
@@ -54,16 +55,18 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         # gaussian_renderer/__init__.py:101-103): None raises there, so it raises here, on every path
         raise TypeError("unsupported operand type(s) for *: 'NoneType' and 'Tensor' (render(): delta_scale is required "
                         "outside the coarse stage)")
-    if _RENDER_STREAMS > 1 and _nograd_fast_path_applies(viewpoint_camera, pc, pipe, stage, override_color, cam_type):
-        pool = getattr(pc, "_fused_render_pool", None)
-        if pool is None or pool.n != _RENDER_STREAMS:
-            from ..fused_render import FusedRenderPool
-            pool = pc._fused_render_pool = FusedRenderPool(pc, _RENDER_STREAMS)
-        image, depth, radii, visible, stream, ready = pool.render(viewpoint_camera, bg_color, delta_scale, scaling_modifier, pipe.debug,
-                                                                  stage=stage)
-        return {"render": image, "viewspace_points": pool.zero_points(), "visibility_filter": visible, "radii": radii,
-                "depth": depth, "flow_loss": 0, "stream": stream, "ready": ready}
-    if _nograd_fast_path_applies(viewpoint_camera, pc, pipe, stage, override_color, cam_type):
+    fused = _fused_path_applies(viewpoint_camera, pc, pipe, stage, override_color, cam_type)
+    if fused and not torch.is_grad_enabled():
+        # forward-only launch sequence (fused_render.py)
+        if _RENDER_STREAMS > 1:
+            pool = getattr(pc, "_fused_render_pool", None)
+            if pool is None or pool.n != _RENDER_STREAMS:
+                from ..fused_render import FusedRenderPool
+                pool = pc._fused_render_pool = FusedRenderPool(pc, _RENDER_STREAMS)
+            image, depth, radii, visible, stream, ready = pool.render(viewpoint_camera, bg_color, delta_scale, scaling_modifier,
+                                                                      pipe.debug, stage=stage)
+            return {"render": image, "viewspace_points": pool.zero_points(), "visibility_filter": visible, "radii": radii,
+                    "depth": depth, "flow_loss": 0, "stream": stream, "ready": ready}
         fr = getattr(pc, "_fused_render", None)
         if fr is None:
             from ..fused_render import FusedRender
@@ -78,17 +81,16 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         screenspace_points.retain_grad()
     except Exception:
         pass
-    from .. import fused_autograd
-    if fused_autograd.applies(viewpoint_camera, pc, pipe, stage, override_color, cam_type):
-        # the whole fine-stage forward of this camera as ONE autograd node (fused_autograd.py); pipe.per_op_autograd = True keeps
-        # the op-by-op path below
-        image, depth, radii = fused_autograd.render(viewpoint_camera, pc, pipe, bg_color, delta_scale, scaling_modifier,
-                                                    screenspace_points)
-        return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
-                "depth": depth, "flow_loss": 0}
-    if fused_autograd.applies_coarse(viewpoint_camera, pc, pipe, stage, override_color, cam_type):
-        # the coarse stage's forward (raw-parameter projection + binning + compositing) as one autograd node, likewise
-        image, depth, radii = fused_autograd.render_coarse(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, screenspace_points)
+    if fused and not getattr(pipe, "per_op_autograd", False):
+        # the whole forward of this camera as ONE autograd node (fused_autograd.py; coarse stage: raw-parameter projection +
+        # binning + compositing); pipe.per_op_autograd = True keeps the op-by-op path below
+        from .. import fused_autograd
+        if stage == "coarse":
+            image, depth, radii = fused_autograd.render_coarse(viewpoint_camera, pc, pipe, bg_color, scaling_modifier,
+                                                               screenspace_points)
+        else:
+            image, depth, radii = fused_autograd.render(viewpoint_camera, pc, pipe, bg_color, delta_scale, scaling_modifier,
+                                                        screenspace_points)
         return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
                 "depth": depth, "flow_loss": 0}
 

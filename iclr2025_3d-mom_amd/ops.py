@@ -199,6 +199,47 @@ def field_forward(hp, md, P, xyz, time, order, scal, rot, flow, coef, pts, sc_d,
     return False
 
 
+# --------------------------------------------------------------------------- rasterizer arguments (the fused paths)
+def gaussian_params(g, who):
+    """(xyz, f_dc, f_rest, scaling, rotation, opacity) of model g, detached; MomError unless every one is contiguous (the kernels
+    read them through raw pointers).  (.data: a detached alias like .detach(), at half the host time -- the fused steps are paced
+    by the host at small sizes.)"""
+    ps = g._xyz.data, g._features_dc.data, g._features_rest.data, g._scaling.data, g._rotation.data, g._opacity.data
+    for t in ps:
+        if not t.is_contiguous():
+            raise N.MomError(f"{who}: the Gaussian parameters must be contiguous")
+    return ps
+
+
+def raster_args(cam, view, proj, campos, bg, P, D, means, f_dc, f_rest, opac, scales, rots, params_raw, scale_modifier, debug,
+                keep_all_tiles):
+    """MomRasterArgs of one camera with 16 SH coefficients read through two pointers (DC, rest).  params_raw: scales / rots / opac
+    are the raw parameters and the projection applies exp / normalize / sigmoid itself.  The struct holds raw pointers only: the
+    caller keeps every tensor behind them alive until the last launch that reads it."""
+    a = N.MomRasterArgs()
+    a.P, a.D, a.M, a.W, a.H = P, D, 16, int(cam.image_width), int(cam.image_height)
+    a.background, a.means3D = bg.data_ptr(), means.data_ptr()
+    a.shs, a.shs_rest = f_dc.data_ptr(), f_rest.data_ptr()
+    a.opacities, a.scales, a.rotations = opac.data_ptr(), scales.data_ptr(), rots.data_ptr()
+    a.params_raw = int(params_raw)
+    a.viewmatrix, a.projmatrix, a.campos = view.data_ptr(), proj.data_ptr(), campos.data_ptr()
+    a.scale_modifier = float(scale_modifier)
+    a.tan_fovx, a.tan_fovy = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
+    a.debug = int(bool(debug))
+    a.keep_all_tiles = int(keep_all_tiles)
+    return a
+
+
+def raster_grads(g2d, gcol, gop, gxyz, gcov, gdc, grest, gsc, grot):
+    """MomRasterGrads with the nine gradient outputs every backward of the fused paths writes."""
+    gr = N.MomRasterGrads()
+    gr.dL_dmeans2D, gr.dL_dcolors, gr.dL_dopacity = g2d.data_ptr(), gcol.data_ptr(), gop.data_ptr()
+    gr.dL_dmeans3D, gr.dL_dcov3D = gxyz.data_ptr(), gcov.data_ptr()
+    gr.dL_dsh, gr.dL_dsh_rest = gdc.data_ptr(), grest.data_ptr()
+    gr.dL_dscales, gr.dL_drotations = gsc.data_ptr(), grot.data_ptr()
+    return gr
+
+
 # --------------------------------------------------------------------------- fused deformation MLP
 class DeformMLPFunction(torch.autograd.Function):
     """(pts, scales, rots) = fused trunk + pos/scales/rotations heads + residual adds

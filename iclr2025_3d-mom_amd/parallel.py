@@ -486,7 +486,7 @@ def attach(trainer, rank, world, seed=6666, mode="camera", shard_adam=None):
         shard_adam = os.environ.get("MOM_SHARD_ADAM", "0") == "1"
     fused = getattr(trainer, "fused", None)
     if fused is not None and getattr(trainer, "stage", "fine") == "coarse":
-        # the coarse fused step (fused_coarse.py) is single-GPU: a sharded coarse stage runs on the autograd path with
+        # the coarse fused step (fused_step.FusedCoarseStep) is single-GPU: a sharded coarse stage runs on the autograd path with
         # sync_param_grads, as without fused=True
         fused = trainer.fused = None
     if shard_adam and (fused is None or mode != "camera"):

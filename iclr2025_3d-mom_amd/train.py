@@ -27,15 +27,12 @@ class Trainer:
         self.ema_loss, self.ema_psnr = 0.0, 0.0
         self.last = {}
         self.dist = None     # set by parallel.attach(): camera-batch shard, one camera per rank
-        # fused=True: the iteration runs as an explicit launch sequence (fused_step.py; coarse stage: fused_coarse.py) instead of
-        # render()+autograd
+        # fused=True: the iteration runs as an explicit launch sequence (fused_step.py: FusedStep, coarse stage FusedCoarseStep)
+        # instead of render()+autograd
         self.fused = None
-        if fused and stage == "fine" and opt.batch_size == 1:
-            from .fused_step import FusedStep
-            self.fused = FusedStep(gaussians, opt, hyper, self.background)
-        elif fused and stage == "coarse" and opt.batch_size == 1:
-            from .fused_coarse import FusedCoarseStep
-            self.fused = FusedCoarseStep(gaussians, opt, hyper, self.background)
+        if fused and stage in ("fine", "coarse") and opt.batch_size == 1:
+            from .fused_step import FusedCoarseStep, FusedStep
+            self.fused = (FusedStep if stage == "fine" else FusedCoarseStep)(gaussians, opt, hyper, self.background)
         # every fused step since the last verified one: (serial, iteration, camera); and the overflow-word read-backs in flight:
         # (serial of the last step they cover, ring slot, event)
         self._log = deque()

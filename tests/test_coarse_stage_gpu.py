@@ -1,4 +1,4 @@
-"""The coarse stage (no deformation field) on its three accelerated paths -- the fused step (fused_coarse.py), render() as one
+"""The coarse stage (no deformation field) on its three accelerated paths -- the fused step (fused_step.FusedCoarseStep), render() as one
 autograd node (fused_autograd.render_coarse) and the no-grad fast path -- against the op-by-op autograd path, and the raw-parameter
 projection kernels (MomRasterArgs.params_raw, MomRasterGrads.stats_*) against the activation kernel + the plain projection."""
 import ctypes as C

@@ -3,7 +3,7 @@ fused step at the same config for comparison:
 
   op-by-op   render() with pipe.per_op_autograd = True (torch activations, the rasterizer node) + loss.backward() + optimizer.step()
   one-node   render() as one autograd node (fused_autograd.render_coarse) + loss.backward() + optimizer.step()
-  fused      Trainer(stage="coarse", fused=True): the explicit launch sequence of fused_coarse.py
+  fused      Trainer(stage="coarse", fused=True): the explicit launch sequence of fused_step.FusedCoarseStep
 
 Every path runs Trainer.step over a window of coarse iterations with no densify / prune / opacity-reset / SH boundary
 (2601..2690 by default), after a warm-up inside the same window, and trainer.drain() before the clock stops.
