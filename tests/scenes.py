@@ -55,3 +55,14 @@ def random_gaussians(P, seed=0, W=128, H=96, zrange=(1.0, 6.0), scale=(-4.5, -2.
     shs[:, 0, :] += rng.uniform(0, 2.0, (P, 3)).astype(np.float32)
     bg = np.array([0.1, 0.2, 0.3], np.float32)
     return dict(means3D=means, scales=scales, rotations=rots, opacities=opac, shs=shs, bg=bg, **cam)
+
+
+def clamp_some_channels(s, seed=0, frac=0.3):
+    """Give a fraction of the Gaussians a strongly negative DC term in one channel (in place): their colour from SH falls below
+    zero there, so the rasterizer clamps it and its backward masks that channel's colour gradient."""
+    rng = np.random.default_rng(seed)
+    P = s["shs"].shape[0]
+    sel = np.nonzero(rng.random(P) < frac)[0]
+    ch = rng.integers(0, 3, len(sel))
+    s["shs"][sel, 0, ch] = rng.uniform(-4.0, -1.5, len(sel)).astype(np.float32)
+    return s

@@ -1,6 +1,7 @@
 """The coarse stage (no deformation field) on its three accelerated paths -- the fused step (fused_step.FusedCoarseStep), render() as one
 autograd node (fused_autograd.render_coarse) and the no-grad fast path -- against the op-by-op autograd path, and the raw-parameter
 projection kernels (MomRasterArgs.params_raw, MomRasterGrads.stats_*) against the activation kernel + the plain projection."""
+import contextlib
 import ctypes as C
 import importlib
 import os
@@ -23,7 +24,7 @@ def _mods():
             importlib.import_module("iclr2025_3d-mom_amd.train"), importlib.import_module("iclr2025_3d-mom_amd._native"))
 
 
-def _coarse_state(cfg, fused=False, per_op=False, lambda_dssim=0.0, trained=True, **opt_kw):
+def _coarse_state(cfg, fused=False, per_op=False, lambda_dssim=0.0, trained=True, device="cuda", **opt_kw):
     A, S, T, _ = _mods()
     args, lp, op, pp, hp = A.default_args(time_resolution=cfg["time_res"])
     op.lambda_dssim = lambda_dssim
@@ -32,7 +33,7 @@ def _coarse_state(cfg, fused=False, per_op=False, lambda_dssim=0.0, trained=True
     pp.per_op_autograd = per_op
     torch.manual_seed(6666)
     scene = S.SyntheticScene(cfg["P"], cfg["F"], cfg["W"], cfg["H"], seed=6666)
-    g = S.GaussianModel(lp.sh_degree, hp, device=torch.device("cuda"))
+    g = S.GaussianModel(lp.sh_degree, hp, device=torch.device(device))
     scene.init_gaussians(g)
     if trained:
         scene.make_trained_like(g)
@@ -125,7 +126,7 @@ def _bwd(ctx, raw, stats=None, skip=None):
 
 
 @pytest.mark.parametrize("cfg", [TINY, C2], ids=["tiny", "c2"])
-@pytest.mark.parametrize("D", [0, 3])
+@pytest.mark.parametrize("D", [0, 1, 2, 3])
 def test_raw_projection_and_its_backward_are_bit_equal_to_the_activation_kernel_path(cfg, D):
     scene, g, trainer = _coarse_state(cfg)
     cam = trainer.cams[1]
@@ -302,6 +303,93 @@ def test_coarse_half_of_the_g10_curve_on_the_fused_coarse_step():
     assert float(rel[:5].max()) <= 1e-4, rel[:5]
     assert float(rel.max()) <= 2e-3, (int(rel.argmax()), float(rel.max()))
     _untouched(g)
+
+
+PARAMS = ("xyz", "f_dc", "f_rest", "scaling", "rotation", "opacity")
+
+
+def _params(g):
+    return dict(zip(PARAMS, (g._xyz, g._features_dc, g._features_rest, g._scaling, g._rotation, g._opacity)))
+
+
+def _coarse_one_step(device, fused, per_op, D, it=2601):
+    """One coarse iteration from the trained-like state (nonzero _features_rest) rendered at SH degree D; returns the loss, the six
+    gradients (Adam's first moment after ONE step is 0.1 * gradient exactly) and the statistics."""
+    from oracle import cpu_backend
+    with cpu_backend.installed() if device == "cpu" else contextlib.nullcontext():
+        scene, g, trainer = _coarse_state(TINY, fused=fused, per_op=per_op, device=device)
+        assert (trainer.fused is not None) == fused
+        g.active_sh_degree = D
+        loss = float(trainer.step(it, cams=[trainer.cams[1]]))
+        if device != "cpu":
+            trainer.drain()
+            torch.cuda.synchronize()
+        grads = {k: g.optimizer.state[p]["exp_avg"].detach().float().cpu().numpy() * 10.0 for k, p in _params(g).items()}
+        stats = {"accum": g.xyz_gradient_accum.detach().cpu().numpy().copy(), "denom": g.denom.detach().cpu().numpy().copy(),
+                 "maxr": g.max_radii2D.detach().cpu().numpy().copy()}
+    return loss, grads, stats
+
+
+@pytest.mark.parametrize("D", [0, 1, 2, 3])
+def test_one_coarse_iteration_hip_vs_cpu_oracle(D):
+    """The coarse stage's counterpart of test_whole_step_gpu.py::test_one_iteration_hip_vs_cpu_oracle, at every degree the stage
+    renders at (iteration 2601: no degree change, no densification round): op by op, one node and FusedCoarseStep against
+    Trainer(stage="coarse") on the CPU oracle, at that test's per-element gates for the tiny size."""
+    ref_loss, ref_g, ref_s = _coarse_one_step("cpu", False, True, D)
+    used = (D + 1) * (D + 1) - 1            # rows of _features_rest at or below the degree
+    assert float(np.abs(ref_g["f_rest"][:, :used]).max(initial=1.0)) > 0
+    for fused, per_op in ((False, True), (False, False), (True, False)):
+        what = ("fused" if fused else "op by op" if per_op else "one node", D)
+        loss, grads, stats = _coarse_one_step("cuda", fused, per_op, D)
+        assert abs(loss - ref_loss) <= 2e-6 * max(1.0, abs(ref_loss)), (what, loss, ref_loss)
+        np.testing.assert_array_equal(stats["denom"], ref_s["denom"])
+        np.testing.assert_array_equal(stats["maxr"], ref_s["maxr"])
+        assert not grads["f_rest"][:, used:].any(), (what, "gradient above the active degree")
+        for k in PARAMS:
+            a, b = grads[k], ref_g[k]
+            assert a.shape == b.shape
+            scale = max(float(np.abs(b).max()), 1e-30)
+            err = np.abs(a - b) / scale
+            frac_loose, n_far = float((err > 1e-4).mean()), int((err > 2e-3).sum())
+            assert frac_loose <= 1e-3 and n_far == 0 and float(err.max()) <= 5e-3, (what, k, frac_loose, n_far, float(err.max()))
+        acc_scale = max(float(np.abs(ref_s["accum"]).max()), 1e-30)
+        e = np.abs(stats["accum"] - ref_s["accum"]) / acc_scale
+        assert float((e > 1e-4).mean()) <= 1e-3 and float(e.max()) <= 2e-3, (what, float(e.max()))
+
+
+def _across_the_degree_change(fused):
+    """Iterations 998-1002 from degree 0: iteration 1000 raises the degree to 1 before it renders.  densify_from_iter is moved past
+    the window so that P stays fixed while the statistics (who was seen) still accumulate."""
+    scene, g, trainer = _coarse_state(TINY, fused=fused, per_op=not fused, densify_from_iter=2000)
+    g.active_sh_degree = 0
+    P = g._xyz.shape[0]
+    losses, rest, denom = [], {}, {}
+    for i, it in enumerate(range(998, 1003)):
+        losses.append(float(trainer.step(it, cams=[trainer.cams[(3 * i + 1) % len(trainer.cams)]])))
+        if it in (999, 1002):
+            trainer.drain()
+            torch.cuda.synchronize()
+            rest[it] = g.optimizer.state[g._features_rest]["exp_avg"].detach().cpu().numpy().copy()
+            denom[it] = g.denom.detach().cpu().numpy().reshape(-1).copy()
+    assert g.active_sh_degree == 1 and g._xyz.shape[0] == P
+    moments = {k: g.optimizer.state[p]["exp_avg"].detach().cpu().numpy().copy() for k, p in _params(g).items()}
+    lr_max = max(grp["lr"] for grp in g.optimizer.param_groups)
+    return losses, _snap(g), moments, rest, denom[1002] - denom[999] > 0, lr_max
+
+
+def test_fused_coarse_step_across_the_sh_degree_change():
+    la, pa, ma, ra, seen, lr = _across_the_degree_change(False)
+    lf, pf, mf, rf, seen_f, _ = _across_the_degree_change(True)
+    np.testing.assert_array_equal(seen_f, seen)
+    np.testing.assert_allclose(lf, la, rtol=2e-5)
+    _close_params(pa, pf, 5, lr)
+    for name, (r, m) in (("op by op", (ra, ma)), ("fused", (rf, mf))):
+        assert not r[999].any(), (name, "_features_rest moved at degree 0")
+        rows = np.abs(r[1002][:, :3]).reshape(len(seen), -1).max(axis=1) > 0
+        assert not r[1002][:, 3:].any(), (name, "rows above degree 1 moved")
+        # degree-1 rows: moved only for Gaussians the frames 1000-1002 saw, and for most of those (a Gaussian that is seen but whose
+        # every channel is clamped, or that reaches no pixel at 1/255, gets none)
+        assert not rows[~seen].any() and rows[seen].mean() >= 0.5, (name, int(rows[~seen].sum()), float(rows[seen].mean()))
 
 
 # ------------------------------------------------------------------------------------------------ densify boundary, overflow replay

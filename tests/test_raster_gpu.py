@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from oracle import raster_oracle as ro
-from scenes import camera, random_gaussians
+from scenes import camera, clamp_some_channels, random_gaussians
 
 pytestmark = pytest.mark.gpu
 
@@ -23,6 +23,14 @@ IMG_MAX_TOL = 2e-2
 MAX_EXC_FRAC = 1e-4    # at most this fraction of the pixels / Gaussian rows (and never fewer than 2 allowed) may be exceptions
 GRAD_REL_TOL = 5e-5
 ROW_TOL, ROW_MAX = 2e-5, 5e-3
+# The SH backward against float64 (hip_helpers.sh_backward_fp64) on the kernel's own dL_dcolors and clamp flags: per-Gaussian
+# arithmetic with no threshold in it, so every element is held, relative to the largest element of its Gaussian's row, with no
+# exceptions.  Coefficient gradients: measured 3.4e-7 on an MI355X (fp32 direction and basis against fp64).  The view-direction
+# term of dL/d mean3D, taken as the difference from a projection backward at degree 0 on the same record (test_sh_layouts_gpu):
+# measured within 2.1e-7 of the row's whole dL/d mean3D, the scale at which the two fp32 sums it is the difference of round (the
+# term itself is a median 1.3 % (degree 1) to 5.4 % (degree 3) of that scale); DIR_TOL leaves room for the term's own fp32 arithmetic.
+SH_EXACT_TOL = 1e-6
+DIR_TOL, DIR_SUM_TOL = 1e-5, 1e-6
 
 
 def _allowed(n):
@@ -70,6 +78,23 @@ def _oracle(s, **kw):
     args.update(kw)
     return ro.forward(s["means3D"], s["opacities"], s["viewmatrix"], s["projmatrix"], s["campos"], s["W"], s["H"],
                       s["tanfovx"], s["tanfovy"], s["bg"], **args)
+
+
+def _check_sh_fp64(D, dsh, shs, means3D, campos, dcolors, clamped, radii, what=""):
+    """dL_dsh [P, M, 3] of a kernel: Y_k(dir) dRGB in float64 on every visible Gaussian, exactly zero above the active degree and
+    on every Gaussian with radius 0.  Returns the float64 view-direction term of dL/d mean3D of the visible ones."""
+    from hip_helpers import sh_backward_fp64
+    vis = radii > 0
+    assert vis.any(), what
+    want, ddir = sh_backward_fp64(D, shs[vis], means3D[vis], campos, dcolors[vis], clamped[vis])
+    got = dsh[vis].astype(np.float64)
+    row = np.abs(want).reshape(len(want), -1).max(axis=1)
+    err = np.abs(got - want).reshape(len(want), -1).max(axis=1)
+    assert (err <= SH_EXACT_TOL * row).all(), (what, D, float((err / np.maximum(row, 1e-30)).max()), int((err > SH_EXACT_TOL * row).sum()))
+    used = (D + 1) * (D + 1)
+    assert not np.any(dsh[:, used:]), (what, D, "gradient above the active degree")
+    assert not np.any(dsh[~vis]), (what, D, "gradient on a Gaussian with radius 0")
+    return ddir
 
 
 def _last_contributor(n_contrib, ranges, point_list, W, H):
@@ -298,12 +323,18 @@ def test_backward_parity(seed, P, W, H, kw):
     st = _oracle(s)
     g = hip_backward(fw, dcol, ddep)
     go = ro.backward(st, dcol, ddep)
-    for name in ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales",
-                 "dL_drotations"):
+    _cmp_grads(g, go, st)
+
+
+GRAD_NAMES = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations")
+
+
+def _cmp_grads(g, go, st, names=GRAD_NAMES, what=""):
+    for name in names:
         a, b = g[name], go[name].reshape(g[name].shape)
-        assert _relerr(a, b) <= GRAD_REL_TOL, (name, _relerr(a, b))
+        assert _relerr(a, b) <= GRAD_REL_TOL, (what, name, _relerr(a, b))
         inv = st.radii == 0
-        assert np.abs(a[inv]).max(initial=0.0) == 0.0, name
+        assert np.abs(a[inv]).max(initial=0.0) == 0.0, (what, name)
         # per GAUSSIAN, not only as a whole-tensor norm (a norm hides a few badly wrong rows): the worst element of a row,
         # relative to the tensor's largest element, is within ROW_TOL on all rows but a counted handful (_allowed) and within
         # ROW_MAX on those -- Gaussians with a (pixel, splat) pair whose alpha sits within an ulp of the 1/255 or 0.99
@@ -311,7 +342,87 @@ def test_backward_parity(seed, P, W, H, kw):
         scale = max(float(np.abs(b).max()), 1e-30)
         row_err = np.abs(a - b).reshape(a.shape[0], -1).max(axis=1) / scale
         n_bad = int((row_err > ROW_TOL).sum())
-        assert n_bad <= _allowed(a.shape[0]) and float(row_err.max()) <= ROW_MAX, (name, n_bad, float(row_err.max()))
+        assert n_bad <= _allowed(a.shape[0]) and float(row_err.max()) <= ROW_MAX, (what, name, n_bad, float(row_err.max()))
+
+
+def _backward_case(s, seed, hip_kw, oracle_kw, names=GRAD_NAMES, feat=None):
+    """Forward and backward through the `_C` drop-in against the oracle on the same inputs, a random image gradient and a nonzero
+    depth gradient: the forward at _cmp_forward's gates, the gradients `names` at test_backward_parity's."""
+    from hip_helpers import hip_backward, hip_forward
+    P, W, H = s["means3D"].shape[0], s["W"], s["H"]
+    rng = np.random.default_rng(seed)
+    dcol = rng.normal(size=(3, H, W)).astype(np.float32)
+    ddep = (rng.normal(size=(1, H, W)) * 0.2).astype(np.float32)
+    fw = hip_forward(s, **hip_kw)
+    st = _oracle(s, **oracle_kw)
+    _cmp_forward(fw, st, P, feat=feat)
+    g = hip_backward(fw, dcol, ddep)
+    go = ro.backward(st, dcol, ddep)
+    _cmp_grads(g, go, st, names, what=str(hip_kw.keys()))
+    return fw, st, g, go
+
+
+@pytest.mark.parametrize("scale_modifier", [1.0, 0.7])
+@pytest.mark.parametrize("deg", [0, 1, 2])
+def test_backward_parity_lower_sh_degree_and_scale_modifier(deg, scale_modifier):
+    """The degrees the coarse stage renders at (0 -> 1 -> 2 over its first 3000 iterations), all 16 coefficients random and
+    nonzero: the degree-1 / degree-2 derivatives of the view direction reach dL_dmeans3D, the coefficients above the degree get
+    exactly zero."""
+    s = random_gaussians(1500, seed=60 + deg, W=128, H=96)
+    kw = dict(sh_degree=deg, scale_modifier=scale_modifier)
+    fw, st, g, go = _backward_case(s, 60 + deg, kw, kw)
+    _check_sh_fp64(deg, g["dL_dsh"], s["shs"], s["means3D"], s["campos"], g["dL_dcolors"], fw["clamped"], fw["radii"], "deg")
+
+
+@pytest.mark.parametrize("M", [1, 4, 9])
+def test_sh_counts_below_16(M):
+    """A model with max_sh_degree < 3 hands the `_C` path shs of shape [P, M, 3], M = (max_sh_degree + 1)^2, rendered at that degree."""
+    D = int(round(M ** 0.5)) - 1
+    s = random_gaussians(1500, seed=70 + M, W=112, H=80)
+    s["shs"] = np.ascontiguousarray(s["shs"][:, :M])
+    fw, st, g, go = _backward_case(s, 70 + M, dict(sh_degree=D), dict(sh_degree=D))
+    assert g["dL_dsh"].shape == (1500, M, 3)
+    _check_sh_fp64(D, g["dL_dsh"], s["shs"], s["means3D"], s["campos"], g["dL_dcolors"], fw["clamped"], fw["radii"], "M")
+
+
+def test_backward_parity_precomputed_colors():
+    s = random_gaussians(1200, seed=80, W=96, H=64)
+    cols = np.random.default_rng(80).uniform(0, 1, (1200, 3)).astype(np.float32)
+    names = tuple(n for n in GRAD_NAMES if n != "dL_dsh")
+    fw, st, g, go = _backward_case(s, 80, dict(colors_precomp=cols), dict(shs=None, colors_precomp=cols), names, feat=cols)
+    assert float(np.abs(g["dL_dcolors"]).max()) > 0
+    assert g["dL_dsh"].size == 0 or not g["dL_dsh"].any()
+
+
+@pytest.mark.parametrize("deg", [1, 3])
+def test_backward_parity_precomputed_cov3d(deg):
+    s = random_gaussians(1200, seed=81 + deg, W=96, H=64)
+    cov = _oracle(s).cov3D
+    names = tuple(n for n in GRAD_NAMES if n not in ("dL_dscales", "dL_drotations"))
+    fw, st, g, go = _backward_case(s, 81 + deg, dict(cov3D_precomp=cov, sh_degree=deg),
+                                   dict(scales=None, rotations=None, cov3D_precomp=cov, sh_degree=deg), names)
+    assert float(np.abs(g["dL_dcov3D"]).max()) > 0
+    for n in ("dL_dscales", "dL_drotations"):
+        assert g[n].size == 0 or not g[n].any(), n
+    _check_sh_fp64(deg, g["dL_dsh"], s["shs"], s["means3D"], s["campos"], g["dL_dcolors"], fw["clamped"], fw["radii"], "cov3D")
+
+
+@pytest.mark.parametrize("deg", [0, 1, 2, 3])
+def test_backward_parity_with_clamped_colour_channels(deg):
+    """Strongly negative DC terms in one channel of ~30 % of the Gaussians: that channel's colour clamps at 0 and the backward
+    must drop its colour gradient on the way to the SH coefficients and the view direction (dRGB masked per channel)."""
+    s = clamp_some_channels(random_gaussians(2000, seed=90 + deg, W=128, H=96), seed=90 + deg)
+    kw = dict(sh_degree=deg)
+    fw, st, g, go = _backward_case(s, 90 + deg, kw, kw)
+    vis = st.radii > 0
+    cl = st.clamped[vis].astype(bool)
+    assert 0.05 * vis.sum() <= cl.any(axis=1).sum() < vis.sum(), (int(cl.any(axis=1).sum()), int(vis.sum()))
+    # the mask matters only where the colour gradient is nonzero: many clamped channels of Gaussians that reach pixels
+    dcol = g["dL_dcolors"][vis]
+    assert int((cl & (dcol != 0)).sum()) >= 50, int((cl & (dcol != 0)).sum())
+    dsh = g["dL_dsh"][vis]
+    assert not np.any(np.where(cl[:, None, :], dsh, 0.0)), "a clamped channel received an SH gradient"
+    _check_sh_fp64(deg, g["dL_dsh"], s["shs"], s["means3D"], s["campos"], g["dL_dcolors"], fw["clamped"], fw["radii"], "clamped")
 
 
 def test_dropin_autograd_matches_oracle():

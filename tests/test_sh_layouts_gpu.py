@@ -1,0 +1,197 @@
+"""The rasterizer at the C ABI in the layouts the training paths use (ops.raster_args / ops.raster_grads, as the fused steps build
+them): DC and higher-order SH coefficients read through two pointers, at every SH degree, with the raw or the activated
+scale / rotation / opacity, and with the higher-order rows staged in LDS or read in place -- against the oracle on the activated
+inputs, against a float64 statement of the SH backward, and against each other."""
+import ctypes as C
+import importlib
+import math
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import raster_oracle as ro
+from scenes import clamp_some_channels, random_gaussians
+from test_raster_gpu import DIR_SUM_TOL, DIR_TOL, _check_sh_fp64, _cmp_forward, _cmp_grads
+
+pytestmark = pytest.mark.gpu
+
+# where the higher-order rows (and their gradient) sit: both 16-byte aligned (the launchers stage them in LDS), the coefficient rows
+# at a 4-byte offset inside a larger buffer (forward and backward read them in place), or only the gradient rows at that offset
+# (the forward stages, the backward does not)
+LAYOUTS = ("staged", "rest_unaligned", "grad_unaligned")
+GUARD = 64          # floats of NaN on either side of the higher-order rows / their gradient: the kernels must not touch them
+
+
+def _mods():
+    return importlib.import_module("iclr2025_3d-mom_amd._native"), importlib.import_module("iclr2025_3d-mom_amd.ops")
+
+
+def _scene(P, seed):
+    """Seeded Gaussians (some with a clamped channel) as raw parameters (log scale, an unnormalised quaternion, logit opacity)
+    and as the activations mom_activations_forward makes of them -- the bits the raw projection computes in registers."""
+    N, _ = _mods()
+    s = random_gaussians(P, seed=seed, W=160, H=96)
+    if P < 50:      # random_gaussians puts its first max(1, P // 50) Gaussians behind the camera: keep a lone one in view
+        s["means3D"][:] = np.array([0.05, -0.04, 2.0], np.float32)
+        s["scales"][:] = np.array([0.03, 0.015, 0.05], np.float32)      # anisotropic: its rotation gradient is not rounding noise
+    clamp_some_channels(s, seed=seed)
+    rng = np.random.default_rng(seed + 1)
+    raw = {"scales": np.log(s["scales"]).astype(np.float32),
+           "rotations": (s["rotations"] * rng.uniform(0.5, 2.0, (P, 1))).astype(np.float32),
+           "opacities": np.log(s["opacities"] / (1 - s["opacities"])).astype(np.float32)}
+    dev = dict(dtype=torch.float32, device="cuda")
+    r = {k: torch.as_tensor(v, device="cuda") for k, v in raw.items()}
+    sc, rot, op = torch.empty(P, 3, **dev), torch.empty(P, 4, **dev), torch.empty(P, 1, **dev)
+    lib = N.lib()
+    N.check(lib.mom_activations_forward(P, r["scales"].data_ptr(), r["rotations"].data_ptr(), r["opacities"].data_ptr(),
+                                        sc.data_ptr(), rot.data_ptr(), op.data_ptr(), N.current_stream()), "act")
+    torch.cuda.synchronize()
+    act = dict(s, scales=sc.cpu().numpy(), rotations=rot.cpu().numpy(), opacities=op.cpu().numpy())
+    rng = np.random.default_rng(seed + 2)
+    W, H = s["W"], s["H"]
+    dcol = rng.normal(size=(3, H, W)).astype(np.float32)
+    ddep = (rng.normal(size=(1, H, W)) * 0.2).astype(np.float32)
+    return act, raw, dcol, ddep
+
+
+def _in_guarded(n, dev, offset):
+    """A view of n floats inside a NaN-filled buffer, 16-byte aligned plus `offset` floats, with GUARD floats around it."""
+    buf = torch.full((n + 2 * GUARD + 8,), float("nan"), dtype=torch.float32, device=dev)
+    base = GUARD + ((-(buf.data_ptr() + 4 * GUARD)) % 16) // 4 + offset
+    return buf, buf[base:base + n], base
+
+
+def _frames(s, raw, dcol, ddep, D, params_raw):
+    """Every layout through the C ABI: its own forward, then the projection backward on ONE compositing backward's record (that
+    of the staged forward -- its float atomics make the compositing backward's sums differ from run to run in the last bit), and
+    the projection backward again at degree 0 on the same record, whose dL/d mean3D lacks exactly the view-direction term.  Every
+    gradient buffer starts as NaN: a row the kernels do not write shows.  Returns {layout: (forward state, gradients, dL/d mean3D
+    at degree 0)}."""
+    from hip_helpers import decode_state
+    N, ops = _mods()
+    lib, stream = N.lib(), N.current_stream()
+    dev = "cuda"
+    P, W, H = s["means3D"].shape[0], s["W"], s["H"]
+    tt = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device=dev)
+    means, bg, view, proj, campos = tt(s["means3D"]), tt(s["bg"]), tt(s["viewmatrix"]), tt(s["projmatrix"]), tt(s["campos"])
+    f_dc = tt(s["shs"][:, :1])
+    src = raw if params_raw else s
+    sc, rot, op = tt(src["scales"]), tt(src["rotations"]), tt(src["opacities"])
+    cam = types.SimpleNamespace(image_width=W, image_height=H, FoVx=2 * math.atan(s["tanfovx"]), FoVy=2 * math.atan(s["tanfovy"]))
+    fwd = {}
+    for lay in LAYOUTS:
+        rest_buf, f_rest, _ = _in_guarded(P * 45, dev, 1 if lay == "rest_unaligned" else 0)
+        f_rest.copy_(tt(s["shs"][:, 1:]).view(-1))
+        a = ops.raster_args(cam, view, proj, campos, bg, P, D, means, f_dc, f_rest, op, sc, rot, params_raw, 1.0, False, False)
+        a.tan_fovx, a.tan_fovy = s["tanfovx"], s["tanfovy"]      # the oracle's float values, not a round trip through the FoV
+        geom = torch.empty(lib.mom_raster_geom_bytes(P), dtype=torch.uint8, device=dev)
+        img = torch.empty(lib.mom_raster_image_bytes(W, H), dtype=torch.uint8, device=dev)
+        radii = torch.empty(P, dtype=torch.int32, device=dev)
+        nr_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        nr_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        N.check(lib.mom_raster_forward_geometry(C.byref(a), geom.data_ptr(), img.data_ptr(), radii.data_ptr(), nr_dev.data_ptr(),
+                                                nr_host.data_ptr(), stream), "geometry")
+        torch.cuda.synchronize()
+        R = int(nr_host[0])
+        binning = torch.empty(lib.mom_raster_binning_bytes(P, W, H, R), dtype=torch.uint8, device=dev)
+        color, depth = torch.empty(3, H, W, device=dev), torch.empty(1, H, W, device=dev)
+        N.check(lib.mom_raster_forward_render(C.byref(a), geom.data_ptr(), binning.data_ptr(), R, img.data_ptr(), color.data_ptr(),
+                                              depth.data_ptr(), None, stream), "render")
+        torch.cuda.synchronize()
+        fw = dict(R=R, color=color.cpu().numpy(), depth=depth.cpu().numpy(), radii=radii.cpu().numpy(), keep_all_tiles=False)
+        fw.update(decode_state(P, W, H, R, geom, binning, img))
+        fwd[lay] = (a, fw, rest_buf, (geom, binning, img, radii, R))
+    a, _, _, (geom, binning, img, radii, R) = fwd["staged"]
+    dc, dd = tt(dcol), tt(ddep)
+    N.check(lib.mom_raster_backward_render(C.byref(a), geom.data_ptr(), binning.data_ptr(), R, img.data_ptr(), dc.data_ptr(),
+                                           dd.data_ptr(), stream), "backward_render")
+
+    def grads(a, lay, deg):
+        nan = dict(dtype=torch.float32, device=dev)
+        out = {k: torch.full(shp, float("nan"), **nan) for k, shp in (
+            ("dL_dmeans2D", (P, 3)), ("dL_dcolors", (P, 3)), ("dL_dopacity", (P, 1)), ("dL_dmeans3D", (P, 3)),
+            ("dL_dcov3D", (P, 6)), ("dc", (P, 1, 3)), ("dL_dscales", (P, 3)), ("dL_drotations", (P, 4)))}
+        gbuf, grest, base = _in_guarded(P * 45, dev, 1 if lay == "grad_unaligned" else 0)
+        gr = ops.raster_grads(out["dL_dmeans2D"], out["dL_dcolors"], out["dL_dopacity"], out["dL_dmeans3D"], out["dL_dcov3D"],
+                              out["dc"], grest, out["dL_dscales"], out["dL_drotations"])
+        a.D = deg
+        N.check(lib.mom_raster_backward_geometry(C.byref(a), radii.data_ptr(), geom.data_ptr(), C.byref(gr), stream), "bwd_geometry")
+        a.D = D
+        torch.cuda.synchronize()
+        g = {k: v.cpu().numpy() for k, v in out.items() if k != "dc"}
+        g["dL_dsh"] = np.concatenate([out["dc"].cpu().numpy(), grest.view(P, 15, 3).cpu().numpy()], axis=1)
+        gb = gbuf.cpu().numpy()
+        assert np.isnan(gb[:base]).all() and np.isnan(gb[base + P * 45:]).all(), (lay, "a write outside the gradient rows")
+        return g
+
+    runs = {}
+    for lay, (a, fw, rest_buf, _) in fwd.items():
+        g = grads(a, lay, D)
+        dmean0 = grads(a, lay, 0)["dL_dmeans3D"]
+        rb = rest_buf.cpu().numpy()
+        assert np.array_equal(rb[~np.isnan(rb)], s["shs"][:, 1:].reshape(-1)), (lay, "the coefficient rows were written to")
+        runs[lay] = (fw, g, dmean0)
+    return runs
+
+
+def _through_activations(go, raw):
+    """The oracle's gradients with respect to the activated scale / rotation / opacity taken back to the raw parameters through
+    exp, F.normalize and sigmoid (gaussian_renderer/__init__.py), in float64 autograd."""
+    f = dict(dtype=torch.float64)
+    out = dict(go)
+    sr = torch.tensor(raw["scales"], **f, requires_grad=True)
+    qr = torch.tensor(raw["rotations"], **f, requires_grad=True)
+    orr = torch.tensor(raw["opacities"], **f, requires_grad=True)
+    loss = ((torch.exp(sr) * torch.as_tensor(go["dL_dscales"], **f)).sum()
+            + (torch.nn.functional.normalize(qr, dim=1) * torch.as_tensor(go["dL_drotations"], **f)).sum()
+            + (torch.sigmoid(orr) * torch.as_tensor(go["dL_dopacity"], **f).reshape(-1, 1)).sum())
+    loss.backward()
+    out["dL_dscales"], out["dL_drotations"], out["dL_dopacity"] = sr.grad.numpy(), qr.grad.numpy(), orr.grad.numpy()
+    return out
+
+
+def _bits(x):
+    return np.ascontiguousarray(x).view(np.uint8)
+
+
+@pytest.mark.parametrize("P", [1, 200, 6000])
+@pytest.mark.parametrize("params_raw", [0, 1])
+@pytest.mark.parametrize("D", [0, 1, 2, 3])
+def test_training_layouts_against_the_oracle(D, params_raw, P):
+    """P = 1: one partial workgroup; 200: one partial workgroup of many; 6000: 23 whole workgroups and a partial tail."""
+    s, raw, dcol, ddep = _scene(P, seed=100 + P + D)
+    runs = _frames(s, raw, dcol, ddep, D, params_raw)
+    fw, g, dmean0 = runs["staged"]
+    assert (fw["radii"] > 0).sum() >= min(P, 50)
+    # staged and in place: the same arithmetic on the same values -- the same bits, forward and backward
+    for lay in LAYOUTS[1:]:
+        fw2, g2, d02 = runs[lay]
+        for k in ("R", "color", "depth", "radii", "means2D", "depths", "conic_opacity", "rgb", "clamped", "ranges", "point_list",
+                  "n_contrib", "final_T"):
+            assert np.array_equal(_bits(np.asarray(fw2[k])), _bits(np.asarray(fw[k]))), (lay, "forward", k)
+        for k in g:
+            assert np.array_equal(_bits(g2[k]), _bits(g[k])), (lay, "backward", k)
+        assert np.array_equal(_bits(d02), _bits(dmean0)), (lay, "backward at degree 0")
+    for k, v in g.items():
+        assert not np.isnan(v).any(), ("a gradient the kernels did not write", k)
+    # the oracle on the activated inputs (the values the raw projection computes in registers, bit for bit)
+    st = ro.forward(s["means3D"], s["opacities"], s["viewmatrix"], s["projmatrix"], s["campos"], s["W"], s["H"], s["tanfovx"],
+                    s["tanfovy"], s["bg"], shs=s["shs"], sh_degree=D, scales=s["scales"], rotations=s["rotations"])
+    _cmp_forward(fw, st, P)
+    go = ro.backward(st, dcol, ddep)
+    _cmp_grads(g, _through_activations(go, raw) if params_raw else go, st, what=("D", D, "raw", params_raw))
+    # the SH backward in float64 on the kernel's own colour gradient and clamp flags: coefficients and view-direction term
+    ddir = _check_sh_fp64(D, g["dL_dsh"], s["shs"], s["means3D"], s["campos"], g["dL_dcolors"], fw["clamped"], fw["radii"],
+                          ("layout", D, params_raw))
+    vis = fw["radii"] > 0
+    got = g["dL_dmeans3D"][vis].astype(np.float64) - dmean0[vis]
+    scale_dir = np.abs(ddir).max(axis=1, keepdims=True)
+    scale_sum = np.maximum(np.abs(g["dL_dmeans3D"][vis]), np.abs(dmean0[vis])).max(axis=1, keepdims=True)
+    err = np.abs(got - ddir)
+    assert (err <= DIR_TOL * scale_dir + DIR_SUM_TOL * scale_sum).all(), \
+        (D, float((err / np.maximum(scale_dir, 1e-30)).max()), float((err / np.maximum(scale_sum, 1e-30)).max()))
+    live = scale_sum[:, 0] > 0
+    if D > 0 and live.any():       # the term is there to be checked: not lost in the rest of dL/d mean3D
+        assert float(np.median(scale_dir[live] / scale_sum[live])) > 100 * DIR_SUM_TOL

@@ -35,15 +35,18 @@ def _tensors(g):
             "w_sc1": dn.scales_deform[1].weight, "w_rot3": dn.rotations_deform[3].weight, "b_rot3": dn.rotations_deform[3].bias}
 
 
-def _one_step(device, fused, lambda_dssim, cam_index=1, cfg=None):
-    """One fine-stage iteration from the seeded benchmark state; returns loss, every live gradient (Adam's first moment
-    after ONE step is 0.1 * gradient exactly), the statistics and the radii."""
+def _one_step(device, fused, lambda_dssim, cam_index=1, cfg=None, sh_degree=None):
+    """One fine-stage iteration from the seeded benchmark state (rendered at `sh_degree` if given, else at the trained-like
+    state's 3); returns loss, every live gradient (Adam's first moment after ONE step is 0.1 * gradient exactly), the statistics
+    and the radii."""
     import bench
     from oracle import cpu_backend
     ctx = cpu_backend.installed() if device == "cpu" else contextlib.nullcontext()
     with ctx:
         scene, g, trainer, op = bench.build_state(cfg or CFG, torch.device(device), fused=fused, lambda_dssim=lambda_dssim)
         assert (trainer.fused is not None) == fused
+        if sh_degree is not None:
+            g.active_sh_degree = sh_degree
         loss = float(trainer.step(5001, cams=[trainer.cams[cam_index]]))
         if device != "cpu":
             trainer.drain()
@@ -68,14 +71,29 @@ def test_one_iteration_hip_vs_cpu_oracle(cfg_name, lambda_dssim):
     """"tiny": 6 k Gaussians, 160x96.  "c2": BASELINE configs[1] at full size -- bench.py's own scene and model state (200 k
     Gaussians, 960x540, 60 frames, HexPlane [64, 64, 64, 50]) -- one whole iteration (field, rasterizer, loss, backward,
     statistics, Adam) on the HIP paths against the CPU oracle Trainer running on 16 threads (VERDICT r3 missing 3)."""
+    _against_the_oracle(cfg_name, lambda_dssim)
+
+
+@pytest.mark.parametrize("sh_degree", [1, 2])
+def test_one_iteration_hip_vs_cpu_oracle_at_lower_sh_degree(sh_degree):
+    """The same iteration rendered at degree 1 and 2 (every coefficient of the trained-like state nonzero), fused and autograd."""
+    _against_the_oracle("tiny", 0.0, sh_degree)
+
+
+def _against_the_oracle(cfg_name, lambda_dssim, sh_degree=None):
     cfg = _cfg(cfg_name)
     if cfg_name != "tiny":
         from oracle import raster_oracle as ro
         ro.set_threads(16)
         torch.set_num_threads(min(16, os.cpu_count() or 1))
-    ref_loss, ref_g, ref_s, _ = _one_step("cpu", False, lambda_dssim, cfg=cfg)
+    ref_loss, ref_g, ref_s, _ = _one_step("cpu", False, lambda_dssim, cfg=cfg, sh_degree=sh_degree)
+    if sh_degree is not None:
+        used = (sh_degree + 1) ** 2 - 1
+        assert float(np.abs(ref_g["f_rest"][:, :used]).max()) > 0 and not ref_g["f_rest"][:, used:].any()
     for fused in (False, True):
-        loss, grads, stats, dead = _one_step("cuda", fused, lambda_dssim, cfg=cfg)
+        loss, grads, stats, dead = _one_step("cuda", fused, lambda_dssim, cfg=cfg, sh_degree=sh_degree)
+        if sh_degree is not None:
+            assert not grads["f_rest"][:, (sh_degree + 1) ** 2 - 1:].any(), (fused, "gradient above the active degree")
         assert not dead, ("dead heads received a gradient", dead)
         assert abs(loss - ref_loss) <= 2e-6 * max(1.0, abs(ref_loss)), (fused, loss, ref_loss)
         # statistics: visibility (radius > 0) is integer work and must agree exactly; the accumulated gradient norm is float
