@@ -1,5 +1,5 @@
 // The exact three-way bf16 split of fp32 operands for v_mfma_f32_32x32x16_bf16 (see deform_field.hip for the scheme): shared by
-// the fused forward (pre-split weight fragments in LDS) and the MLP backward (weights split on the fly from their fp32 copy).
+// the fused forward (deform_field.hip) and the one-kernel MLP backward (deform_bwd_b3.hip), both with pre-split weight fragments.
 #pragma once
 #include "deform_mlp_dev.h"
 
@@ -85,36 +85,6 @@ __device__ __forceinline__ f32x16 mfma16(uint4 a, uint4 b, f32x16 c)
     return c;
 #endif
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// acc[mt] += W x (TRANS: W^T x) with the weights read from their fp32 copy in LDS (Wl[in * kWStride + out]) and split on the
-// fly: the A operand of K-step s is the eight weights whose contraction index is 16 s + 4 h + (j & 3) + 8 (j >> 2), j = 0..7 --
-// the order in which an accumulator tile holds its features, so that B is a predecessor's accumulator, split in place.
-template <bool TRANS>
-__device__ __forceinline__ void layer_b3_otf(const float* __restrict__ Wl, const Frag3 (&B)[4], f32x16 (&acc)[2], int col, int h)
-{
-#pragma unroll
-    for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-        for (int s = 0; s < 4; s++) {
-            float v[8];
-            const int m = 32 * mt + col;
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const int kk = 16 * s + 4 * h + (j & 3) + 8 * (j >> 2);
-                v[j] = TRANS ? Wl[m * kWStride + kk] : Wl[kk * kWStride + m];
-            }
-            const Frag3 A = split8(v);
-            f32x16 c = acc[mt];
-            c = mfma16(A.p[2], B[s].p[0], c);
-            c = mfma16(A.p[0], B[s].p[2], c);
-            c = mfma16(A.p[1], B[s].p[1], c);
-            c = mfma16(A.p[1], B[s].p[0], c);
-            c = mfma16(A.p[0], B[s].p[1], c);
-            c = mfma16(A.p[0], B[s].p[0], c);
-            acc[mt] = c;
-            __builtin_amdgcn_sched_barrier(0);
-        }
 }
 
 }  // namespace

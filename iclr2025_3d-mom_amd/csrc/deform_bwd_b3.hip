@@ -8,8 +8,9 @@
 //   two kernels (rounds 1-3):  dx writes dH [4][P][64] and dfeat (256 MB at 200 k Gaussians), dW reads dH, a0 three times and feat
 //                              (309 MB) on a second stream BESIDE the HexPlane backward, which it slows from 83 + 81 us to
 //                              116 + 139 us: that stretch of the step is bound by memory bandwidth;
-//   round 3's one-kernel f32 form: no dH traffic, but all 640 v_mfma_f32_32x32x2_f32 of a tile on one wave's critical path,
-//                              and that instruction blocks the SIMD's vector ALU: 266 us against 183;
+//   round 3's one-kernel f32 form (removed; docs/DESIGN_rounds_1_to_3.md): no dH traffic, but all 640 v_mfma_f32_32x32x2_f32
+//                              of a tile were on one wave's critical path, and that instruction blocks the SIMD's vector ALU:
+//                              266 us against 183;
 //   here:  the fp32-exact three-way bf16 split of deform_field.hip's forward (six v_mfma_f32_32x32x16_bf16 per product block,
 //          0.375 of the f32 matrix cycles, vector ALU free meanwhile) and FOUR ROLES, each cut in two by deform_bwd_b3g_kernel
 //          further down (the roles as such:
@@ -18,8 +19,9 @@
 //            wave 3, "trunk":      dH0 = relu'(a0) (dA0_0 + dA0_1 + dA0_2), dfeat = W0^T dH0, dW0 += dH0^T feat, db0.)
 //          A role needs TWO weight-fragment sets, not seven: a head wave keeps W1_k's forward fragments (96 registers) for its
 //          whole share of the Gaussians and reads W1_k^T's from LDS (3 x 24 KB, pre-split once per workgroup); the trunk wave
-//          keeps W0^T's in registers.  Nothing is split per tile except activations.  (The per-tile, on-the-fly split of the
-//          weights is what held deform_bwd_dx_kernel<B3> to 116 us: 3360 of its ~4500 vector instructions per tile.)
+//          keeps W0^T's in registers.  Nothing is split per tile except activations.  (A per-tile, on-the-fly split of the
+//          weights is what held round 5's bf16 variant of deform_bwd_dx_kernel, since removed, to 116 us: 3360 of its ~4500
+//          vector instructions per tile.)
 //          A wave holds ONE 64x64 weight-gradient tile in accumulators (64 registers) -- the one-wave-does-everything form
 //          needed four (256) and could not keep them.
 //
@@ -28,12 +30,11 @@
 // ten output gradients, dfeat: ~155 MB at 200 k Gaussians against ~640 MB.
 //
 // Numerics: every product is the six-term bf16 expansion of deform_b3_dev.h (terms below 2^-23 |x||y| dropped), accumulated in
-// fp32 by the MFMA: the same arithmetic as the forward kernel and as deform_bwd_dx_kernel<B3>; against the f32-MFMA kernels the
+// fp32 by the MFMA: the same arithmetic as the forward kernel; against the f32-MFMA kernels the
 // results differ by summation order (tests/test_ops_gpu.py: dfeat to 2e-5 of scale, weight gradients to 2e-5 of scale).
 // (-DMOM_SPLIT_RNE: the operand split by v_cvt_pk_bf16_f32 instead of masks, deform_b3_dev.h -- 11 instead of ~13.5 vector
 // instructions per pair of values.  Measured 185 against 182 us: no gain, so the masks stay, the same arithmetic as the forward.)
 #include "deform_b3_dev.h"
-#include <stdlib.h>
 #include <mutex>
 
 namespace {
@@ -509,8 +510,7 @@ int mom_launch_deform_bwd_b3f(const MomDeformMLP* w, int P, const float* feat, c
     // 256 / 240 / 232 / 224 / 216 / 208 workgroups: config 2 1047 / 1040 / 1035 / 1061 / 1057 / 1054, config 3 285 / 282 / 280 /
     // 291 / 289 / 287, config 5 91.1 / - / - / 93.1 (a workgroup's tile count steps from 25 to 27 at 240 and to 28 at 224: 240 pays
     // for too few free CUs).  MOM_B3F_BLOCKS overrides.
-    static int forced_blocks = -1;
-    if (forced_blocks < 0) { const char* e = getenv("MOM_B3F_BLOCKS"); forced_blocks = (e && atoi(e) > 0 && atoi(e) <= 256) ? atoi(e) : 0; }
+    static const int forced_blocks = mom_env_int("MOM_B3F_BLOCKS", 0, 1, 256);
     const int max_blocks = forced_blocks ? forced_blocks : (dw_stream != s ? 224 : 256);
     const int blocks = tiles < max_blocks ? tiles : max_blocks;
     int dev_id = 0;
@@ -534,8 +534,7 @@ int mom_launch_deform_bwd_b3f(const MomDeformMLP* w, int P, const float* feat, c
     // The sum over the workgroups' partials is all that is left of "the weight gradients are complete on dw_stream": it goes to the
     // caller's second stream, behind an event.  On `stream` it sat between the MLP backward and the HexPlane backward and, in the
     // training step, shared HBM with the early Adam launch: 46 us on the critical path for a kernel that takes 6 alone.
-    static int reduce_on_main = -1;      // MOM_B3F_REDUCE_MAIN=1: keep the reduction on `stream` (measurement)
-    if (reduce_on_main < 0) { const char* e = getenv("MOM_B3F_REDUCE_MAIN"); reduce_on_main = (e && e[0] == '1') ? 1 : 0; }
+    static const int reduce_on_main = mom_env_int("MOM_B3F_REDUCE_MAIN", 0, 0, 1);      // 1: keep the reduction on `stream` (measurement)
     if (reduce_on_main) dw_stream = s;
     if (dw_stream != s) {
         // one event per call: record + wait capture the state at the record, and hipEventDestroy of a recorded event is deferred

@@ -4,8 +4,8 @@
 // points (reference scene/deformation.py:97-153 calling scene/hexplane.py:73-106,160-183: 12 x F.grid_sample + product,
 // then the 7 nn.Linear of the trunk and the pos / scales / rotations heads).  The separate kernels (hexplane.hip,
 // deform_mlp.hip) pass feat[P,64] through HBM and are bound by vector-instruction issue (HexPlane) and by the phases around
-// the MFMAs (MLP); here a wave gathers the features of its 32 Gaussians straight into the MFMA's B-operand tile in LDS, and
-// while it runs its 256 MFMAs the SIMD's other wave gathers.
+// the MFMAs (MLP); here a wave gathers the features of its 32 Gaussians and runs their MLP on the bf16 matrix pipe, whose
+// MFMAs co-issue with the gathers of the SIMD's other waves (deform_field_fwd_b3_kernel).
 //
 // Two things make the gather cheap enough to hide:
 //  * One timestamp per frame collapses the three space-time planes to LINES: the bilinear sample of plane (x,t) at (x, t) is
@@ -27,26 +27,10 @@
 #include "deform_mlp_dev.h"
 #include "hexplane_dev.h"
 #include "deform_b3_dev.h"
-#include <stdlib.h>
 
 namespace {
 
-constexpr int kTileStride = 68;                      // B-operand tile rows: [32 gaussians][64 features + 4]: 16-byte aligned, conflict-free
-constexpr int kTileFloats = 32 * kTileStride;
 constexpr int kRecDw = 8;                            // dwords of one (point, level) record
-constexpr int kBufFloats = kTileFloats + 64 * kRecDw;   // one gather wave's buffer: the tile + its records
-#define MOM_FIELD_PRIO 2
-#define MOM_FIELD_NG 2
-#define MOM_FIELD_NM 1
-constexpr int kNG = MOM_FIELD_NG;                    // gather waves per SIMD
-constexpr int kNM = MOM_FIELD_NM;                    // MFMA waves per SIMD: they take the SIMD's tiles in turn
-constexpr int kMfmaGroup = (kNM + kNG) >= 4 ? 8 : 16;   // A-fragment prefetch depth (registers)
-constexpr int kNB = kNG > kNM ? kNG : kNM;           // tile buffers per SIMD
-constexpr int kFieldWaves = 4 * (kNM + kNG);
-constexpr int kLFlags = kLFwdTotal;                  // [4 SIMDs][kNG][2] ints: tiles published / tiles consumed
-constexpr int kLBufs = kLFlags + 32;
-constexpr int kLFieldTotal = kLBufs + 4 * kNB * kBufFloats;
-
 
 // lines[level][axis][r][32] = ay * plane_(axis,t)[t0][r][:] + by * plane_(axis,t)[t1][r][:]
 __global__ void __launch_bounds__(256) hexplane_lines_kernel(HexArgs a, LineTab lt, float* __restrict__ lines, int total)
@@ -68,50 +52,6 @@ __global__ void __launch_bounds__(256) hexplane_lines_kernel(HexArgs a, LineTab 
     if (t0 >= 0) v += pl[(size_t)t0 * Wd * 32 + rel] * w0;
     if (t1 >= 0) v += pl[(size_t)t1 * Wd * 32 + rel] * w1;
     lines[i] = v;
-}
-
-struct WeightRegs {
-    float4 v[16];
-    float bias;
-};
-// load_weights of deform_mlp_dev.h in two halves, so that the gather of a wave's first tile runs while the 70 KB of weights
-// are in flight (256 CUs pull the same lines out of L2 at once: 16 k cycles when waited for on the spot)
-__device__ __forceinline__ void weights_issue(const MlpDev& m, WeightRegs& w, int tid, int nth)
-{
-    const float* Ws[4] = {m.W0, m.W1[0], m.W1[1], m.W1[2]};
-    const float* bs[4] = {m.b0, m.b1[0], m.b1[1], m.b1[2]};
-    constexpr int kQuads = 4 * kHid * kHid / 4;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const int q = tid + j * nth;
-        if (q < kQuads) w.v[j] = reinterpret_cast<const float4*>(Ws[q >> 10])[q & 1023];
-    }
-    w.bias = 0.f;
-    if (tid < 4 * kHid) w.bias = bs[tid >> 6][tid & 63];
-}
-__device__ __forceinline__ void weights_commit(const MlpDev& m, const WeightRegs& w, float* __restrict__ lds, int tid, int nth)
-{
-    constexpr int kQuads = 4 * kHid * kHid / 4;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const int q = tid + j * nth;
-        if (q < kQuads) {
-            const int L = q >> 10, i = 4 * (q & 1023), o = i >> 6, k = i & 63;
-            float* d = lds + kLW + L * kWFloats + k * kWStride + o;
-            d[0] = w.v[j].x; d[kWStride] = w.v[j].y; d[2 * kWStride] = w.v[j].z; d[3 * kWStride] = w.v[j].w;
-        }
-    }
-    if (tid < 4 * kHid) lds[kLB + tid] = w.bias;
-    for (int i = tid; i < 3 * 4 * kHid; i += nth) {
-        const int head = i >> 8, n = (i >> 6) & 3, f = i & 63;
-        const int nout = head == 2 ? 4 : 3;
-        lds[kLW2 + i] = n < nout ? m.W2[head][n * kHid + f] : 0.f;
-    }
-    if (tid < 12) {
-        const int head = tid >> 2, n = tid & 3;
-        const int nout = head == 2 ? 4 : 3;
-        lds[kLB2 + tid] = n < nout ? m.b2[head][n] : 0.f;
-    }
 }
 
 __device__ __forceinline__ float4 ld4(const float* __restrict__ base, unsigned byte_off)
@@ -173,13 +113,12 @@ struct UnitLoads {
     int gl;
 };
 
-// Gather the 64 features of the tile's 32 Gaussians into `tile` ([gaussian][kTileStride]) and, optionally, into feat[P][64].
-// g_mine: the Gaussian of lane (lane & 31) (or -1 past the end).  Eight lanes work on one (point, level); the eight units of a
-// pass are software pipelined two deep: the loads of unit u + 2 are issued as soon as unit u's registers are free, so two
-// memory round trips are always in flight (issued one unit at a time and waited for on the spot, a tile took 34-41 k cycles).
+// Gather the 64 features of the tile's 32 Gaussians into their rows of feat[P][64].
+// g_mine: the Gaussian of lane (lane & 31) (or -1 past the end).  Eight lanes work on one (point, level), one pass of eight
+// units in flight per wave.
 __device__ __forceinline__ void gather_tile(const HexArgs& a, const LineTab& lt, const float* __restrict__ lines,
-                                            const float* __restrict__ xyz, int g_mine, float* __restrict__ tile,
-                                            uint4* __restrict__ rec, float* __restrict__ feat_save, int lane)
+                                            const float* __restrict__ xyz, int g_mine, uint4* __restrict__ rec,
+                                            float* __restrict__ feat, int lane)
 {
     // phase A: lane = unit (gaussian lane & 31, level lane >> 5)
     {
@@ -239,10 +178,9 @@ __device__ __forceinline__ void gather_tile(const HexArgs& a, const LineTab& lt,
         f = mul44(f, space(L.t + 8, ay, by, az, bz));
         f = mul44(f, fma4(L.t[15], by, mul4(L.t[14], ay)));
         f = mul44(f, fma4(L.t[17], bz, mul4(L.t[16], az)));
-        if (tile) *reinterpret_cast<float4*>(tile + L.gl * kTileStride + 32 * lvl + 4 * c) = f;
-        if (feat_save) {
+        if (feat) {      // (never null; the test is kept because the compiler schedules the kernel around it)
             const int g = __shfl(g_mine, L.gl);
-            if (g >= 0) *reinterpret_cast<float4*>(feat_save + (size_t)g * kHid + 32 * lvl + 4 * c) = f;
+            if (g >= 0) *reinterpret_cast<float4*>(feat + (size_t)g * kHid + 32 * lvl + 4 * c) = f;
         }
     };
 #pragma unroll 1
@@ -259,197 +197,12 @@ __device__ __forceinline__ void gather_tile(const HexArgs& a, const LineTab& lt,
     __builtin_amdgcn_wave_barrier();
 }
 
-// B operand of the trunk layer from the tile: register r of lane half h is feature fmap(r, h) = (r & 3) + 8 (r >> 2) + 4 h
-__device__ __forceinline__ void load_tile(const float* __restrict__ tile, int col, int h, f32x16 (&t)[2])
-{
-#pragma unroll
-    for (int kt = 0; kt < 2; kt++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const float4 v = *reinterpret_cast<const float4*>(tile + col * kTileStride + 32 * kt + 8 * q + 4 * h);
-            t[kt][4 * q + 0] = v.x;
-            t[kt][4 * q + 1] = v.y;
-            t[kt][4 * q + 2] = v.z;
-            t[kt][4 * q + 3] = v.w;
-        }
-}
-
 #ifdef MOM_FIELD_STAMPS
 __device__ unsigned long long g_field_dbg[256 * 32 * 4];
 #define STAMP() __builtin_amdgcn_s_memtime()
 #else
 #define STAMP() 0ull
 #endif
-__device__ __forceinline__ void flag_wait(const int* f, int need)
-{
-    while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < need) __builtin_amdgcn_s_sleep(1);
-}
-__device__ __forceinline__ void flag_set(int* f, int v) { __hip_atomic_store(f, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-// Waves specialise.  Waves 0..3 (one per SIMD) run the MLP of their SIMD's tiles on the matrix pipe and never wait for memory;
-// waves 4.. (kNG per SIMD) gather: each owns one tile buffer in LDS, fills it for its next tile while the MFMA wave works through
-// the previous one, and hands it over through two counters in LDS (tiles published / tiles consumed).  The MFMA wave frees a
-// buffer as soon as the tile sits in its registers, so the gather has a whole tile's MFMA time (16 k cycles) for the next one.
-// Run as ONE program per wave (gather a tile, then multiply it) the two waves of a SIMD moved in lockstep -- all gathering, then
-// all queueing for the matrix pipe -- and the kernel took the sum of the two phases (120 us); so did the two separate kernels.
-__global__ void __launch_bounds__(64 * kFieldWaves)
-deform_field_fwd_kernel(HexArgs a, LineTab lt, MlpDev m, int tiles, const float* __restrict__ lines, const float* __restrict__ xyz,
-                        const float* __restrict__ scaling, const float* __restrict__ rotation, const float* __restrict__ flow,
-                        float flow_coef, float* __restrict__ pts, float* __restrict__ scales, float* __restrict__ rots,
-                        float* __restrict__ feat_save, float* __restrict__ a0_save, ActOut act)
-{
-    extern __shared__ float lds[];
-    const int lane = threadIdx.x & 63, col = lane & 31, h = lane >> 5, wv = threadIdx.x >> 6;
-    const int P = a.P;
-    const int t_begin = (int)((long long)tiles * blockIdx.x / gridDim.x), t_end = (int)((long long)tiles * (blockIdx.x + 1) / gridDim.x);
-    int* flags = reinterpret_cast<int*>(lds + kLFlags);
-    if (threadIdx.x < 32) flags[threadIdx.x] = 0;
-    auto gaussian_of = [&](int t) {
-        const int gi = t * 32 + col;
-        return gi < P ? (a.order ? (int)a.order[gi] : gi) : -1;
-    };
-    const bool mfma_wave = wv < 4 * kNM;
-    const int simd = wv & 3, gj = mfma_wave ? wv >> 2 : (wv - 4 * kNM) >> 2;      // waves w, w + 4, w + 8 share a SIMD (speed only)
-    WeightRegs wr;
-    if (mfma_wave) weights_issue(m, wr, (int)threadIdx.x, 256 * kNM);
-    __syncthreads();                                                   // the flags are zero
-    if (!mfma_wave) {
-        // the SIMD's k-th tile (tile t_begin + simd + 4 k) goes through buffer k % kNB; gather wave gj fills k = gj, gj + kNG, ...
-        unsigned long long tw = 0, tg = 0, t00 = STAMP();
-        int n_done = 0;
-        for (int k = gj; t_begin + simd + 4 * k < t_end; k += kNG, n_done++) {
-            const int t = t_begin + simd + 4 * k, j = k % kNB, n = k / kNB;
-            float* tile = lds + kLBufs + (simd * kNB + j) * kBufFloats;
-            uint4* rec = reinterpret_cast<uint4*>(tile + kTileFloats);
-            int* f_ready = flags + (simd * kNB + j) * 2, *f_free = f_ready + 1;
-            const int g = gaussian_of(t);
-            const unsigned long long s0 = STAMP();
-            flag_wait(f_free, n);                                      // the buffer's previous tile sits in an MFMA wave's registers
-            const unsigned long long s1 = STAMP();
-            gather_tile(a, lt, lines, xyz, g, tile, rec, feat_save, lane);
-            flag_set(f_ready, n + 1);
-            const unsigned long long s2 = STAMP();
-            tw += s1 - s0; tg += s2 - s1;
-        }
-#ifdef MOM_FIELD_STAMPS
-        if (lane == 0) {
-            unsigned long long* d = g_field_dbg + ((size_t)blockIdx.x * 32 + wv) * 4;
-            d[0] = tw; d[1] = tg; d[2] = STAMP() - t00; d[3] = n_done;
-        }
-#endif
-        return;
-    }
-    __builtin_amdgcn_s_setprio(MOM_FIELD_PRIO);     // the matrix wave's few vector / LDS instructions go ahead of the gather waves' many
-    weights_commit(m, wr, lds, (int)threadIdx.x, 256 * kNM);
-    // only the four MFMA waves read the weights: a barrier among them (the gather waves never come here)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (lane == 0) __hip_atomic_fetch_add(flags + 31, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    flag_wait(flags + 31, 4 * kNM);
-    int k = 0;
-    unsigned long long tw = 0, t00 = STAMP(), tpro = 0, tl = 0, tm = 0, to = 0;
-    // MFMA wave gj of the SIMD takes the SIMD's tiles k = gj, gj + kNM, ...: while one wave is between its MFMA phases (bias,
-    // ReLU, output layers, stores) the other's MFMAs keep the pipe busy
-    for (k = gj; t_begin + simd + 4 * k < t_end; k += kNM) {
-        const int t = t_begin + simd + 4 * k;
-        const int j = k % kNB, n = k / kNB;
-        const float* tile = lds + kLBufs + (simd * kNB + j) * kBufFloats;
-        int* f_ready = flags + (simd * kNB + j) * 2, *f_free = f_ready + 1;
-        const int g = gaussian_of(t);
-        const bool ok = g >= 0;
-        // this Gaussian's inputs of the residual adds: requested now, used after the heads (a load issued where it is used costs
-        // this wave -- alone on its SIMD -- the whole memory latency, three times per tile)
-        float in_xyz[3] = {0.f, 0.f, 0.f}, in_flow[3] = {0.f, 0.f, 0.f}, in_scal[3] = {0.f, 0.f, 0.f}, in_opac = 0.f;
-        float4 in_rot = make_float4(0.f, 0.f, 0.f, 0.f);
-        constexpr bool kPrefetchIn = kNM == 1;     // with a second MFMA wave on the SIMD the loads are issued where they are used
-        if (kPrefetchIn && h == 0 && ok) {
-#pragma unroll
-            for (int q = 0; q < 3; q++) {
-                in_xyz[q] = xyz[3 * g + q];
-                in_flow[q] = flow[3 * g + q];
-                in_scal[q] = scaling[3 * g + q];
-            }
-            in_rot = *reinterpret_cast<const float4*>(rotation + 4 * g);
-            if (act.opacity) in_opac = act.opacity_raw[g];
-        }
-        f32x16 a0[2];
-        {
-            f32x16 x[2];
-            const unsigned long long s0 = STAMP();
-            flag_wait(f_ready, n + 1);
-            tw += STAMP() - s0;
-            if (k == gj) tpro = STAMP() - t00;
-            load_tile(tile, col, h, x);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // the tile is in registers: its buffer is free again
-            flag_set(f_free, n + 1);
-            init_bias(lds + kLB, a0, h);
-            const unsigned long long s1 = STAMP();
-            layer64p<false, kMfmaGroup>(lds + kLW, x, a0, col, h);
-            tl += STAMP() - s1;
-        }
-        relu_tile(a0);
-        if (a0_save) store_feat(a0_save, g, ok, h, a0);
-        // Heads.  (A software-pipelined form -- the thin output layer of head k riding between the MFMAs of head k + 1's hidden
-        // layer -- pays for a wave that is ALONE on its SIMD and needs two hidden tiles in registers; with two MFMA waves per SIMD the
-        // other wave's MFMAs fill those gaps and the plain order is used: round 3, in the git history.)
-        f32x16 hcur[2];
-#pragma nounroll
-        for (int head = 0; head < 3; head++) {
-            float o[4];
-            const unsigned long long s3 = STAMP();
-            init_bias(lds + kLB + (1 + head) * kHid, hcur, h);
-            layer64p<false, kMfmaGroup>(lds + kLW + (1 + head) * kWFloats, a0, hcur, col, h);
-            tm += STAMP() - s3;
-            relu_tile(hcur);
-            out_layer(lds + kLW2 + head * 4 * kHid, lds + kLB2 + head * 4, hcur, h, o);
-            to += STAMP() - s3;
-            if (h == 0 && ok) {
-                if (!kPrefetchIn) {
-                    if (head == 0) {
-#pragma unroll
-                        for (int q = 0; q < 3; q++) { in_xyz[q] = xyz[3 * g + q]; in_flow[q] = flow[3 * g + q]; }
-                    } else if (head == 1) {
-#pragma unroll
-                        for (int q = 0; q < 3; q++) in_scal[q] = scaling[3 * g + q];
-                    } else {
-                        in_rot = *reinterpret_cast<const float4*>(rotation + 4 * g);
-                        if (act.opacity) in_opac = act.opacity_raw[g];
-                    }
-                }
-                if (head == 0) {
-#pragma unroll
-                    for (int q = 0; q < 3; q++) pts[3 * g + q] = in_xyz[q] + (o[q] + flow_coef * in_flow[q]);
-                } else if (head == 1) {
-                    float s3v[3];
-#pragma unroll
-                    for (int q = 0; q < 3; q++) {
-                        s3v[q] = in_scal[q] + o[q];
-                        scales[3 * g + q] = s3v[q];
-                    }
-                    if (act.scales) {
-#pragma unroll
-                        for (int q = 0; q < 3; q++) act.scales[3 * g + q] = expf(s3v[q]);
-                    }
-                } else {
-                    const float4 q4 = make_float4(in_rot.x + o[0], in_rot.y + o[1], in_rot.z + o[2], in_rot.w + o[3]);
-                    *reinterpret_cast<float4*>(rots + 4 * g) = q4;
-                    if (act.rots) {
-                        const float nq = mom_quat_norm(q4.x, q4.y, q4.z, q4.w);
-                        *reinterpret_cast<float4*>(act.rots + 4 * g) = make_float4(q4.x / nq, q4.y / nq, q4.z / nq, q4.w / nq);
-                    }
-                    if (act.opacity) act.opacity[g] = mom_sigmoid(in_opac);
-                }
-            }
-        }
-    }
-#ifdef MOM_FIELD_STAMPS
-    if (lane == 0) {
-        unsigned long long* d = g_field_dbg + ((size_t)blockIdx.x * 32 + wv) * 4;
-        d[0] = tw; d[1] = tpro; d[2] = STAMP() - t00; d[3] = k;
-        unsigned long long* e = g_field_dbg + ((size_t)blockIdx.x * 32 + 16 + wv) * 4;
-        e[0] = tl; e[1] = tm; e[2] = to; e[3] = 0;
-    }
-#endif
-}
 
 // ---- the MLP on the bf16 matrix cores, fp32-exact operands --------------------------------------------------------------
 // v_mfma_f32_32x32x2_f32 runs at the fp32 VECTOR rate and occupies the SIMD's vector ALU while it does (tools/probe/
@@ -507,7 +260,7 @@ deform_field_fwd_b3_kernel(HexArgs a, LineTab lt, MlpDev m, int tiles, const flo
     const int lane = threadIdx.x & 63, col = lane & 31, h = lane >> 5, wv = threadIdx.x >> 6;
     uint4* rec = reinterpret_cast<uint4*>(lds + kL3Recs + wv * 64 * kRecDw);
     const int P = a.P;
-    const unsigned long long t_start = STAMP();
+    [[maybe_unused]] const unsigned long long t_start = STAMP();     // (the stamps: MOM_FIELD_STAMPS builds only)
     // ---- prologue: weight fragments (exact three-way split), biases, output layers
     {
         const float* Ws[4] = {m.W0, m.W1[0], m.W1[1], m.W1[2]};
@@ -536,9 +289,9 @@ deform_field_fwd_b3_kernel(HexArgs a, LineTab lt, MlpDev m, int tiles, const flo
     }
     __syncthreads();
     const int t_begin = (int)((long long)tiles * blockIdx.x / gridDim.x), t_end = (int)((long long)tiles * (blockIdx.x + 1) / gridDim.x);
-    unsigned long long tg = 0, tb = 0, tl = 0, to = 0;
+    [[maybe_unused]] unsigned long long tg = 0, tb = 0, tl = 0, to = 0;
     int n_t = 0;
-    const unsigned long long t_pro = STAMP();
+    [[maybe_unused]] const unsigned long long t_pro = STAMP();
     const int n_waves = (int)(blockDim.x >> 6);
     for (int t = t_begin + wv; t < t_end; t += n_waves, n_t++) {
         const int gi = t * 32 + col;
@@ -561,7 +314,7 @@ deform_field_fwd_b3_kernel(HexArgs a, LineTab lt, MlpDev m, int tiles, const flo
         }
         // features: gathered eight lanes per (point, level), bounced through this wave's own rows of feat[P,64] (kept for the
         // backward anyway) into the MFMA layout; the rows were written by this wave: visible to it after the wait
-        gather_tile(a, lt, lines, xyz, g, nullptr, rec, feat, lane);
+        gather_tile(a, lt, lines, xyz, g, rec, feat, lane);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const unsigned long long s1 = STAMP();
         Frag3 B[4];
@@ -636,9 +389,10 @@ deform_field_fwd_b3_kernel(HexArgs a, LineTab lt, MlpDev m, int tiles, const flo
 
 
 // ---- HexPlane backward, pass 1 (gather) in the forward's layout ------------------------------------------------------------
-// Same contract as hexplane_bwd5_gather_kernel (hexplane.hip): per (point, level) the six samples, their product, the six
-// gv = dfeat * (product of the other five) rows STORED at the point's position in the order of the space plane each row is
-// scattered with, and the position gradient reduced over the channels.  What changes is the shape: eight lanes own one
+// The work of hexplane_bwd5_gather_kernel (hexplane.hip): per (point, level) the six samples, their product, the six
+// gv = dfeat * (product of the other five) rows, and the position gradient reduced over the channels; what is STORED, at the
+// point's position in the order of the space plane it is scattered with, is one common-factor row per order slot from which
+// the scatter pass forms the slot's two gv rows (see the kernel's epilogue).  What changes is the shape: eight lanes own one
 // (point, level) with four channels each, so the 18 texel rows (the space-time planes are this frame's lines: two rows instead
 // of four) are 18 sixteen-byte loads per lane and one wave instruction serves eight (point, level) units; the lane-per-channel
 // kernel issued 24 four-byte loads per two units and spent half its time issuing vector instructions (37 M per launch).  A wave
@@ -667,11 +421,10 @@ __device__ __forceinline__ float unit_sum(float v)
 }
 
 #define HX6_WAVES 3
-template <bool CROWS>
 __global__ void __launch_bounds__(256, HX6_WAVES)
 hexplane_bwd6_gather_kernel(HexArgs a, LineTab lt, int nchunks, const float* __restrict__ lines, const float* __restrict__ xyz,
                             const float* __restrict__ dfeat, float* __restrict__ dxyz, const uint32_t* __restrict__ inv /* [3][levels][P] */,
-                            float* __restrict__ gvbuf /* [3 slots][levels][P][2][32]; CROWS: common-factor rows [3 slots][levels][P][32] */)
+                            float* __restrict__ gvbuf /* common-factor rows [3 slots][levels][P][32] */)
 {
     __shared__ uint4 s_rec[4][64 * (kRec6Dw / 4)];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -718,7 +471,7 @@ hexplane_bwd6_gather_kernel(HexArgs a, LineTab lt, int nchunks, const float* __r
                 }
                 R2 = make_uint4(__float_as_uint(gm[0]), __float_as_uint(gm[1]), __float_as_uint(gm[2]), 0u);
 #pragma unroll
-                for (int k = 0; k < 3; k++) (&R3.x)[k] = iv[k] * (CROWS ? 128u : 256u);   // CROWS: [slot][level][position][32], else [..][position][space | time][32]
+                for (int k = 0; k < 3; k++) (&R3.x)[k] = iv[k] * 128u;   // byte offset in [slot][level][position][32]
                 R3.w = (unsigned)g_mine;
             }
             rec[4 * lane] = R0;
@@ -798,11 +551,6 @@ hexplane_bwd6_gather_kernel(HexArgs a, LineTab lt, int nchunks, const float* __r
 #pragma unroll
                 for (int p = 0; p < 6; p++) {
                     const float4 gv = p == 5 ? pre[5] : mul44(pre[p], suf[p]);
-                    if (!CROWS && live) {
-                        const unsigned pos = p == 0 || p == 2 ? R3.x : (p == 1 || p == 5 ? R3.y : R3.z);     // order slot of the plane
-                        *reinterpret_cast<float4*>(reinterpret_cast<char*>(gvbuf + ((size_t)(p == 0 || p == 2 ? 0 : (p == 1 || p == 5 ? 1 : 2)) * a.levels + lvl) * 2 * plane_floats) +
-                                                   pos + (p == 2 || p == 4 || p == 5 ? 128u : 0u) + cb) = gv;
-                    }
                     // first coordinate of the plane: x for 0 1 2, y for 3 4, z for 5; second: y for 0, z for 1 and 3
                     if (p < 3) gx = dot4(gv, da[p], gx);
                     else if (p < 5) gy = dot4(gv, da[p], gy);
@@ -811,13 +559,13 @@ hexplane_bwd6_gather_kernel(HexArgs a, LineTab lt, int nchunks, const float* __r
                     if (p == 1) gz = dot4(gv, db[1], gz);
                     if (p == 3) gz = dot4(gv, db[2], gz);
                 }
-                // CROWS: what goes to memory is ONE row per order slot, not the two gv rows of the slot's planes: the factor they share,
+                // What goes to memory is ONE row per order slot, not the two gv rows of the slot's planes: the factor they share,
                 // c = dfeat * (product of the four OTHER planes' samples).  The scatter pass multiplies it by the time line's sample
                 // (gv of the space plane) and by the space plane's own sample (gv of the time plane) -- both of which it has at hand:
                 // the line values sit in its LDS and the space plane's four texel rows are the rows it is accumulating into.
                 // 154 MB of rows written and read back per step instead of 307 MB each way, on a stretch bound by memory bandwidth.
                 //   slot 0 = (x,y) + (x,t): planes 0, 2     slot 1 = (x,z) + (z,t): planes 1, 5     slot 2 = (y,z) + (y,t): planes 3, 4
-                if (CROWS && live) {
+                if (live) {
                     const float4 c0 = mul44(mul44(go, v[1]), suf[2]);                    // go v1 (v3 v4 v5)
                     const float4 c1 = mul44(pre[1], mul44(mul44(v[2], v[3]), v[4]));     // (go v0) v2 v3 v4
                     const float4 c2 = mul44(pre[3], v[5]);                               // (go v0 v1 v2) v5
@@ -853,7 +601,7 @@ size_t mom_hexplane_lines_bytes(const MomHexPlane* hp)
 // pass 1 of the two-pass HexPlane backward for a field mom_deform_field_supported() accepts (called by mom_hexplane_backward,
 // hexplane.hip): the frame's lines into `lines`, then the gather
 int mom_launch_hexplane_gather6(const MomHexPlane* hp, int P, const float* xyz, float time, const uint32_t* order, const float* dfeat,
-                                float* dxyz, const uint32_t* plane_inverse, float* gvbuf, float* lines, bool lines_ready, bool crows, hipStream_t s)
+                                float* dxyz, const uint32_t* plane_inverse, float* gvbuf, float* lines, bool lines_ready, hipStream_t s)
 {
     HexArgs a;
     fill_args(hp, P, nullptr, time, order, true, &a);
@@ -861,15 +609,11 @@ int mom_launch_hexplane_gather6(const MomHexPlane* hp, int P, const float* xyz, 
     const int nline = line_table(hp, &lt);
     if (!lines_ready) hipLaunchKernelGGL(hexplane_lines_kernel, dim3((nline + 255) / 256), dim3(256), 0, s, a, lt, lines, nline);
     const int nchunks = (P + 31) / 32;
-    static int cap = 0;
     // workgroups (MOM_HEX6_BLOCKS overrides); measured, gather + scatter beside dW: 512 293 us, 1024 281, 1536 280, 4096 280
-    if (!cap) { const char* e = getenv("MOM_HEX6_BLOCKS"); cap = e ? atoi(e) : 1536; if (cap < 1) cap = 1536; }
+    static const int cap = mom_env_int("MOM_HEX6_BLOCKS", 1536, 1, 1 << 20);
     int blocks = (nchunks + 3) / 4;
     if (blocks > cap) blocks = cap;
-    if (crows)
-        hipLaunchKernelGGL(hexplane_bwd6_gather_kernel<true>, dim3(blocks), dim3(256), 0, s, a, lt, nchunks, lines, xyz, dfeat, dxyz, plane_inverse, gvbuf);
-    else
-        hipLaunchKernelGGL(hexplane_bwd6_gather_kernel<false>, dim3(blocks), dim3(256), 0, s, a, lt, nchunks, lines, xyz, dfeat, dxyz, plane_inverse, gvbuf);
+    hipLaunchKernelGGL(hexplane_bwd6_gather_kernel, dim3(blocks), dim3(256), 0, s, a, lt, nchunks, lines, xyz, dfeat, dxyz, plane_inverse, gvbuf);
     return hipGetLastError() == hipSuccess ? MOM_OK : MOM_ELAUNCH;
 }
 
@@ -922,47 +666,16 @@ extern "C" int mom_deform_field_forward(const MomHexPlane* hp, const MomDeformML
     hipLaunchKernelGGL(hexplane_lines_kernel, dim3((nline + 255) / 256), dim3(256), 0, s, a, lt, lines, nline);
     const int tiles = (P + 31) / 32;
     const ActOut act = {scales_act, rots_act, opacity_act, opacity_raw};
-    static int mode = -1;                 // MOM_FIELD_MODE=f32: the f32-MFMA kernel (gather waves feeding MFMA waves; measurement)
-    if (mode < 0) {
-        const char* e = getenv("MOM_FIELD_MODE");
-        mode = (e && e[0] == 'f') ? 1 : 0;
-    }
-    if (mode == 0) {
-        float* feat = feat_save ? feat_save : (float*)mom_align_ptr((char*)lines + mom_align_up((size_t)nline * sizeof(float)));
-        // Waves per workgroup (MOM_B3_RUN_WAVES overrides): measured at 200 k Gaussians, 24.4 tiles per CU: 5 waves 116 us, 6: 109,
-        // 8: 98, 9: 92, 10: 91, 11: 86, 12: 87 -- the gather wants bytes in flight more than the tile rounds want an even split
-        // (12 waves take 3 rounds for 2.03 tiles each, 10 waves 3 rounds for 2.44)
-        int waves = kB3Waves;
-        {
-            static int forced = -1;
-            if (forced < 0) { const char* e = getenv("MOM_B3_RUN_WAVES"); forced = e ? atoi(e) : 0; }
-            if (forced >= 4 && forced <= kB3Waves) waves = forced;
-        }
-        const int blocks = tiles < 256 * waves ? (tiles + waves - 1) / waves : 256;
-        static bool attr_b3 = false;
-        const size_t lds_b3 = sizeof(float) * kL3Total;
-        if (!attr_b3) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(deform_field_fwd_b3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds_b3) != hipSuccess)
-                return MOM_ELAUNCH;
-            attr_b3 = true;
-        }
-        hipLaunchKernelGGL(deform_field_fwd_b3_kernel, dim3(blocks), dim3(64 * waves), lds_b3, s, a, lt, d, tiles, lines, xyz, scaling,
-                           rotation, scene_flow, flow_coef, pts, scales, rots, feat, a0_save, act);
-        return hipGetLastError() == hipSuccess ? MOM_OK : MOM_ELAUNCH;
-    }
-    // one workgroup per CU (MFMA waves fed by gather waves); a small problem is spread over the CUs
-    const int blocks = tiles < 256 * 4 ? (tiles + 3) / 4 : 256;
-    static bool attr_set = false;
-    const size_t lds_bytes = sizeof(float) * kLFieldTotal;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(deform_field_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_bytes) != hipSuccess)
-            return MOM_ELAUNCH;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(deform_field_fwd_kernel, dim3(blocks), dim3(64 * kFieldWaves), lds_bytes, s, a, lt, d, tiles, lines, xyz, scaling,
-                       rotation, scene_flow, flow_coef, pts, scales, rots, feat_save, a0_save, act);
+    float* feat = feat_save ? feat_save : (float*)mom_align_ptr((char*)lines + mom_align_up((size_t)nline * sizeof(float)));
+    // Waves per workgroup (MOM_B3_RUN_WAVES overrides): measured at 200 k Gaussians, 24.4 tiles per CU: 5 waves 116 us, 6: 109,
+    // 8: 98, 9: 92, 10: 91, 11: 86, 12: 87 -- the gather wants bytes in flight more than the tile rounds want an even split
+    // (12 waves take 3 rounds for 2.03 tiles each, 10 waves 3 rounds for 2.44)
+    static const int waves = mom_env_int("MOM_B3_RUN_WAVES", kB3Waves, 4, kB3Waves);
+    const int blocks = tiles < 256 * waves ? (tiles + waves - 1) / waves : 256;
+    const size_t lds_b3 = sizeof(float) * kL3Total;
+    if (!mom_lds_limit<deform_field_fwd_b3_kernel>(lds_b3)) return MOM_ELAUNCH;
+    hipLaunchKernelGGL(deform_field_fwd_b3_kernel, dim3(blocks), dim3(64 * waves), lds_b3, s, a, lt, d, tiles, lines, xyz, scaling,
+                       rotation, scene_flow, flow_coef, pts, scales, rots, feat, a0_save, act);
     return hipGetLastError() == hipSuccess ? MOM_OK : MOM_ELAUNCH;
 }
 

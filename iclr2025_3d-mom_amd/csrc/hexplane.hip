@@ -15,7 +15,6 @@
 // border, nw/ne/sw/se weights, accumulation order nw,ne,sw,se) so that results agree with the
 // reference's torch ops to rounding.
 #include "hexplane_dev.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -729,7 +728,7 @@ extern "C" int mom_hexplane_orders(const MomHexPlane* hp, int P, const float* xy
 // deform_field.hip: the gather in the fused forward's layout, for fields mom_deform_field_supported() accepts
 size_t mom_hexplane_lines_bytes(const MomHexPlane* hp);
 int mom_launch_hexplane_gather6(const MomHexPlane* hp, int P, const float* xyz, float time, const uint32_t* order, const float* dfeat,
-                                float* dxyz, const uint32_t* plane_inverse, float* gvbuf, float* lines, bool lines_ready, bool crows, hipStream_t s);
+                                float* dxyz, const uint32_t* plane_inverse, float* gvbuf, float* lines, bool lines_ready, hipStream_t s);
 extern "C" int mom_deform_field_supported(const MomHexPlane* hp);
 
 static size_t gv_bytes(const MomHexPlane* hp, int P) { return mom_align_up((size_t)6 * (size_t)P * (size_t)hp->levels * 32 * sizeof(float)); }
@@ -783,37 +782,23 @@ static int hexplane_backward(const MomHexPlane* hp, int P, const float* xyz, con
     const bool fits32 = (unsigned long long)P * 256ull < (1ull << 32);
     if (!times && plane_order && plane_inverse && scratch && lds_s <= 160 * 1024 && fits32) {
         // two-pass path: one shared timestamp, per-plane orders and the gv scratch given
-        static bool attr_set = false;
-        if (!attr_set) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(hexplane_bwd5_scatter_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(hexplane_bwd5_scatter_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024) != hipSuccess)
-                return MOM_ELAUNCH;
-            attr_set = true;
-        }
+        if (!mom_lds_limit<hexplane_bwd5_scatter_kernel<false>>(160 * 1024) || !mom_lds_limit<hexplane_bwd5_scatter_kernel<true>>(160 * 1024))
+            return MOM_ELAUNCH;
         float* gvbuf = (float*)mom_align_ptr(scratch);
-        static int blocks_g = 0, blocks_s = 0;
-        if (!blocks_g) {
-            const char* e = getenv("MOM_HEX_BLOCKS");
-            blocks_g = e ? atoi(e) : 1536;
-            const char* e2 = getenv("MOM_HEX_SBLOCKS");
-            blocks_s = e2 ? atoi(e2) : 512;
-        }
-        // MOM_HEX_GATHER=5: the lane-per-channel gather (measurement, and the comparison in tests/test_ops_gpu.py; read per call)
-        const char* e_g = getenv("MOM_HEX_GATHER");
-        const int gather6 = (e_g && e_g[0] == '5') ? 0 : 1;
-        const size_t lds_c = lds_s;
-        const bool use6 = gather6 && mom_deform_field_supported(hp);
-        // One common-factor row per (slot, position) instead of the slot's two gv rows (see the scatter kernel); MOM_HEX_CROWS=0: the
-        // six-row form.  Measured at 200 k Gaussians: alone the two passes take 83 + 81 us instead of 105 + 84 and move 307 MB
+        // workgroups of the lane-per-channel gather, at most: six per CU (the default of the former MOM_HEX_BLOCKS; no measurement
+        // of its own is recorded -- the gather that replaced it on the step's path has one for the same cap: deform_field.hip)
+        constexpr int kGather5MaxBlocks = 1536;
+        static const int blocks_s = mom_env_int("MOM_HEX_SBLOCKS", 512, 1, 1 << 16);
+        // MOM_HEX_GATHER=5: the lane-per-channel gather and the six-row scatter, which are also what a field of another shape gets
+        // (measurement, and the comparison in tests/test_ops_gpu.py; read per call)
+        const bool use6 = mom_env_int("MOM_HEX_GATHER", 6, 5, 6) == 6 && mom_deform_field_supported(hp);
+        // use6: one common-factor row per (slot, position) instead of the slot's two gv rows (see the scatter kernel).  Measured
+        // against the six-row form at 200 k Gaussians: alone the two passes take 83 + 81 us instead of 105 + 84 and move 307 MB
         // less; beside the MLP's weight-gradient kernel, where they run in the training step, 117 + 141 against 160 + 105 (the
         // scatter now waits for the texel values of every new cell in the middle of its walk, and a walk that waits suffers more
         // from a neighbour than one that streams).  The step, same box, alternating runs: +0.2 ... +1.4 % at 200 k Gaussians,
         // +5 % at 1 M (1080p), +6 % at 4 M.  (Staging the line values in LDS cost two of five workgroups per CU: 106 us; requesting
         // the flagged positions' texel values with the batch's rows, after a scan of the batch's flags: 116 us.)
-        const char* e_c = getenv("MOM_HEX_CROWS");
-        const bool crows = use6 && !(e_c && e_c[0] == '0');
         const float* lines_c = nullptr;
         LineTab lt;
         line_table(hp, &lt);
@@ -822,13 +807,13 @@ static int hexplane_backward(const MomHexPlane* hp, int P, const float* xyz, con
             float* lines = field_scratch ? (float*)mom_align_ptr(const_cast<void*>(field_scratch))
                                          : (float*)mom_align_ptr((char*)gvbuf + gv_bytes(hp, P));
             int rc = mom_launch_hexplane_gather6(hp, P, xyz, time, order, dfeat, dxyz, plane_inverse, gvbuf, lines, field_scratch != nullptr,
-                                                 crows, (hipStream_t)stream);
+                                                 (hipStream_t)stream);
             if (rc) return rc;
             lines_c = lines;
         } else {
             const int nchunks = (P + kChunk5 - 1) / kChunk5;
             int blocks = (nchunks + 3) / 4;
-            if (blocks > blocks_g) blocks = blocks_g;
+            if (blocks > kGather5MaxBlocks) blocks = kGather5MaxBlocks;
             hipLaunchKernelGGL(hexplane_bwd5_gather_kernel, dim3(blocks, hp->levels), dim3(256), 0, (hipStream_t)stream, a, nchunks, xyz,
                                dfeat, dxyz, plane_inverse, gvbuf);
             if (hipGetLastError() != hipSuccess) return MOM_ELAUNCH;
@@ -839,8 +824,8 @@ static int hexplane_backward(const MomHexPlane* hp, int P, const float* xyz, con
             int per_half = (P + halves - 1) / halves;
             per_half = ((per_half + kChunk5s - 1) / kChunk5s) * kChunk5s;
             const int blocks = (int)(((long long)P + (long long)per_half * 8 - 1) / ((long long)per_half * 8));
-            if (crows)       // the gather left one common-factor row per (slot, position): this pass forms the two gv rows itself
-                hipLaunchKernelGGL(hexplane_bwd5_scatter_kernel<true>, dim3(blocks, 3, hp->levels), dim3(256), lds_c, (hipStream_t)stream, a,
+            if (use6)        // the gather left one common-factor row per (slot, position): this pass forms the two gv rows itself
+                hipLaunchKernelGGL(hexplane_bwd5_scatter_kernel<true>, dim3(blocks, 3, hp->levels), dim3(256), lds_s, (hipStream_t)stream, a,
                                    per_half, xyz, plane_order, gvbuf, lines_c, lt);
             else
                 hipLaunchKernelGGL(hexplane_bwd5_scatter_kernel<false>, dim3(blocks, 3, hp->levels), dim3(256), lds_s, (hipStream_t)stream, a,

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
 #include "../../include/mom4d.h"
 
 #define MOM_WAVE 64
@@ -96,6 +97,26 @@ static inline size_t bin_view(char* base, size_t cap, BinView* v)
 static inline char* mom_align_ptr(void* p)
 {
     return (char*)(((uintptr_t)p + MOM_ALIGN - 1) & ~(uintptr_t)(MOM_ALIGN - 1));
+}
+
+// An integer switch from the environment (every integer MOM_* switch of the library goes through here; the two string-valued
+// ones, MOM_MLP_BWD and MOM_RCCL_LIB, are read where they are used): unset, empty, not a number or outside [lo, hi] gives dflt.
+static inline int mom_env_int(const char* name, int dflt, int lo, int hi)
+{
+    const char* e = getenv(name);
+    if (!e || !*e) return dflt;
+    char* end;
+    const long v = strtol(e, &end, 10);
+    return (*end || v < lo || v > hi) ? dflt : (int)v;
+}
+
+// Raises a kernel's dynamic-LDS limit to `bytes`, once per kernel: mom_lds_limit<my_kernel>(bytes).  False: the runtime refused.
+template <auto Kernel>
+static inline bool mom_lds_limit(size_t bytes)
+{
+    static bool done = false;
+    if (!done) done = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+    return done;
 }
 
 // flags of the events that order two streams of one device (stream_order.hip)

@@ -7,7 +7,6 @@
 // gradient).  All are streaming passes: 16-byte accesses where the layout allows, grid-stride,
 // one atomic per workgroup for reductions.
 #include "mom_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -284,12 +283,7 @@ extern "C" int mom_l1_loss_acc(size_t n, const float* img, const float* gt, floa
     if (n == 0) return MOM_OK;
     // every block ends with two atomics on the same two floats, and same-address atomics serialise in the L2: with 760
     // blocks that tail cost more than streaming the images.  A few hundred fat blocks keep every CU busy and the tail short.
-    static size_t cap = 0;
-    if (!cap) {
-        const char* e = getenv("MOM_L1_BLOCKS");
-        cap = e ? (size_t)atoi(e) : 256;
-        if (cap < 1) cap = 1;
-    }
+    const size_t cap = 256;
     size_t blocks = (n + 256 * 4 - 1) / (256 * 4);
     if (blocks > cap) blocks = cap;
     MomProfScope ps(MOM_P_L1, (hipStream_t)stream);

@@ -1,12 +1,10 @@
 // extern "C" entry points of the rasterizer (see include/mom4d.h).
 #include "mom_common.h"
-#include <stdlib.h>
 
-int mom_launch_preprocess_fwd(const MomRasterArgs* a, const GeomView& g, int* radii, uint32_t* zero_words, int n_zero,
-                              uint32_t* hist_counts, bool* did_hist, hipStream_t s);
+int mom_launch_preprocess_fwd(const MomRasterArgs* a, const GeomView& g, int* radii, uint32_t* zero_words, int n_zero, hipStream_t s);
 int mom_launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
 int mom_launch_binning_count(const MomRasterArgs* a, const GeomView& g, const ImageView& im, uint32_t* num_rendered_dev,
-                             uint32_t* num_rendered_host, bool hist_done, hipStream_t s);
+                             uint32_t* num_rendered_host, hipStream_t s);
 int mom_launch_binning_sort(const MomRasterArgs* a, const GeomView& g, const BinView& b, const ImageView& im, size_t capacity,
                             uint32_t* status_dev, bool render_sorts_small, hipStream_t s);
 int mom_launch_render_fwd(const MomRasterArgs* a, const GeomView& g, const BinView& b, const ImageView& im, size_t capacity,
@@ -115,13 +113,10 @@ int mom_raster_forward_geometry(const MomRasterArgs* a, void* geom, void* image,
     image_view(mom_align_ptr(image), a->W, a->H, &im);
     // the header and the tile counters are adjacent in the image scratch (image_view): the projection kernel clears both
     const int tiles = ((a->W + MOM_TILE - 1) / MOM_TILE) * ((a->H + MOM_TILE - 1) / MOM_TILE);
-    bool did_hist = false;
-    static int fold = -1;                 // MOM_FOLD_HIST=1: the tile histogram inside the projection kernel (measured: slower, see raster_preprocess.hip)
-    if (fold < 0) { const char* e = getenv("MOM_FOLD_HIST"); fold = (e && e[0] == '1') ? 1 : 0; }
-    rc = mom_launch_preprocess_fwd(a, g, radii, im.hdr, (int)((im.tile_counts + tiles) - im.hdr), fold ? im.tile_counts : nullptr, &did_hist, s);
+    rc = mom_launch_preprocess_fwd(a, g, radii, im.hdr, (int)((im.tile_counts + tiles) - im.hdr), s);
     if (rc) return rc;
     MOM_CHECK_LAUNCH(a, s);
-    rc = mom_launch_binning_count(a, g, im, num_rendered_dev, num_rendered_host, did_hist, s);
+    rc = mom_launch_binning_count(a, g, im, num_rendered_dev, num_rendered_host, s);
     if (rc) return rc;
     MOM_CHECK_LAUNCH(a, s);
     return MOM_OK;
@@ -147,8 +142,7 @@ int mom_raster_forward_render(const MomRasterArgs* a, void* geom, void* binning,
     bin_view(mom_align_ptr(binning), capacity, &b);
     // MOM_RENDER_SORT=0: every tile sorted by the binning's own launches (measurement, and the comparison in tests/test_raster_gpu.py;
     // read per call for that)
-    const char* e_sort = getenv("MOM_RENDER_SORT");
-    const int merged = (e_sort && e_sort[0] == '0') ? 0 : 1;
+    const int merged = mom_env_int("MOM_RENDER_SORT", 1, 0, 1);
     rc = mom_launch_binning_sort(a, g, b, im, capacity, status_dev, merged != 0, s);
     if (rc) return rc;
     MOM_CHECK_LAUNCH(a, s);

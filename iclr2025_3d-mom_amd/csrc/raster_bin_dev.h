@@ -1,6 +1,4 @@
-// Device helpers of the tile binning shared by raster_binning.hip and raster_preprocess.hip (the projection kernel also decides
-// which (splat, tile) instances are binned and counts them per tile: the per-(splat, tile) test sits in a kernel that waits for
-// memory most of the time, and the separate histogram launch with its second read of the records is gone).
+// Device helpers of the tile binning (raster_binning.hip): the per-(splat, tile) decision tile_hist_kernel and tile_scatter_kernel share.
 #pragma once
 #include "mom_common.h"
 

@@ -22,7 +22,6 @@
 //                     so no padding is ever materialised) and writes point_list.
 // Instances never travel through HBM more than: 8 B write, 8 B read, 4 B write.
 #include "raster_bin_dev.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -328,8 +327,16 @@ __global__ void __launch_bounds__(256) tile_sort_kernel(const uint2* __restrict_
 
 }  // namespace
 
+// 256-Gaussian chunks per workgroup of tile_hist and tile_scatter: one, until the grid would pass 2048 workgroups (fatter
+// workgroups -- fewer global atomics -- were slower at every setting tried: the atomics were not the cost, parallelism was)
+static int bin_chunks(int P)
+{
+    const int chunks = (P + 256 * 2048 - 1) / (256 * 2048);
+    return chunks < 1 ? 1 : chunks;
+}
+
 int mom_launch_binning_count(const MomRasterArgs* a, const GeomView& g, const ImageView& im, uint32_t* num_rendered_dev,
-                             uint32_t* num_rendered_host, bool hist_done, hipStream_t s)
+                             uint32_t* num_rendered_host, hipStream_t s)
 {
     const int gx = (a->W + MOM_TILE - 1) / MOM_TILE, gy = (a->H + MOM_TILE - 1) / MOM_TILE;
     const int tiles = gx * gy;
@@ -339,18 +346,10 @@ int mom_launch_binning_count(const MomRasterArgs* a, const GeomView& g, const Im
     // the header and the tile counters were cleared by the projection kernel (raster_api.hip): no fill launch here.  (Folding
     // the scan into the histogram kernel too -- the last workgroup to finish scans -- was measured and dropped: with the
     // device-scope fence the ticket needs, 782 workgroups each wrote the L2 back, 27 -> 72 us.)
-    int chunks = (a->P + 256 * 2048 - 1) / (256 * 2048);
-    if (chunks < 1) chunks = 1;
-    {
-        static int forced = -1;           // MOM_BIN_CHUNKS: 256-Gaussian chunks per workgroup (measurement)
-        if (forced < 0) { const char* e = getenv("MOM_BIN_CHUNKS"); forced = e ? atoi(e) : 0; }
-        if (forced > 0) chunks = forced;
-    }
+    const int chunks = bin_chunks(a->P);
     const int blocks = (a->P + 256 * chunks - 1) / (256 * chunks);
     mom_prof_begin(MOM_P_HIST, s);
-    if (hist_done) {
-        // the projection kernel counted the instances (raster_preprocess.hip, HIST)
-    } else if (tiles <= kMaxLdsTiles)
+    if (tiles <= kMaxLdsTiles)
         hipLaunchKernelGGL(tile_hist_kernel<true>, dim3(blocks), dim3(256), (size_t)tiles * 4, s, a->P, chunks, gx, gy, ry0, ry1, cull,
                            g.rec, im.tile_counts, g.reach);
     else
@@ -372,13 +371,7 @@ int mom_launch_binning_sort(const MomRasterArgs* a, const GeomView& g, const Bin
     int ry0, ry1;
     mom_tile_rows(a, gy, &ry0, &ry1);
     const int cull = a->keep_all_tiles ? 0 : 1;
-    int chunks = (a->P + 256 * 2048 - 1) / (256 * 2048);
-    if (chunks < 1) chunks = 1;
-    {
-        static int forced = -1;           // MOM_BIN_CHUNKS: 256-Gaussian chunks per workgroup (measurement)
-        if (forced < 0) { const char* e = getenv("MOM_BIN_CHUNKS"); forced = e ? atoi(e) : 0; }
-        if (forced > 0) chunks = forced;
-    }
+    const int chunks = bin_chunks(a->P);
     const int blocks = (a->P + 256 * chunks - 1) / (256 * chunks);
     const uint32_t cap = capacity > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)capacity;
     const uint32_t tag = a->overflow_tag ? a->overflow_tag : 1u;

@@ -5,7 +5,7 @@
 // -ffp-contract=off: radii, tile rectangles and the depth sort keys must be
 // bit-identical to an IEEE evaluation of the reference's expressions in source
 // order (fp64 ndc2Pix, truncating casts, un-normalised quaternion), and they are.
-#include "raster_bin_dev.h"
+#include "mom_common.h"
 
 namespace {
 
@@ -47,44 +47,30 @@ struct PreArgs {
     const float *means3D, *shs, *shs_rest, *colors_precomp, *opacities, *scales, *rotations, *cov3D_precomp;
     const float *view, *proj, *cam;  // device pointers, [16] [16] [3]
     float scale_modifier, tan_fovx, tan_fovy, focal_x, focal_y;
-    // HIST: the tile histogram of the binning rides in this kernel (rows [ry0, ry1) of tiles, cull as MomRasterArgs.keep_all_tiles)
-    int ry0, ry1, cull;
-    uint32_t* tile_counts;
-    unsigned long long* reach;
 };
 
 // STAGED: the higher-order SH coefficients of the workgroup's 256 Gaussians -- (M-1)*3 floats each, contiguous in memory --
 // are copied to LDS with coalesced 16-byte loads and each thread then reads its own row from there (row stride odd: no
 // bank conflicts).  Read in place, a thread's 180-byte row makes every load instruction touch 64 different cache lines.
-// HIST: after the projection every wave decides which (splat, tile) instances of its 64 Gaussians are binned (decide_instances,
-// raster_bin_dev.h: the reach test of the tile cull), counts them per tile in an LDS histogram behind the SH rows, leaves the
-// decisions as a 64-bit mask per Gaussian and the workgroup flushes its histogram with one global atomic per non-empty tile --
-// what tile_hist_kernel did in a launch of its own (27 us at 200 k Gaussians, most of it waiting for the records this kernel
-// still holds in registers).  The caller clears the header and the counters with a fill command in front of this kernel.
 // RAW (MomRasterArgs.params_raw): scales / rotations / opacities are the model's raw parameters and the activations of render()
 // (exp, normalize, sigmoid: gaussian_renderer/__init__.py:130-132) are applied here, in registers, with the helpers
 // mom_activations_forward uses (optim_loss.hip, act_fwd_kernel) -- the same bits as that kernel's output fed to this one.
-template <bool STAGED, bool HIST, bool RAW>
+template <bool STAGED, bool RAW>
 __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreArgs a, int* __restrict__ radii, float4* __restrict__ rec,
                                                             float* __restrict__ cov3Ds, uchar4* __restrict__ clamped,
                                                             uint32_t* __restrict__ zero_words, int n_zero, int sh_floats)
 {
     extern __shared__ float s_sh[];
-    uint32_t* s_cnt = reinterpret_cast<uint32_t*>(s_sh + sh_floats);
     const int idx = blockIdx.x * 256 + threadIdx.x;
     // the image scratch's header and tile counters, which the binning kernels behind this one accumulate into, are cleared
-    // here instead of by a fill launch of their own (not with HIST: this kernel then accumulates into them itself)
-    if (!HIST)
-        for (int i = idx; i < n_zero; i += gridDim.x * 256) zero_words[i] = 0u;
-    const int n_tiles = a.gx * a.gy;
-    if (HIST)
-        for (int t = threadIdx.x; t < n_tiles; t += 256) s_cnt[t] = 0u;
+    // here instead of by a fill launch of their own
+    for (int i = idx; i < n_zero; i += gridDim.x * 256) zero_words[i] = 0u;
     const int sh_stride = (a.M - 1) * 3;
     // Everything this thread reads of its Gaussian, asked for in ONE go and before the SH rows are staged.  Read where it is used,
     // each item sat behind the cull test before it -- position -> scale + rotation -> DC colour, one channel at a time -> opacity:
     // seven dependent round trips in a kernel whose workgroups live as long as their longest chain.
     const bool live = idx < a.P;
-    const int gi = live ? idx : 0;                 // lanes past the end (HIST keeps them for the ballots) read Gaussian 0 and discard
+    const int gi = live ? idx : 0;                 // lanes past the end (kept for the staging loop below) read Gaussian 0 and discard
     float px = a.means3D[3 * gi], py = a.means3D[3 * gi + 1], pz = a.means3D[3 * gi + 2];
     float in_c3[6], in_s[3], in_q[4], in_col[3];
     {
@@ -126,8 +112,6 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreArgs a, int* __r
         }
         for (int i = 4 * n4 + threadIdx.x; i < n; i += 256) s_sh[i] = src[i];
         __syncthreads();
-    } else if (HIST) {
-        __syncthreads();
     }
     // All of it complete HERE, not one by one behind the tests below.  (Not `asm volatile`: with no memory operands that still counts
     // as a possible store, and the uniform loads of the view / projection matrices behind it become vector loads -- three more
@@ -143,7 +127,7 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreArgs a, int* __r
         for (int i = 0; i < 4; i++) in_q[i] = in_q[i] / n;
         in_opacity = mom_sigmoid(in_opacity);
     }
-    if (!HIST && idx >= a.P) return;
+    if (idx >= a.P) return;
     const float* __restrict__ view = a.view;
     const float* __restrict__ proj = a.proj;
     const float* __restrict__ cam = a.cam;
@@ -152,7 +136,6 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreArgs a, int* __r
     uint32_t tiles = 0;
     float4 r0 = {0.f, 0.f, 0.f, 0.f}, r1 = {0.f, 0.f, 0.f, 0.f}, r2 = {0.f, 0.f, 0.f, 0.f};
     uchar4 cl = {0, 0, 0, 0};
-    int hx0 = 0, hy0 = 0, hx1 = 0, hy1 = 0;        // the rectangle of tiles (HIST)
     // near cull: keep iff p_view.z > 0.2
     const float vx = view[0] * px + view[4] * py + view[8] * pz + view[12];
     const float vy = view[1] * px + view[5] * py + view[9] * pz + view[13];
@@ -259,7 +242,6 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreArgs a, int* __r
         }
         radius = (int)my_radius;
         tiles = cnt;
-        hx0 = x0; hy0 = y0; hx1 = x1; hy1 = y1;
         r0 = make_float4(pix, piy, vz, __uint_as_float(tiles));
         r1 = make_float4(conx, cony, conz, in_opacity);
         r2 = make_float4(cr, cg, cb, __int_as_float(radius));
@@ -272,23 +254,6 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreArgs a, int* __r
         rec[3 * (size_t)idx + 2] = r2;
         if (clamped) clamped[idx] = cl;
     }
-    if (HIST) {
-        // exactly what load_rect + tile_hist_kernel made of the stored record (raster_binning.hip): the rectangle cut to this
-        // launch's tile rows, the reach parameters from the conic and the opacity
-        hy0 = max(hy0, a.ry0);
-        hy1 = min(hy1, a.ry1);
-        if (hy1 <= hy0 || radius <= 0) hx0 = hy0 = hx1 = hy1 = 0;
-        Reach rc = Reach{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0};
-        if (a.cull && radius > 0 && r1.x > 0.f && r1.z > 0.f)
-            rc = Reach{r0.x, r0.y, r1.x, r1.y, r1.z, mom_power_bound(r1.w), __builtin_amdgcn_rcpf(r1.x), __builtin_amdgcn_rcpf(r1.z), 1};
-        const uint64_t mask = decide_instances(hx0, hy0, hx1, hy1, a.gx, rc, [&](int tile) { atomicAdd(&s_cnt[tile], 1u); });
-        if (live) a.reach[idx] = mask;
-        __syncthreads();
-        for (int t = threadIdx.x; t < n_tiles; t += 256) {
-            const uint32_t n = s_cnt[t];
-            if (n) atomicAdd(&a.tile_counts[t], n);
-        }
-    }
 }
 
 __global__ void mark_visible_kernel(int P, const float* __restrict__ means, const float* __restrict__ view,
@@ -300,32 +265,20 @@ __global__ void mark_visible_kernel(int P, const float* __restrict__ means, cons
     present[idx] = vz <= 0.2f ? 0 : 1;
 }
 
-template <typename K>
-int set_lds_limit(K kernel)
-{
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024) != hipSuccess;
-}
-
 template <bool RAW>
-void launch_fwd(bool staged, bool hist, int blocks, size_t lds, hipStream_t s, const PreArgs& p, int* radii, float4* rec, float* cov,
-                uchar4* cl, uint32_t* zero_words, int n_zero, int sh_floats)
+void launch_fwd(bool staged, int blocks, size_t lds, hipStream_t s, const PreArgs& p, int* radii, float4* rec, float* cov, uchar4* cl,
+                uint32_t* zero_words, int n_zero, int sh_floats)
 {
-    if (hist && staged)
-        hipLaunchKernelGGL((preprocess_fwd_kernel<true, true, RAW>), dim3(blocks), dim3(256), lds, s, p, radii, rec, cov, cl, zero_words, n_zero, sh_floats);
-    else if (hist)
-        hipLaunchKernelGGL((preprocess_fwd_kernel<false, true, RAW>), dim3(blocks), dim3(256), lds, s, p, radii, rec, cov, cl, zero_words, n_zero, sh_floats);
-    else if (staged)
-        hipLaunchKernelGGL((preprocess_fwd_kernel<true, false, RAW>), dim3(blocks), dim3(256), lds, s, p, radii, rec, cov, cl, zero_words, n_zero, sh_floats);
+    if (staged)
+        hipLaunchKernelGGL((preprocess_fwd_kernel<true, RAW>), dim3(blocks), dim3(256), lds, s, p, radii, rec, cov, cl, zero_words, n_zero, sh_floats);
     else
-        hipLaunchKernelGGL((preprocess_fwd_kernel<false, false, RAW>), dim3(blocks), dim3(256), 0, s, p, radii, rec, cov, cl, zero_words, n_zero, sh_floats);
+        hipLaunchKernelGGL((preprocess_fwd_kernel<false, RAW>), dim3(blocks), dim3(256), 0, s, p, radii, rec, cov, cl, zero_words, n_zero, sh_floats);
 }
 
 }  // namespace
 
-// host launcher (called from raster_api.hip).  hist_counts / hist_reach non-null: the tile histogram rides in the projection kernel
-// (the caller has cleared the counters); *did_hist tells the binning whether it still has to run tile_hist_kernel.
-int mom_launch_preprocess_fwd(const MomRasterArgs* a, const GeomView& g, int* radii, uint32_t* zero_words, int n_zero,
-                              uint32_t* hist_counts, bool* did_hist, hipStream_t s)
+// host launcher (called from raster_api.hip)
+int mom_launch_preprocess_fwd(const MomRasterArgs* a, const GeomView& g, int* radii, uint32_t* zero_words, int n_zero, hipStream_t s)
 {
     PreArgs p;
     p.P = a->P; p.D = a->D; p.M = a->M; p.W = a->W; p.H = a->H;
@@ -338,39 +291,20 @@ int mom_launch_preprocess_fwd(const MomRasterArgs* a, const GeomView& g, int* ra
     p.focal_y = a->H / (2.0f * a->tan_fovy);
     p.focal_x = a->W / (2.0f * a->tan_fovx);
     p.view = a->viewmatrix; p.proj = a->projmatrix; p.cam = a->campos;
-    mom_tile_rows(a, p.gy, &p.ry0, &p.ry1);
-    p.cull = a->keep_all_tiles ? 0 : 1;
-    p.tile_counts = hist_counts;
-    p.reach = g.reach;
     const int blocks = (a->P + 255) / 256;
     // staged SH rows: DC and rest stored apart, colours from SH above degree 0, an odd row length, 16-byte aligned rows
     const int sh_stride = (a->M - 1) * 3;
     const bool staged = a->shs_rest && !a->colors_precomp && a->D > 0 && (sh_stride & 1) && sh_stride <= 45 &&
                         ((uintptr_t)a->shs_rest & 15) == 0;
-    const int tiles = p.gx * p.gy;
     const int sh_floats = staged ? 256 * sh_stride : 0;
-    // the histogram needs its counters in LDS beside the SH rows (45 KB): images up to 16 k tiles (e.g. 2048 x 2048)
-    const bool hist = hist_counts != nullptr && tiles <= kMaxLdsTiles && (size_t)(sh_floats + tiles) * 4 <= 64 * 1024 + 46 * 1024;
-    if (did_hist) *did_hist = hist;
-    const size_t lds = (size_t)(sh_floats + (hist ? tiles : 0)) * 4;
+    const size_t lds = (size_t)sh_floats * 4;
     MomProfScope ps(MOM_P_PRE_FWD, s);
     float* cov = a->forward_only ? nullptr : g.cov3D;
     uchar4* cl = a->forward_only ? nullptr : g.clamped;
-    if (hist) {
-        // the header and the tile counters: one fill command in front (this kernel adds into the counters itself)
-        if (hipMemsetAsync(zero_words, 0, (size_t)n_zero * 4, s) != hipSuccess) return MOM_ELAUNCH;
-        static bool attr_set = false;
-        if (!attr_set) {
-            if (set_lds_limit(preprocess_fwd_kernel<true, true, false>) || set_lds_limit(preprocess_fwd_kernel<false, true, false>) ||
-                set_lds_limit(preprocess_fwd_kernel<true, true, true>) || set_lds_limit(preprocess_fwd_kernel<false, true, true>))
-                return MOM_ELAUNCH;
-            attr_set = true;
-        }
-    }
     if (a->params_raw)
-        launch_fwd<true>(staged, hist, blocks, lds, s, p, radii, g.rec, cov, cl, zero_words, n_zero, sh_floats);
+        launch_fwd<true>(staged, blocks, lds, s, p, radii, g.rec, cov, cl, zero_words, n_zero, sh_floats);
     else
-        launch_fwd<false>(staged, hist, blocks, lds, s, p, radii, g.rec, cov, cl, zero_words, n_zero, sh_floats);
+        launch_fwd<false>(staged, blocks, lds, s, p, radii, g.rec, cov, cl, zero_words, n_zero, sh_floats);
     return hipGetLastError() == hipSuccess ? MOM_OK : MOM_ELAUNCH;
 }
 

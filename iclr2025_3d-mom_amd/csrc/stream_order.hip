@@ -4,7 +4,6 @@
 // path's host budget (tools/host_profile.py); a ctypes call into hipEventRecord + hipStreamWaitEvent costs about 1.5 us.
 #include "mom_common.h"
 #include <mutex>
-#include <stdlib.h>
 
 namespace {
 constexpr int kDevices = 64;
@@ -30,10 +29,8 @@ PerDevice* current_device()
 // without -- the fused step's main stream carries three per iteration.  MOM_EVENT_SYSTEM_FENCE=1 restores the default.
 unsigned mom_order_event_flags()
 {
-    static const unsigned flags = [] {
-        const char* e = getenv("MOM_EVENT_SYSTEM_FENCE");
-        return (unsigned)hipEventDisableTiming | ((e && e[0] == '1') ? 0u : (unsigned)hipEventDisableSystemFence);
-    }();
+    static const unsigned flags =
+        (unsigned)hipEventDisableTiming | (mom_env_int("MOM_EVENT_SYSTEM_FENCE", 0, 0, 1) ? 0u : (unsigned)hipEventDisableSystemFence);
     return flags;
 }
 

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os as _os
 
 import numpy as np
 import torch
@@ -157,10 +158,7 @@ def morton_order(xyz, stream=None, keepalive=None):
 
 
 # --------------------------------------------------------------------------- deformation field in one pass
-import os as _os
-
-FUSE_FIELD = _os.environ.get("MOM_FUSE_FIELD", "1") != "0"     # HexPlane lookup fused into the MLP kernels (csrc/deform_field.hip)
-FIELD_ORDER = _os.environ.get("MOM_FIELD_ORDER", "1") != "0"   # the fused kernels walk the Morton order (else the index order)
+FUSE_FIELD = True        # what field_forward does when its caller does not say (fused=None); no environment switch behind it
 _field_scratch = {}
 
 
@@ -175,17 +173,18 @@ def field_scratch(hp, device, P=0):
 
 
 def field_forward(hp, md, P, xyz, time, order, scal, rot, flow, coef, pts, sc_d, rot_d, feat, a0, opac, sc, rot_act, op, s,
-                  scratch_feat=None, scratch=None):
-    """deform_network.forward for one timestamp: the fused kernel when the field's shape allows it, else HexPlane + MLP.
+                  scratch_feat=None, scratch=None, fused=None):
+    """deform_network.forward for one timestamp: the fused kernel (csrc/deform_field.hip) when the field's shape allows it, else
+    HexPlane + MLP; fused=False: the two kernels in any case (the tests' comparison); None: the module's FUSE_FIELD.
     feat / a0: [P,64] tensors that receive the features and relu(h0) for the backward, or None (no backward follows; the
     two-kernel path then needs `scratch_feat` for the features).
     scratch: the caller's own field scratch (mom_deform_field_scratch_bytes) -- callers that keep several frames in flight on
     different streams must not share the per-device one (the time-line table and the feature buffer live for the whole launch)."""
     lib = N.lib()
     q = lambda t: None if t is None else t.data_ptr()
-    if FUSE_FIELD and lib.mom_deform_field_supported(C.byref(hp)):
+    if (FUSE_FIELD if fused is None else fused) and lib.mom_deform_field_supported(C.byref(hp)):
         N.check(lib.mom_deform_field_forward(C.byref(hp), C.byref(md), P, xyz.data_ptr(), float(time),
-                                             q(order) if FIELD_ORDER else None, scal.data_ptr(),
+                                             q(order), scal.data_ptr(),
                                              rot.data_ptr(), flow.data_ptr(), float(coef), pts.data_ptr(), sc_d.data_ptr(),
                                              rot_d.data_ptr(), q(feat), q(a0), q(opac), q(sc), q(rot_act), q(op),
                                              (scratch if scratch is not None else

@@ -458,19 +458,20 @@ int mom_deform_backward(const MomDeformMLP* w, int P, const float* feat, const f
 /* The same with a second stream at the callee's disposal.  Default form (one kernel on the bf16 matrix pipe, csrc/deform_bwd_b3.hip:
  * the pre-activation gradients never leave the CU): dfeat is complete on `stream`; the weight / bias gradients are complete on
  * `dw_stream` (the sum over the workgroups' partial sums runs there, ordered behind the kernel on `stream`).
- * Two-kernel form (MOM_MLP_BWD=split in the environment): dfeat and the thin output layers' gradients are complete on `stream`,
+ * Two-kernel f32 form (MOM_MLP_BWD=split in the environment; the tests' reference): dfeat and the thin output layers' gradients are complete on `stream`,
  * the 64x64 layers' weight / bias gradients on `dw_stream`, which the call orders behind the part on `stream` that produces their
  * input.  Either way the caller joins `dw_stream` before reading the gradients or reusing `scratch`.  dw_stream == stream:
- * identical to mom_deform_backward. */
+ * identical to mom_deform_backward.  These two are the forms there are: any other non-empty value of MOM_MLP_BWD than "b3" (the default)
+ * or "split" is MOM_EINVAL. */
 int mom_deform_backward_split(const MomDeformMLP* w, int P, const float* feat, const float* a0, const float* dpts,
                               const float* dscales, const float* drots, float* dfeat, void* scratch, mom_stream_t stream,
                               mom_stream_t dw_stream);
 
 /* ---- deformation field in one pass (the render() case: ONE timestamp for every point) ----
  * deform_network.forward = HexPlaneField lookup + trunk + heads (scene/deformation.py:97-153, scene/hexplane.py:160-183) as a
- * single persistent kernel: the 64 features of a tile of 32 Gaussians go from the texel gathers through LDS straight into the
- * matrix-core operand, feat[P,64] crosses HBM only if the caller asks for a copy (feat_save, for the backward's weight
- * gradients).  The three space-time planes are first collapsed to per-frame lines (one tiny launch into `scratch`,
+ * single persistent kernel: a wave gathers the 64 features of its tile of 32 Gaussians into their rows of feat[P,64] (feat_save,
+ * kept for the backward's weight gradients, or a buffer in `scratch`), reads them back in the matrix-core operand layout and runs
+ * the MLP on the bf16 pipe.  The three space-time planes are first collapsed to per-frame lines (one tiny launch into `scratch`,
  * mom_deform_field_scratch_bytes).  Same outputs and activated copies as mom_hexplane_forward + mom_deform_forward_activated;
  * `order` (optional) is the processing order as in mom_hexplane_forward.  Needs levels == 2, channels == 32 and resolutions
  * <= 1024 (mom_deform_field_supported); other shapes take the two separate calls. */

@@ -45,6 +45,22 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     assert lib.mom_profile_enable(99, 1) == N.MOM_EINVAL
 
 
+def test_an_unknown_mlp_backward_form_is_refused(monkeypatch):
+    """MOM_MLP_BWD selects the MLP backward's form per call (unset / "b3" / "split", csrc/deform_mlp.hip); any other value --
+    "fused" named a form that no longer exists -- is MOM_EINVAL before anything is launched, not a silent choice.  Every pointer
+    of the call and of the descriptor is non-null, so the environment value is the only thing there is to refuse (a value that
+    selected a form would get as far as the launch and fail there: MOM_ELAUNCH on a machine without a GPU)."""
+    import ctypes as C
+    lib, fake = N.lib(), 1 << 20          # a non-null pointer value; the calls are refused before it could be followed
+    w = N.MomDeformMLP()
+    for name, ctype in N.MomDeformMLP._fields_:
+        setattr(w, name, fake if ctype is C.c_void_p else ctype(fake, fake, fake))
+    for bad in ("fused", "f32", "Split", "b", "split "):
+        monkeypatch.setenv("MOM_MLP_BWD", bad)
+        assert lib.mom_deform_backward_split(C.byref(w), 32, fake, fake, fake, fake, fake, fake, fake, None, None) == N.MOM_EINVAL, bad
+        assert lib.mom_deform_backward(C.byref(w), 32, fake, fake, fake, fake, fake, fake, fake, None) == N.MOM_EINVAL, bad
+
+
 def test_abi_version_and_struct_sizes_are_checked_at_load():
     """mom_abi_version / mom_abi_sizeof (include/mom4d.h, "ABI versioning"): the binding refuses a library of another ABI."""
     import ctypes as C

@@ -52,13 +52,8 @@ def _run_forward(f, params, P, xyz, scal, rot, flow, opac, t, order, fused):
     md = ops.DeformMLPFunction._desc(params)
     e = lambda *sh: torch.full(sh, float("nan"), device="cuda")
     out = dict(pts=e(P, 3), sc_d=e(P, 3), rot_d=e(P, 4), feat=e(P, 64), a0=e(P, 64), sc=e(P, 3), rot=e(P, 4), op=e(P, 1))
-    old = ops.FUSE_FIELD
-    ops.FUSE_FIELD = fused
-    try:
-        ops.field_forward(hp, md, P, xyz, t, order, scal, rot, flow, 0.7, out["pts"], out["sc_d"], out["rot_d"], out["feat"],
-                          out["a0"], opac, out["sc"], out["rot"], out["op"], s)
-    finally:
-        ops.FUSE_FIELD = old
+    ops.field_forward(hp, md, P, xyz, t, order, scal, rot, flow, 0.7, out["pts"], out["sc_d"], out["rot_d"], out["feat"],
+                      out["a0"], opac, out["sc"], out["rot"], out["op"], s, fused=fused)
     torch.cuda.synchronize()
     return out
 

@@ -1,6 +1,6 @@
-"""Error of the three deformation-field forward paths against an fp64 evaluation of the same field and MLP on the same inputs:
-  two-kernel (hexplane_fwd4 + f32-MFMA MLP), one-kernel f32 (MOM_FIELD_MODE=f32), one-kernel bf16x3 (default).
-Run each mode in its own process (the library reads MOM_FIELD_MODE once):  python tools/field_accuracy.py [out.json]
+"""Error of the two deformation-field forward paths against an fp64 evaluation of the same field and MLP on the same inputs:
+  two-kernel (hexplane_fwd4 + f32-MFMA MLP), one-kernel bf16x3 (default).
+Each path runs in a process of its own:  python tools/field_accuracy.py [out.json]
 Prints / writes max and RMS errors of feat, a0, pts, scales, rots relative to the fp64 result's scale."""
 import importlib
 import json
@@ -45,9 +45,8 @@ if __name__ == "__main__":
         child(sys.argv[2])
         sys.exit(0)
     allres = {}
-    for mode, env in (("two-kernel", {}), ("one-kernel-f32", {"MOM_FIELD_MODE": "f32"}), ("one-kernel-bf16x3", {})):
-        e = dict(os.environ, **env)
-        p = subprocess.run([sys.executable, __file__, "--child", mode], env=e, capture_output=True, text=True)
+    for mode in ("two-kernel", "one-kernel-bf16x3"):
+        p = subprocess.run([sys.executable, __file__, "--child", mode], capture_output=True, text=True)
         line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
         if not line:
             print(p.stdout[-2000:], p.stderr[-2000:])

@@ -24,7 +24,7 @@ import sys
 SIMDS = 256 * 4
 P = 200_000
 # dx: three recomputed head layers + three W1^T + W0^T = seven 64x64 layers per Gaussian (the thin output layers run on the VALU)
-FLOP = {"deform_bwd_b3f_kernel": 0, "deform_bwd_b3g_kernel": 0, "deform_fwd_kernel": 34_048 * P, "deform_field_fwd_kernel": 34_048 * P, "deform_field_fwd_b3_kernel": 0, "deform_bwd_dx_kernel": 7 * 2 * 64 * 64 * P, "deform_bwd_dw_kernel": 4 * 2 * 64 * 64 * P}
+FLOP = {"deform_bwd_b3f_kernel": 0, "deform_bwd_b3g_kernel": 0, "deform_fwd_kernel": 34_048 * P, "deform_field_fwd_b3_kernel": 0, "deform_bwd_dx_kernel": 7 * 2 * 64 * 64 * P, "deform_bwd_dw_kernel": 4 * 2 * 64 * 64 * P}
 
 
 def main():
@@ -41,7 +41,7 @@ def main():
         if m:
             dur[m.group(1)].append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
     out = {}
-    for k in ("deform_fwd_kernel", "deform_field_fwd_kernel", "deform_field_fwd_b3_kernel", "deform_bwd_b3f_kernel", "deform_bwd_b3g_kernel", "deform_bwd_dx_kernel",
+    for k in ("deform_fwd_kernel", "deform_field_fwd_b3_kernel", "deform_bwd_b3f_kernel", "deform_bwd_b3g_kernel", "deform_bwd_dx_kernel",
               "deform_bwd_dw_kernel"):
         if k not in cnt:
             continue
