@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import raster_oracle as ro
-from scenes import camera, random_gaussians
+from scenes import POSES, camera, near_plane_scene, pose, random_gaussians, to_world, view_space
 
 
 def _fwd(s, **kw):
@@ -191,9 +191,15 @@ def _loss64(s, wc, wd, **over):
     return float((st.out_color * wc).sum() + (st.out_depth * wd).sum()), st
 
 
-def test_backward_matches_finite_differences_fp64():
+def test_backward_matches_finite_differences_fp64_under_a_general_pose():
+    test_backward_matches_finite_differences_fp64("general")
+
+
+def test_backward_matches_finite_differences_fp64(pose_name="identity"):
     """Analytic backward (backward.cu restated) vs central differences of the fp64 forward, away from the
-    reference's deliberate non-derivatives (0.99 cap: backward.cu:571; frustum clamp: :175-176)."""
+    reference's deliberate non-derivatives (0.99 cap: backward.cu:571; frustum clamp: :175-176).  Under `general` the same
+    camera-space scene is taken to world space and seen through the posed camera: the differences are then taken along the
+    WORLD axes, each of which moves all three view-space coordinates."""
     W, H, P = 40, 24, 24
     s = random_gaussians(P, seed=5, W=W, H=H, zrange=(2.0, 5.0), scale=(-2.6, -1.8))
     s["means3D"][:, 0] *= 0.7
@@ -201,6 +207,12 @@ def test_backward_matches_finite_differences_fp64():
     s["means3D"][:, 2] = np.abs(s["means3D"][:, 2]) + 1.5
     s["opacities"] = np.clip(s["opacities"], 0.05, 0.85)
     s = {k: (v.astype(np.float64) if isinstance(v, np.ndarray) and v.dtype == np.float32 else v) for k, v in s.items()}
+    if pose_name != "identity":
+        kp = pose(pose_name)
+        s["means3D"] = to_world(s["means3D"], **kp)
+        s.update(camera(W, H, dtype=np.float64, **kp))
+        pv = view_space(s["means3D"], s["viewmatrix"])
+        assert (pv[:, 2] > 1.0).all() and (np.abs(pv[:, 0] / pv[:, 2]) < 1.0 * s["tanfovx"]).all()
     rng = np.random.default_rng(0)
     wc = rng.normal(size=(3, H, W))
     wd = rng.normal(size=(1, H, W)) * 0.3
@@ -252,6 +264,89 @@ def test_mark_visible():
     s = random_gaussians(300, seed=4)
     vis = ro.mark_visible(s["means3D"], s["viewmatrix"], s["projmatrix"])
     assert np.array_equal(vis, s["means3D"][:, 2] > 0.2)
+
+
+@pytest.mark.parametrize("pose_name", ("identity",) + POSES)
+def test_mark_visible_under_a_pose(pose_name):
+    s, want = near_plane_scene(300, pose_name, seed=4)
+    assert 20 < want.sum() < 290
+    vis = ro.mark_visible(s["means3D"], s["viewmatrix"], s["projmatrix"])
+    assert np.array_equal(vis, want)
+
+
+def test_default_pose_draws_the_arrays_it_always_drew():
+    """random_gaussians() with the default pose against a verbatim copy of the function as it was before it took a pose: every
+    array bit for bit, so every scene of the identity-pose tests (and every gate measured on them) is what it was."""
+    import math
+
+    def old_projection_matrix(znear, zfar, fovx, fovy):
+        ty, tx = math.tan(fovy / 2), math.tan(fovx / 2)
+        top, right = ty * znear, tx * znear
+        P = np.zeros((4, 4), np.float32)
+        P[0, 0] = 2.0 * znear / (2 * right)
+        P[1, 1] = 2.0 * znear / (2 * top)
+        P[3, 2] = 1.0
+        P[2, 2] = zfar / (zfar - znear)
+        P[2, 3] = -(zfar * znear) / (zfar - znear)
+        return P
+
+    def old_camera(W, H, R=None, T=None, focal=None):
+        R = np.eye(3) if R is None else np.asarray(R, np.float64)
+        T = np.zeros(3) if T is None else np.asarray(T, np.float64)
+        focal = 582.69 if focal is None else focal  # train_motion.py:52-56 style intrinsics
+        fovx = 2 * math.atan(W / (2 * focal * W / H)) if False else 2 * math.atan(W / (2 * focal))
+        fovy = 2 * math.atan(H / (2 * focal))
+        Rt = np.zeros((4, 4))
+        Rt[:3, :3] = R.T
+        Rt[:3, 3] = T
+        Rt[3, 3] = 1.0
+        w2c = np.float32(Rt)
+        view = w2c.T.copy()
+        proj = old_projection_matrix(0.01, 100.0, fovx, fovy).T.copy()
+        full = (view @ proj).astype(np.float32)
+        campos = np.linalg.inv(view.astype(np.float64))[3, :3].astype(np.float32)
+        return dict(viewmatrix=view, projmatrix=full, campos=campos, tanfovx=math.tan(fovx * 0.5),
+                    tanfovy=math.tan(fovy * 0.5), W=W, H=H)
+
+    def old_random_gaussians(P, seed=0, W=128, H=96, zrange=(1.0, 6.0), scale=(-4.5, -2.0), sh_coeffs=16, focal=None):
+        rng = np.random.default_rng(seed)
+        cam = old_camera(W, H, focal=focal)
+        z = rng.uniform(*zrange, P)
+        # a few behind / at the near plane to exercise the cull (auxiliary.h:154)
+        n_near = max(1, P // 50)
+        z[:n_near] = rng.uniform(-1.0, 0.25, n_near)
+        x = rng.uniform(-1.3, 1.3, P) * cam["tanfovx"] * z
+        y = rng.uniform(-1.3, 1.3, P) * cam["tanfovy"] * z
+        means = np.stack([x, y, z], 1).astype(np.float32)
+        scales = np.exp(rng.uniform(scale[0], scale[1], (P, 3))).astype(np.float32)
+        rots = rng.normal(size=(P, 4)).astype(np.float32)
+        rots /= np.linalg.norm(rots, axis=1, keepdims=True)
+        opac = (1 / (1 + np.exp(-rng.normal(0, 2, (P, 1))))).astype(np.float32)
+        shs = (rng.normal(0, 0.3, (P, sh_coeffs, 3))).astype(np.float32)
+        shs[:, 0, :] += rng.uniform(0, 2.0, (P, 3)).astype(np.float32)
+        bg = np.array([0.1, 0.2, 0.3], np.float32)
+        return dict(means3D=means, scales=scales, rotations=rots, opacities=opac, shs=shs, bg=bg, **cam)
+
+    cases = [dict(P=1, seed=0), dict(P=64, seed=2, W=33, H=17), dict(P=5000, seed=1, W=256, H=256),
+             dict(P=700, seed=2, W=100, H=50, scale=(-3.0, -0.5)), dict(P=300, seed=9, zrange=(1.5, 6.0), sh_coeffs=4, focal=300.0)]
+    for kw in cases:
+        old, new = old_random_gaussians(**kw), random_gaussians(**kw)
+        assert old.keys() == new.keys()
+        for k, v in old.items():
+            if isinstance(v, np.ndarray):
+                assert v.dtype == new[k].dtype and v.shape == new[k].shape and v.tobytes() == new[k].tobytes(), (kw, k)
+            else:
+                assert v == new[k], (kw, k)
+        # the identity given explicitly takes the posed route and changes nothing either
+        ident = random_gaussians(R=np.eye(3), T=np.zeros(3), **kw)
+        for k, v in old.items():
+            if isinstance(v, np.ndarray):
+                assert v.tobytes() == ident[k].tobytes(), (kw, k, "explicit identity")
+    # and camera() under a pose is what it was, too
+    kp = pose("general")
+    a, b = old_camera(100, 50, kp["R"], kp["T"]), camera(100, 50, kp["R"], kp["T"])
+    for k, v in a.items():
+        assert (v.tobytes() == b[k].tobytes()) if isinstance(v, np.ndarray) else v == b[k], k
 
 
 def test_block_walk_counts_against_a_dense_numpy_statement():

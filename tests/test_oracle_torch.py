@@ -18,13 +18,19 @@ import torch
 
 from oracle import raster_oracle as ro
 from oracle import torch_raster as tr
-from scenes import camera, random_gaussians
+from scenes import camera, pose, posed_gaussians, quat_left, quat_of, random_gaussians, rigid_move, to_world, view_space
 
 
-def _scene(P, W, H, seed, max_opacity=0.999, spread=1.3, deg=3):
-    s = random_gaussians(P, seed=seed, W=W, H=H, zrange=(1.5, 6.0), scale=(-3.6, -1.6))
-    s["means3D"][:, 0] *= spread / 1.3
-    s["means3D"][:, 1] *= spread / 1.3
+ORACLE_POSES = ("identity", "yaw90", "general", "ref17")
+
+
+def _scene(P, W, H, seed, max_opacity=0.999, spread=1.3, deg=3, pose_name="identity"):
+    if pose_name == "identity":      # the identity scenes stay what they were: narrowed after the draw, in camera = world space
+        s = random_gaussians(P, seed=seed, W=W, H=H, zrange=(1.5, 6.0), scale=(-3.6, -1.6))
+        s["means3D"][:, 0] *= spread / 1.3
+        s["means3D"][:, 1] *= spread / 1.3
+    else:
+        s = posed_gaussians(P, pose_name, seed=seed, W=W, H=H, zrange=(1.5, 6.0), scale=(-3.6, -1.6), spread=spread)
     s["opacities"] = np.minimum(s["opacities"], max_opacity).astype(np.float32)
     s["sh_degree"] = deg
     return s
@@ -87,9 +93,20 @@ def _near_threshold_pixels(st, s, rel=1e-7):
     return bad
 
 
-@pytest.mark.parametrize("P,W,H,seed", [(200, 64, 64, 0), (150, 50, 37, 1), (64, 33, 17, 2)])
-def test_forward_agrees_with_the_c_oracle_fp64(P, W, H, seed):
-    s = _scene(P, W, H, seed)
+FORWARD_CASES = [(200, 64, 64, 0), (150, 50, 37, 1), (64, 33, 17, 2)]
+
+
+@pytest.mark.parametrize("pose_name", ORACLE_POSES[1:])
+@pytest.mark.parametrize("P,W,H,seed", FORWARD_CASES)
+def test_forward_agrees_with_the_c_oracle_fp64_under_a_pose(P, W, H, seed, pose_name):
+    test_forward_agrees_with_the_c_oracle_fp64(P, W, H, seed, pose_name)
+
+
+@pytest.mark.parametrize("P,W,H,seed", FORWARD_CASES)
+def test_forward_agrees_with_the_c_oracle_fp64(P, W, H, seed, pose_name="identity"):
+    """ref17: R17 of golden/g5_cameras.npz is the identity (every camera of the reference's fixture is), so it adds its
+    translation and its fovx == fovy on a non-square image; yaw90 and general carry the rotation."""
+    s = _scene(P, W, H, seed, pose_name=pose_name)
     st = _run_c(s, fp64=True)
     out, _, _ = _run_torch(s)
     assert np.array_equal(out["radii"].numpy(), st.radii)
@@ -116,10 +133,15 @@ def test_forward_agrees_with_the_c_oracle_fp64(P, W, H, seed):
     assert (st.final_T < 2e-4).any() or P < 100
 
 
-def test_forward_agrees_with_the_c_oracle_fp32_build():
+@pytest.mark.parametrize("pose_name", ORACLE_POSES[1:])
+def test_forward_agrees_with_the_c_oracle_fp32_build_under_a_pose(pose_name):
+    test_forward_agrees_with_the_c_oracle_fp32_build(pose_name)
+
+
+def test_forward_agrees_with_the_c_oracle_fp32_build(pose_name="identity"):
     """The fp32 build of the C oracle (the one the HIP kernels are compared with) against the fp64 torch statement: the same
     image to float32 rounding, integers equal away from the thresholds."""
-    s = _scene(200, 64, 64, 3)
+    s = _scene(200, 64, 64, 3, pose_name=pose_name)
     st = _run_c(s, fp64=False)
     out, _, _ = _run_torch(s)
     assert np.array_equal(out["radii"].numpy(), st.radii) and out["num_rendered"] == st.num_rendered
@@ -132,24 +154,41 @@ def test_forward_agrees_with_the_c_oracle_fp32_build():
     assert np.abs(col[:, ok] - st.out_color.reshape(3, -1)[:, ok]).mean() < 1e-6
 
 
-def _grad_scene(seed):
+# seeds for which no (pixel, splat) pair of the scene sits on a branch threshold (the test asserts it)
+GRAD_CASES = [("yaw90", 7), ("yaw90", 8), ("general", 7), ("general", 8), ("ref17", 7), ("ref17", 8)]
+
+
+def _grad_scene(seed, pose_name="identity"):
     """A scene inside the comparisons' domain of validity: opacities below the 0.99 cap, every Gaussian well inside the frustum
-    clamp (|x/z| < 1.3 tan(fov)), in front of the near plane."""
+    clamp (|x/z| < 1.3 tan(fov)), in front of the near plane -- all of it in VIEW space, where the reference tests it."""
     W, H, P = 48, 32, 60
-    s = _scene(P, W, H, seed, max_opacity=0.9, spread=0.85)
-    s["means3D"][:, 2] = np.abs(s["means3D"][:, 2]) + 1.2
-    s["means3D"][0] = [0.0, 0.0, 0.1]         # two Gaussians the near-plane test culls (auxiliary.h:154: z <= 0.2)
-    s["means3D"][1] = [0.01, 0.0, 0.2]
-    cam = camera(W, H)
+    s = _scene(P, W, H, seed, max_opacity=0.9, spread=0.85, pose_name=pose_name)
+    if pose_name == "identity":
+        pc = s["means3D"]
+    else:
+        pc = view_space(s["means3D"], s["viewmatrix"])
+    pc[:, 2] = np.abs(pc[:, 2]) + 1.2
+    pc[0] = [0.0, 0.0, 0.1]         # two Gaussians the near-plane test culls (auxiliary.h:154: z <= 0.2)
+    # on the threshold itself where the transform is exact; under a pose that rounds, clear of it by more than float32 rounding
+    pc[1] = [0.01, 0.0, 0.2 if pose_name == "identity" else 0.199]
+    if pose_name != "identity":
+        s["means3D"] = to_world(pc, **pose(pose_name)).astype(np.float32)
+    pv = view_space(s["means3D"], s["viewmatrix"])
     lim = 1.25
-    assert (np.abs(s["means3D"][:, 0] / s["means3D"][:, 2]) < lim * cam["tanfovx"]).all()
-    assert (np.abs(s["means3D"][:, 1] / s["means3D"][:, 2]) < lim * cam["tanfovy"]).all()
+    assert (np.abs(pv[:, 0] / pv[:, 2]) < lim * s["tanfovx"]).all()
+    assert (np.abs(pv[:, 1] / pv[:, 2]) < lim * s["tanfovy"]).all()
+    assert (pv[2:, 2] > 0.2).all() and (pv[:2, 2] < 0.2 + 1e-6).all()
     return s
 
 
+@pytest.mark.parametrize("pose_name,seed", GRAD_CASES)
+def test_autograd_of_the_torch_statement_equals_the_c_backward_under_a_pose(pose_name, seed):
+    test_autograd_of_the_torch_statement_equals_the_c_backward(seed, pose_name)
+
+
 @pytest.mark.parametrize("seed", [7, 8])
-def test_autograd_of_the_torch_statement_equals_the_c_backward(seed):
-    s = _grad_scene(seed)
+def test_autograd_of_the_torch_statement_equals_the_c_backward(seed, pose_name="identity"):
+    s = _grad_scene(seed, pose_name)
     s64 = {k: (v.astype(np.float64) if isinstance(v, np.ndarray) and v.dtype == np.float32 else v) for k, v in s.items()}
     W, H = s["W"], s["H"]
     rng = np.random.default_rng(seed)
@@ -180,19 +219,26 @@ def test_autograd_of_the_torch_statement_equals_the_c_backward(seed):
         assert np.abs(leaf[name].grad.numpy().reshape(g[gname].shape)[dead]).max() == 0 == np.abs(g[gname][dead]).max()
 
 
-def test_the_two_deliberate_non_derivatives_are_where_the_reference_puts_them():
+def test_the_two_deliberate_non_derivatives_are_in_view_space_under_a_general_pose():
+    test_the_two_deliberate_non_derivatives_are_where_the_reference_puts_them("general")
+
+
+def test_the_two_deliberate_non_derivatives_are_where_the_reference_puts_them(pose_name="identity"):
     """backward.cu:571: no derivative for the 0.99 cap (the capped pair still passes dL/dalpha to opacity and the conic);
     backward.cu:175-176: a mean outside 1.3 tan(fov) gets no covariance-path gradient through the clamped coordinate.  Autograd
-    of the exact forward differs from the C backward exactly there and nowhere else."""
+    of the exact forward differs from the C backward exactly there and nowhere else.  Under `general` the positions below are
+    VIEW-space positions taken to world space: the clamp's non-derivative sits where the view-space x / z passes the limit,
+    whatever the world-space x / z is."""
     W, H = 32, 32
-    cam = camera(W, H)
+    kp = pose(pose_name)
+    cam = camera(W, H, dtype=np.float64, **kp)
     base = dict(scales=np.full((1, 3), 0.08), rotations=np.array([[1.0, 0, 0, 0]]), shs=np.zeros((1, 16, 3)), sh_degree=0,
                 bg=np.zeros(3), **cam)
     base["shs"][0, 0] = 1.0
     wc = np.ones((3, H, W))
 
     def both(mean, opacity):
-        s = dict(base, means3D=np.array([mean], np.float64), opacities=np.array([[opacity]], np.float64))
+        s = dict(base, means3D=to_world(np.array([mean], np.float64), **kp), opacities=np.array([[opacity]], np.float64))
         st = _run_c(s, fp64=True)
         g = ro.backward(st, wc, None)
         out, leaf, _ = _run_torch(s, requires_grad=True)
@@ -207,9 +253,15 @@ def test_the_two_deliberate_non_derivatives_are_where_the_reference_puts_them():
     g, leaf = both([0.0, 0.0, 2.0], 0.9)
     np.testing.assert_allclose(leaf["opacities"].grad.numpy(), g["dL_dopacity"], rtol=1e-8)
     np.testing.assert_allclose(leaf["scales"].grad.numpy(), g["dL_dscales"], rtol=1e-7, atol=1e-12)
+    if pose_name != "identity":
+        # on the view axis, so inside the clamp -- while its WORLD x / z is far beyond 1.3 tan(fov): the mean's gradient is whole
+        m = to_world(np.array([[0.0, 0.0, 2.0]]), **kp)[0]
+        assert abs(m[0] / m[2]) > 2 * 1.3 * cam["tanfovx"]
+        np.testing.assert_allclose(leaf["means3D"].grad.numpy(), g["dL_dmeans3D"], rtol=1e-7,
+                                   atol=1e-9 * np.abs(g["dL_dmeans3D"]).max())
     # (2) a splat beyond the frustum clamp (x/z > 1.3 tan(fov)), large enough to still reach the image
     x = 1.45 * cam["tanfovx"] * 2.0
-    s = dict(base, scales=np.full((1, 3), 0.35), means3D=np.array([[x, 0.0, 2.0]]), opacities=np.array([[0.8]]))
+    s = dict(base, scales=np.full((1, 3), 0.35), means3D=to_world(np.array([[x, 0.0, 2.0]]), **kp), opacities=np.array([[0.8]]))
     st = _run_c(s, fp64=True)
     assert st.radii[0] > 0 and (st.n_contrib > 0).any()
     g = ro.backward(st, wc, None)
@@ -218,3 +270,69 @@ def test_the_two_deliberate_non_derivatives_are_where_the_reference_puts_them():
     np.testing.assert_allclose(out["color"].detach().numpy(), st.out_color, rtol=1e-10, atol=1e-13)     # forward: equal
     np.testing.assert_allclose(leaf["opacities"].grad.numpy(), g["dL_dopacity"], rtol=1e-8)               # untouched paths: equal
     assert np.abs(leaf["means3D"].grad.numpy() - g["dL_dmeans3D"]).max() > 1e-6 * np.abs(g["dL_dmeans3D"]).max()
+    # ... and it differs along the view-space z only.  The forward's clamped coordinate is t.x = +-lim * t.z: its derivative by
+    # the view-space x is 0, which is the reference's gradient multiplier of 0 and autograd's clamp alike, so the view-space x
+    # (and the unclamped y) component of dL/dmean is the same in both; the reference drops d(t.x)/d(t.z) = +-lim, autograd keeps it.
+    V = np.asarray(cam["viewmatrix"], np.float64)[:3, :3]
+    ga, gc = leaf["means3D"].grad.numpy() @ V, g["dL_dmeans3D"] @ V
+    scale = np.abs(gc).max()
+    assert abs(gc[0, 0]) > 1e-3 * scale                                # (the pixel-position path still moves with x)
+    np.testing.assert_allclose(ga[:, :2], gc[:, :2], rtol=1e-7, atol=1e-9 * scale)
+    assert abs(ga[0, 2] - gc[0, 2]) > 1e-6 * scale
+
+
+def _weights(seed, W, H):
+    rng = np.random.default_rng(seed)
+    return rng.normal(size=(3, H, W)), rng.normal(size=(1, H, W)) * 0.3
+
+
+@pytest.mark.parametrize("pose_name", ["yaw90", "general"])
+@pytest.mark.parametrize("P,W,H,seed", [(200, 64, 64, 0), (150, 50, 37, 1)])
+def test_rigid_motion_of_scene_and_camera_leaves_the_frame_and_turns_the_gradients(P, W, H, seed, pose_name):
+    """A check of the C oracle under rotation that trusts neither statement of it there.  Scene and camera moved together by a
+    rigid motion G = (R, T) (scenes.rigid_move: means to R (p - T), quaternions left-multiplied by the quaternion of R, SH degree
+    0) give the identity-pose frame, and the identity-pose frame is pinned to the reference.  In the fp64 build: radii, tiles,
+    lists and n_contrib equal; colour, depth and final_T within 1e-10 relative away from threshold pixels; the gradients
+    covariant: dL/dmean' = R dL/dmean, dL/dscale, dL/dopacity, dL/dsh equal, dL/dq' = L(q_R) dL/dq, within the 1e-7 of the
+    autograd comparison.  The scene is drawn out to 1.6 tan(fov), so both branches of the frustum clamp are in it.
+
+    The quaternions are normalised in float64 first and dL/dq is compared in the plane orthogonal to q: the reference builds
+    its rotation matrix from the quaternion as given, M(q) = N(q) + (1 - |q|^2) I with N homogeneous of degree 2, and only N
+    turns with q_R (N(q_R q) = R N(q)); the last term's derivative, along q itself, stays put.  On unit quaternions the values
+    agree and the gradients agree off that one direction."""
+    s0 = _scene(P, W, H, seed, deg=0, spread=1.6)
+    s0 = {k: (v.astype(np.float64) if isinstance(v, np.ndarray) and v.dtype == np.float32 else v) for k, v in s0.items()}
+    s0["rotations"] /= np.linalg.norm(s0["rotations"], axis=1, keepdims=True)
+    kp = pose(pose_name)
+    R, T = kp["R"], kp["T"]
+    s1 = rigid_move(s0, R, T, dtype=np.float64)
+    np.testing.assert_allclose(tr.quaternion_matrix(torch.tensor(quat_of(R)[None]))[0].numpy(), R, rtol=0, atol=1e-15)
+    np.testing.assert_allclose(view_space(s1["means3D"], s1["viewmatrix"]), s0["means3D"], rtol=0, atol=1e-14)
+    st0, st1 = _run_c(s0, fp64=True), _run_c(s1, fp64=True)
+    assert st0.num_rendered > 0 and (st0.n_contrib > 0).mean() > 0.3
+    near = _near_threshold_pixels(st0, s0, rel=1e-9)
+    assert not near.any(), "pick another seed: a pair sits on a branch threshold"
+    for k in ("radii", "tiles_touched", "ranges", "point_list", "n_contrib", "clamped"):
+        assert np.array_equal(st0[k], st1[k]), k
+    np.testing.assert_allclose(st1.out_color, st0.out_color, rtol=1e-10, atol=1e-12)
+    np.testing.assert_allclose(st1.out_depth, st0.out_depth, rtol=1e-10, atol=1e-12)
+    np.testing.assert_allclose(st1.final_T, st0.final_T, rtol=1e-10, atol=1e-14)
+    wc, wd = _weights(seed, W, H)
+    g0, g1 = ro.backward(st0, wc, wd), ro.backward(st1, wc, wd)
+
+    def close(a, b, name):
+        scale = np.abs(b).max()
+        assert scale > 0, name
+        np.testing.assert_allclose(a, b, rtol=1e-7, atol=1e-9 * scale, err_msg=name)
+
+    close(g1["dL_dmeans3D"], g0["dL_dmeans3D"] @ R.T, "means3D")
+    for k in ("dL_dscales", "dL_dopacity", "dL_dsh", "dL_dmeans2D"):
+        close(g1[k], g0[k], k)
+    want = g0["dL_drotations"] @ quat_left(quat_of(R)).T
+    q1 = s1["rotations"]
+    tangent = lambda g: g - (g * q1).sum(1, keepdims=True) * q1
+    close(tangent(g1["dL_drotations"]), tangent(want), "rotations")
+    # the clamp branch is in the comparison: some visible Gaussians lie beyond 1.3 tan(fov) in view space
+    vis = st0.radii > 0
+    for ax, lim in ((0, s0["tanfovx"]), (1, s0["tanfovy"])):
+        assert (np.abs(s0["means3D"][vis, ax] / s0["means3D"][vis, 2]) > 1.31 * lim).sum() >= 5

@@ -7,7 +7,8 @@ import pytest
 import torch
 
 from oracle import raster_oracle as ro
-from scenes import camera, clamp_some_channels, random_gaussians
+from scenes import (POSES, camera, clamp_some_channels, near_plane_scene, pose, posed_gaussians, quat_left, quat_of, random_gaussians,
+                    rigid_move, to_world, view_space)
 
 pytestmark = pytest.mark.gpu
 
@@ -692,3 +693,176 @@ def test_tile_sort_inside_the_compositing_forward_changes_nothing(seed, P, W, H,
         assert n.max() > 1536 > n[n > 0].min(), (n.min(), n.max())
     for k in ("ranges", "point_list", "color", "depth", "final_T", "n_contrib", "radii"):
         np.testing.assert_array_equal(a[k], b[k])
+
+
+# ---- under rotated and translated cameras (scenes.pose): every test above sees the identity view matrix and campos = 0, under
+# which a transposed view index, a forgotten translation, mean - campos against the mean, and a contracted dot product all give
+# the same numbers.  Same helpers, same gates.
+# Measured on an MI355X (tools/parity_stats.py posed; every pose, both binnings, the mid-size and the beyond-the-clamp cases):
+# image mean L1 4.6e-9 .. 3.6e-8 (gate 1e-6), max 2.3e-5 with at most 1 pixel above 1e-5 (a counted threshold exception),
+# n_contrib and last contributors identical, final_T mean within 6.1e-11; gradient norms within 1.2e-5 (gate 5e-5), no row
+# above 2e-5 of its tensor's scale, worst row 1.4e-5.
+
+ALL_POSES = ("identity",) + POSES
+
+
+@pytest.mark.parametrize("pose_name", POSES)
+@pytest.mark.parametrize("seed,P,W,H,kw", [
+    (201, 5000, 256, 256, {}),
+    (202, 700, 100, 50, dict(scale=(-3.0, -0.5))),   # ragged image, large splats
+])
+def test_forward_parity_under_a_pose(seed, P, W, H, kw, pose_name):
+    """Both binnings against one oracle frame.  ref17 is the reference's own camera 17 (golden/g5_cameras.npz): its R is the
+    identity, it brings a translation and fovx == fovy on a non-square image; yaw90 and general carry the rotation."""
+    from hip_helpers import hip_forward
+    ro.set_threads(1)
+    s = posed_gaussians(P, pose_name, seed=seed, W=W, H=H, **kw)
+    st = _oracle(s)
+    assert (st.radii > 0).sum() > P // 2
+    for keep_all_tiles in (True, False):
+        _cmp_forward(hip_forward(s, keep_all_tiles=keep_all_tiles), st, P)
+
+
+def test_forward_parity_mid_size_under_a_general_pose():
+    from hip_helpers import hip_forward
+    ro.set_threads(16)
+    P = 100000
+    s = posed_gaussians(P, "general", seed=207, W=480, H=270, scale=(-5.5, -3.5))
+    st = _oracle(s)
+    for keep_all_tiles in (True, False):
+        _cmp_forward(hip_forward(s, keep_all_tiles=keep_all_tiles), st, P)
+
+
+@pytest.mark.parametrize("pose_name", POSES)
+@pytest.mark.parametrize("seed,P,W,H,kw", [(210, 1500, 128, 96, {}), (212, 5000, 256, 256, dict(scale=(-5.0, -3.0)))])
+def test_backward_parity_under_a_pose(seed, P, W, H, kw, pose_name):
+    """All eight gradient tensors, nonzero depth gradient, degree 3; the SH backward against float64 with the pose's campos."""
+    ro.set_threads(1)
+    s = posed_gaussians(P, pose_name, seed=seed, W=W, H=H, **kw)
+    fw, st, g, go = _backward_case(s, seed, {}, {})
+    assert float(np.abs(go["dL_ddepths"]).max()) > 0
+    _check_sh_fp64(3, g["dL_dsh"], s["shs"], s["means3D"], s["campos"], g["dL_dcolors"], fw["clamped"], fw["radii"], pose_name)
+
+
+@pytest.mark.parametrize("deg,seed", [(0, 220), (1, 225), (2, 222), (3, 223)])
+def test_backward_parity_at_every_sh_degree_under_a_general_pose(deg, seed):
+    s = posed_gaussians(1500, "general", seed=seed, W=128, H=96)
+    assert float(np.abs(s["campos"]).min()) > 0.1
+    kw = dict(sh_degree=deg)
+    fw, st, g, go = _backward_case(s, seed, kw, kw)
+    _check_sh_fp64(deg, g["dL_dsh"], s["shs"], s["means3D"], s["campos"], g["dL_dcolors"], fw["clamped"], fw["radii"], "general")
+
+
+def test_backward_parity_precomputed_colors_under_a_general_pose():
+    s = posed_gaussians(1200, "general", seed=230, W=96, H=64)
+    cols = np.random.default_rng(230).uniform(0, 1, (1200, 3)).astype(np.float32)
+    names = tuple(n for n in GRAD_NAMES if n != "dL_dsh")
+    fw, st, g, go = _backward_case(s, 230, dict(colors_precomp=cols), dict(shs=None, colors_precomp=cols), names, feat=cols)
+    assert float(np.abs(g["dL_dcolors"]).max()) > 0
+    assert g["dL_dsh"].size == 0 or not g["dL_dsh"].any()
+
+
+def test_backward_parity_precomputed_cov3d_under_a_general_pose():
+    s = posed_gaussians(1200, "general", seed=231, W=96, H=64)
+    cov = _oracle(s).cov3D
+    names = tuple(n for n in GRAD_NAMES if n not in ("dL_dscales", "dL_drotations"))
+    fw, st, g, go = _backward_case(s, 231, dict(cov3D_precomp=cov), dict(scales=None, rotations=None, cov3D_precomp=cov), names)
+    assert float(np.abs(g["dL_dcov3D"]).max()) > 0
+    for n in ("dL_dscales", "dL_drotations"):
+        assert g[n].size == 0 or not g[n].any(), n
+    _check_sh_fp64(3, g["dL_dsh"], s["shs"], s["means3D"], s["campos"], g["dL_dcolors"], fw["clamped"], fw["radii"], "cov3D")
+
+
+def clamp_census(s, st, margin=1e-5):
+    """Of the oracle's visible Gaussians, the fractions beyond the frustum clamp of computeCov2D (|t.x / t.z| > 1.3f tan(fovx/2),
+    and the same in y), read off the oracle's own state: its pixel centre is ndc2Pix of t.x / (t.z tan(fovx/2)), so beyond the
+    clamp is |ndc| > 1.3.  Asserts from float64 view-space coordinates that no visible Gaussian is within `margin` (relative) of
+    the limit -- where a float32 evaluation may take the other branch of the hard threshold -- and, with that, that the float64
+    coordinates sort every visible Gaussian to the same side as the oracle's state does."""
+    vis = st.radii > 0
+    pv = view_space(s["means3D"], s["viewmatrix"])[vis]
+    out = []
+    for ax, tanfov, size in ((0, s["tanfovx"], s["W"]), (1, s["tanfovy"], s["H"])):
+        lim = float(np.float32(1.3)) * tanfov
+        r = np.abs(pv[:, ax] / pv[:, 2])
+        assert (np.abs(r - lim) > margin * lim).all(), ("pick another seed: a Gaussian sits on the clamp limit", ax)
+        ndc = (2.0 * st.means2D[vis, ax].astype(np.float64) + 1.0) / size - 1.0
+        beyond = np.abs(ndc) > 1.3
+        settled = np.abs(np.abs(ndc) - 1.3) > 1e-4        # (the pixel centre is a float32 of magnitude ~100: ndc to ~1e-7)
+        np.testing.assert_array_equal(beyond[settled], (r > lim)[settled])
+        out.append(float(beyond.mean()))
+    return out
+
+
+@pytest.mark.parametrize("pose_name,seed", [("identity", 242), ("general", 241)])
+def test_parity_beyond_the_frustum_clamp(pose_name, seed):
+    """Gaussians drawn out to 2.0 tan(fov) and large enough to reach the image from there: the clamped coordinate in the forward's
+    Jacobian and the zero gradient multiplier of the backward (computeCov2D, forward.cu:86-90 / backward.cu:171-176), which
+    random_gaussians' default spread of exactly 1.3 never takes."""
+    from hip_helpers import hip_forward
+    P, W, H = 1500, 128, 96
+    s = posed_gaussians(P, pose_name, seed=seed, W=W, H=H, spread=2.0, scale=(-3.0, -0.5))
+    fw, st, g, go = _backward_case(s, seed, {}, {})
+    fx, fy = clamp_census(s, st)
+    assert fx >= 0.05 and fy >= 0.05, (fx, fy)
+    _cmp_forward(hip_forward(s, keep_all_tiles=True), st, P)
+
+
+@pytest.mark.parametrize("seed,P,W,H", [(250, 1500, 128, 96)])
+def test_rigid_motion_of_scene_and_camera_on_the_hip_path(seed, P, W, H):
+    """scenes.rigid_move at SH degree 0: the identity-pose scene, and the same scene moved together with its camera by the
+    `general` pose, are one frame (tests/test_oracle_torch.py shows it for the oracle in float64).  Here the moved inputs are
+    rounded to float32, so the two HIP frames are compared at the image and gradient gates, the integers up to the counted
+    exceptions, and the gradients after turning them back: dL/dmean = R^T dL/dmean', dL/dq = L(q_R)^T dL/dq' in the plane
+    orthogonal to q (the reference uses q unnormalised; the derivative along q does not turn, see the oracle test)."""
+    from hip_helpers import hip_backward, hip_forward
+    s0 = random_gaussians(P, seed=seed, W=W, H=H)
+    kp = pose("general")
+    s1 = rigid_move(s0, kp["R"], kp["T"])
+    rng = np.random.default_rng(seed)
+    dcol = rng.normal(size=(3, H, W)).astype(np.float32)
+    ddep = (rng.normal(size=(1, H, W)) * 0.2).astype(np.float32)
+    st0 = _oracle(s0, sh_degree=0)
+    fw0, fw1 = hip_forward(s0, sh_degree=0), hip_forward(s1, sh_degree=0)
+    _cmp_forward(fw0, st0, P)
+    for k in ("radii", "tiles_touched"):
+        assert int((fw0[k] != fw1[k]).sum()) <= _allowed(P), k
+    # every pixel's last contributor (a position in a culled list means nothing across two frames; the Gaussian it names does)
+    bad = np.nonzero(_last_contributor(fw0["n_contrib"], fw0["ranges"], fw0["point_list"], W, H)
+                     != _last_contributor(fw1["n_contrib"], fw1["ranges"], fw1["point_list"], W, H))[0]
+    assert len(bad) <= _allowed(W * H), len(bad)
+    for p in bad:
+        assert _near_threshold(st0, int(p % W), int(p // W), W), ("last contributor differs without a threshold pair", p)
+    _assert_image(fw1["color"], fw0["color"], st0, "color")
+    dscale = max(1.0, float(st0.depths.max()))
+    _assert_image(fw1["depth"] / dscale, fw0["depth"] / dscale, st0, "depth")
+    g0, g1 = hip_backward(fw0, dcol, ddep), hip_backward(fw1, dcol, ddep)
+    back = dict(g1)
+    back["dL_dmeans3D"] = (g1["dL_dmeans3D"].astype(np.float64) @ kp["R"]).astype(np.float32)
+    q0 = s0["rotations"].astype(np.float64)
+    tangent = lambda g: g - (g * q0).sum(1, keepdims=True) * q0
+    back["dL_drotations"] = tangent(g1["dL_drotations"].astype(np.float64) @ quat_left(quat_of(kp["R"]))).astype(np.float32)
+    ref = dict(g0)
+    ref["dL_drotations"] = tangent(g0["dL_drotations"].astype(np.float64))
+    names = tuple(n for n in GRAD_NAMES if n != "dL_dcov3D")        # (a symmetric tensor: it turns as R . R^T; dL/dscale and dL/dq carry it)
+    _cmp_grads(back, ref, st0, names, what="rigid")
+
+
+@pytest.mark.parametrize("P", [1, 63, 64, 65, 20011])
+@pytest.mark.parametrize("pose_name", ALL_POSES)
+def test_mark_visible_against_the_oracle(pose_name, P):
+    """mom_mark_visible through the `_C` boundary: whole and partial workgroups, a quarter of the means within 1e-4 .. 1e-2 of
+    the 0.2 cull on either side of it."""
+    from hip_helpers import RC, t
+    s, want = near_plane_scene(P, pose_name, seed=260 + P)
+    if P == 1:       # near_plane_scene's first Gaussian is behind the camera: put the lone one in front, then behind
+        for z, seen in ((0.21, True), (0.19, False)):
+            m = to_world(np.array([[0.01, -0.02, z]]), **pose(pose_name)).astype(np.float32)
+            got = RC.mark_visible(t(m), t(s["viewmatrix"]), t(s["projmatrix"])).cpu().numpy()
+            assert got.dtype == np.bool_ and got.tolist() == [seen] == ro.mark_visible(m, s["viewmatrix"], s["projmatrix"]).tolist()
+        return
+    got = RC.mark_visible(t(s["means3D"]), t(s["viewmatrix"]), t(s["projmatrix"])).cpu().numpy()
+    assert got.dtype == np.bool_
+    np.testing.assert_array_equal(got, ro.mark_visible(s["means3D"], s["viewmatrix"], s["projmatrix"]))
+    np.testing.assert_array_equal(got, want)
+    assert 0 < want.sum() < P

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from oracle import raster_oracle as ro
-from scenes import clamp_some_channels, random_gaussians
+from scenes import clamp_some_channels, posed_gaussians
 from test_raster_gpu import DIR_SUM_TOL, DIR_TOL, _check_sh_fp64, _cmp_forward, _cmp_grads
 
 pytestmark = pytest.mark.gpu
@@ -28,11 +28,11 @@ def _mods():
     return importlib.import_module("iclr2025_3d-mom_amd._native"), importlib.import_module("iclr2025_3d-mom_amd.ops")
 
 
-def _scene(P, seed):
+def _scene(P, seed, pose_name="identity"):
     """Seeded Gaussians (some with a clamped channel) as raw parameters (log scale, an unnormalised quaternion, logit opacity)
     and as the activations mom_activations_forward makes of them -- the bits the raw projection computes in registers."""
     N, _ = _mods()
-    s = random_gaussians(P, seed=seed, W=160, H=96)
+    s = posed_gaussians(P, pose_name, seed=seed, W=160, H=96)
     if P < 50:      # random_gaussians puts its first max(1, P // 50) Gaussians behind the camera: keep a lone one in view
         s["means3D"][:] = np.array([0.05, -0.04, 2.0], np.float32)
         s["scales"][:] = np.array([0.03, 0.015, 0.05], np.float32)      # anisotropic: its rotation gradient is not rounding noise
@@ -161,7 +161,20 @@ def _bits(x):
 @pytest.mark.parametrize("D", [0, 1, 2, 3])
 def test_training_layouts_against_the_oracle(D, params_raw, P):
     """P = 1: one partial workgroup; 200: one partial workgroup of many; 6000: 23 whole workgroups and a partial tail."""
-    s, raw, dcol, ddep = _scene(P, seed=100 + P + D)
+    _layouts_case(D, params_raw, P, 100 + P + D, "identity")
+
+
+@pytest.mark.parametrize("P", [200, 6000])
+@pytest.mark.parametrize("params_raw", [0, 1])
+@pytest.mark.parametrize("D", [0, 1, 2, 3])
+def test_training_layouts_against_the_oracle_under_a_general_pose(D, params_raw, P):
+    """The split DC / rest layout and the raw-parameter projection with a rotated view and campos = (-1.8, -0.7, -1.6): the view
+    direction is mean - campos, neither the mean nor the view-space mean."""
+    _layouts_case(D, params_raw, P, 300 + P + D, "general")
+
+
+def _layouts_case(D, params_raw, P, seed, pose_name):
+    s, raw, dcol, ddep = _scene(P, seed, pose_name)
     runs = _frames(s, raw, dcol, ddep, D, params_raw)
     fw, g, dmean0 = runs["staged"]
     assert (fw["radii"] > 0).sum() >= min(P, 50)
