@@ -60,6 +60,17 @@ class MomRasterGrads(C.Structure):
                                           "stats_max_radii2D", "stats_grad_accum", "stats_denom", "stats_skip_if_nonzero")]
 
 
+class MomRasterAccum(C.Structure):
+    # what mom_raster_backward_acc / _geometry_acc take beside MomRasterGrads (a batch of cameras on one GPU: the later cameras ADD)
+    _fields_ = [("struct_size", C.c_uint),                          # sizeof(MomRasterAccum): set by __init__, checked by both entry points
+                ("dL_dmeans3D_copy", C.c_void_p),                   # this call's own dL_dmeans3D, plain stores (or null)
+                ("radii_max", C.c_void_p)]                          # radii_max[i] = max(radii_max[i], radii[i]) (or null)
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(type(self))
+
+
 class MomRasterLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in ("geom_rec", "geom_cov3D", "geom_clamped", "geom_gacc", "img_ranges",
                                           "img_n_contrib", "img_final_T", "img_tile_counts", "bin_keys",
@@ -164,6 +175,10 @@ def _sig(lib):
     lib.mom_raster_backward.argtypes = [C.POINTER(MomRasterArgs), vp, vp, vp, sz, vp, vp, vp, C.POINTER(MomRasterGrads), vp]
     lib.mom_raster_backward_render.argtypes = [C.POINTER(MomRasterArgs), vp, vp, sz, vp, vp, vp, vp]
     lib.mom_raster_backward_geometry.argtypes = [C.POINTER(MomRasterArgs), vp, vp, C.POINTER(MomRasterGrads), vp]
+    lib.mom_raster_backward_acc.argtypes = [C.POINTER(MomRasterArgs), vp, vp, vp, sz, vp, vp, vp, C.POINTER(MomRasterGrads),
+                                            C.POINTER(MomRasterAccum), vp]
+    lib.mom_raster_backward_geometry_acc.argtypes = [C.POINTER(MomRasterArgs), vp, vp, C.POINTER(MomRasterGrads),
+                                                     C.POINTER(MomRasterAccum), vp]
     lib.mom_mark_visible.argtypes = [i32, vp, vp, vp, vp, vp]
     lib.mom_selftest_wave_sum.argtypes = [vp, vp, i32, vp]
     lib.mom_selftest_row_reduce.argtypes = [vp, vp, i32, i32, vp]
@@ -244,6 +259,7 @@ EXPORTS = [
     "mom_comm_available", "mom_comm_last_error", "mom_comm_unique_id", "mom_comm_create", "mom_comm_destroy", "mom_comm_abort",
     "mom_comm_world", "mom_comm_rank", "mom_comm_group_start", "mom_comm_group_end", "mom_comm_all_reduce", "mom_comm_all_gather",
     "mom_comm_reduce_scatter",
+    "mom_raster_backward_acc", "mom_raster_backward_geometry_acc",
 ]
 
 
@@ -255,7 +271,8 @@ def _abi_structs():
     return [("MOM_STRUCT_RASTER_ARGS", MomRasterArgs), ("MOM_STRUCT_RASTER_GRADS", MomRasterGrads),
             ("MOM_STRUCT_RASTER_LAYOUT", MomRasterLayout), ("MOM_STRUCT_HEXPLANE", MomHexPlane),
             ("MOM_STRUCT_ADAM_TENSOR", MomAdamTensor), ("MOM_STRUCT_ROW_SELECT", MomRowSelect),
-            ("MOM_STRUCT_REG_PLANE", MomRegPlane), ("MOM_STRUCT_DEFORM_MLP", MomDeformMLP)]
+            ("MOM_STRUCT_REG_PLANE", MomRegPlane), ("MOM_STRUCT_DEFORM_MLP", MomDeformMLP),
+            ("MOM_STRUCT_RASTER_ACCUM", MomRasterAccum)]
 
 
 _CTYPE_NAMES = {C.c_int: "C.c_int", C.c_uint: "C.c_uint", C.c_float: "C.c_float", C.c_void_p: "C.c_void_p",

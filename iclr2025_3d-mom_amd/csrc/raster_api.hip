@@ -11,7 +11,8 @@ int mom_launch_render_fwd(const MomRasterArgs* a, const GeomView& g, const BinVi
                           float* out_color, float* out_depth, bool sort_small, hipStream_t s);
 int mom_launch_render_bwd(const MomRasterArgs* a, const GeomView& g, const BinView& b, const ImageView& im, size_t capacity,
                           const float* dL_dpix, const float* dL_ddepth, hipStream_t s);
-int mom_launch_preprocess_bwd(const MomRasterArgs* a, const int* radii, const GeomView& g, const MomRasterGrads* gr, hipStream_t s);
+int mom_launch_preprocess_bwd(const MomRasterArgs* a, const int* radii, const GeomView& g, const MomRasterGrads* gr, const MomRasterAccum* acc,
+                              hipStream_t s);
 
 static int check_args(const MomRasterArgs* a)
 {
@@ -42,6 +43,13 @@ static int check_grads(const MomRasterArgs* a, const MomRasterGrads* gr)
     return MOM_OK;
 }
 
+static int check_accum(const MomRasterArgs* a, const MomRasterAccum* acc)
+{
+    if (!acc || acc->struct_size != sizeof(MomRasterAccum)) return MOM_EINVAL;
+    if (a->tile_row0 != 0 || a->tile_row1 != 0) return MOM_EINVAL;          // a tile-row shard of a batch: not supported
+    return MOM_OK;
+}
+
 extern "C" {
 
 #ifndef MOM_SRC_HASH
@@ -60,6 +68,7 @@ size_t mom_abi_sizeof(int which)
     case MOM_STRUCT_ROW_SELECT: return sizeof(MomRowSelect);
     case MOM_STRUCT_REG_PLANE: return sizeof(MomRegPlane);
     case MOM_STRUCT_DEFORM_MLP: return sizeof(MomDeformMLP);
+    case MOM_STRUCT_RASTER_ACCUM: return sizeof(MomRasterAccum);
     default: return 0;
     }
 }
@@ -181,10 +190,47 @@ int mom_raster_backward_geometry(const MomRasterArgs* a, const int* radii, void*
     if (rc) return rc;
     GeomView g;
     geom_view(mom_align_ptr(geom), a->P, &g);
-    rc = mom_launch_preprocess_bwd(a, radii, g, gr, s);
+    rc = mom_launch_preprocess_bwd(a, radii, g, gr, nullptr, s);
     if (rc) return rc;
     MOM_CHECK_LAUNCH(a, s);
     return MOM_OK;
+}
+
+int mom_raster_backward_geometry_acc(const MomRasterArgs* a, const int* radii, void* geom, const MomRasterGrads* gr,
+                                     const MomRasterAccum* acc, mom_stream_t stream)
+{
+    int rc = check_args(a);
+    if (rc) return rc;
+    rc = check_accum(a, acc);                   // (P == 0 as well: the struct describes the call, not the data)
+    if (rc) return rc;
+    if (a->P == 0) return MOM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (!geom || !radii || acc->radii_max == radii) return MOM_EINVAL;
+    rc = check_grads(a, gr);
+    if (rc) return rc;
+    GeomView g;
+    geom_view(mom_align_ptr(geom), a->P, &g);
+    rc = mom_launch_preprocess_bwd(a, radii, g, gr, acc, s);
+    if (rc) return rc;
+    MOM_CHECK_LAUNCH(a, s);
+    return MOM_OK;
+}
+
+int mom_raster_backward_acc(const MomRasterArgs* a, const int* radii, void* geom, void* binning, size_t capacity, void* image,
+                            const float* dL_dout_color, const float* dL_dout_depth, const MomRasterGrads* gr,
+                            const MomRasterAccum* acc, mom_stream_t stream)
+{
+    int rc = check_args(a);                     // every argument is checked before anything is launched
+    if (rc) return rc;
+    rc = check_accum(a, acc);
+    if (rc) return rc;
+    if (a->P == 0) return MOM_OK;
+    if (!geom || !binning || !image || !radii || !dL_dout_color || acc->radii_max == radii) return MOM_EINVAL;
+    rc = check_grads(a, gr);
+    if (rc) return rc;
+    rc = mom_raster_backward_render(a, geom, binning, capacity, image, dL_dout_color, dL_dout_depth, stream);
+    if (rc) return rc;
+    return mom_raster_backward_geometry_acc(a, radii, geom, gr, acc, stream);
 }
 
 int mom_raster_backward(const MomRasterArgs* a, const int* radii, void* geom, void* binning, size_t capacity, void* image,

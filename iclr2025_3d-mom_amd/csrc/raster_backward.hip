@@ -59,7 +59,18 @@ struct BwdArgs {
     // dL/d mean2D (all three accumulators or none); st_skip as that function's skip_if_nonzero
     float *st_maxr, *st_accum, *st_denom;
     const uint32_t* st_skip;
+    // MomRasterAccum (read by the ACC instantiations only; last, so that the other forms' argument offsets stay what they were)
+    float* dmeans3D2;            // dL_dmeans3D_copy: this call's own dL_dmeans3D, plain stores (or null)
+    int* radii_max;              // radii_max[i] = max(radii_max[i], radius of this call) (or null)
 };
+
+// old + value as ONE fp32 add of the value the store form writes: the value is made opaque first, so the add cannot be contracted
+// into the multiply that produced it (an FMA would round once where store-then-add rounds twice)
+__device__ __forceinline__ float acc_add(float old, float v)
+{
+    asm("" : "+v"(v));
+    return old + v;
+}
 
 // STAGED (DC and rest stored apart, an odd row length): the workgroup's higher-order SH rows are copied to LDS with
 // coalesced loads, every thread reads its row there, writes the row's GRADIENT over it once it is done reading, and the
@@ -68,7 +79,14 @@ struct BwdArgs {
 // RAW (MomRasterArgs.params_raw): MomRasterArgs.scales / rotations hold the raw parameters.  exp(scale) and the normalised quaternion
 // are recomputed here as the forward (and mom_activations_forward) made them, the activated opacity is the one in the forward's record,
 // and the scale / rotation / opacity gradients go out through the activations as with act_rotations_raw.
-template <bool STAGED, bool RAW>
+// ACC (mom_raster_backward_acc, the second and later cameras of a batch, train_4DGS.py:189-229): dL_dmeans2D, dL_dmeans3D, the SH
+// gradients, dL_dscales, dL_drotations and dL_dopacity hold an earlier call's values and this call ADDS its own -- old + value, one
+// fp32 add of the bits the store form writes -- for the Gaussians this camera saw; a Gaussian with radius 0 here has nothing of them
+// written.  dL_dcolors, dL_dcov3D and the _copy outputs stay plain stores.  The old values are asked for with the other inputs, at
+// the top; the old higher-order SH rows (STAGED) ride beside the staging loads and are added in the coalesced write-back, whose
+// rows of unseen Gaussians are skipped (the at most three floats of a block's rows beyond its last whole float4 are read there).  The statistics epilogue works on the MERGED radius and the accumulated dL_dmeans2D.
+// (Not STAGED: the SH rows are added in place, read where they are written -- the joined layout is not a training path.)
+template <bool STAGED, bool RAW, bool ACC>
 __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdArgs a)
 {
     extern __shared__ float s_sh[];
@@ -104,6 +122,31 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdArgs a)
         in_qraw = make_float4(pr[0], pr[1], pr[2], pr[3]);
     }
     unsigned in_cl = *reinterpret_cast<const unsigned*>(a.colors_from_sh ? reinterpret_cast<const void*>(a.clamped + gi) : reinterpret_cast<const void*>(a.view));
+    // ACC: what the destinations hold, and the running radius (an absent destination reads the view matrix / the radius itself)
+    int in_rmax = 0;
+    float old2d[2], oldop = 0.f, oldm[3], olddc[3], olds[3], oldq[4];
+    float4 oldp[12];
+    uint8_t* s_vis = nullptr;
+    if constexpr (ACC) {
+        in_rmax = (a.radii_max ? a.radii_max : a.radii)[gi];
+        old2d[0] = a.dmeans2D[3 * (size_t)gi];
+        old2d[1] = a.dmeans2D[3 * (size_t)gi + 1];
+        oldop = a.dopacity[gi];
+        const float* __restrict__ pdc = a.dsh ? a.dsh + (size_t)gi * (a.dsh_rest ? 1 : a.M) * 3 : a.view;
+        const float* __restrict__ ps = a.dscales ? a.dscales + 3 * (size_t)gi : a.view;
+        const float* __restrict__ pq = a.drot ? a.drot + 4 * (size_t)gi : a.view;
+#pragma unroll
+        for (int i = 0; i < 3; i++) { oldm[i] = a.dmeans3D[3 * (size_t)gi + i]; olddc[i] = pdc[i]; olds[i] = ps[i]; }
+#pragma unroll
+        for (int i = 0; i < 4; i++) oldq[i] = pq[i];
+        if (STAGED) {
+            const float4* __restrict__ od = reinterpret_cast<const float4*>(a.dsh_rest + (size_t)block0 * sh_stride);
+            const int n4 = n_stage >> 2;
+#pragma unroll
+            for (int k = 0; k < 12; k++) oldp[k] = od[max(min((int)threadIdx.x + 256 * k, n4 - 1), 0)];
+            s_vis = reinterpret_cast<uint8_t*>(s_sh + 256 * sh_stride);     // behind the rows: who of the workgroup saw its Gaussian
+        }
+    }
     if (STAGED) {
         const float* __restrict__ src = a.shs_rest + (size_t)block0 * sh_stride;
         const int n4 = n_stage >> 2;
@@ -121,11 +164,18 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdArgs a)
             if (i < n4) reinterpret_cast<float4*>(s_sh)[i] = piece[k];
         }
         for (int i = 4 * n4 + threadIdx.x; i < n_stage; i += 256) s_sh[i] = src[i];
+        if constexpr (ACC) {
+#pragma unroll
+            for (int k = 0; k < 12; k++) asm("" : "+v"(oldp[k].x), "+v"(oldp[k].y), "+v"(oldp[k].z), "+v"(oldp[k].w));
+            s_vis[threadIdx.x] = (idx < a.P && in_radius > 0) ? 1 : 0;
+        }
         __syncthreads();
     }
     // (outputs only, not `asm volatile`: that counts as a possible store and turns the uniform matrix loads below into vector loads)
     asm("" : "+v"(in_radius), "+v"(ga[0]), "+v"(ga[1]), "+v"(ga[2]), "+v"(ga[3]), "+v"(ga[4]), "+v"(ga[5]), "+v"(ga[6]), "+v"(ga[7]), "+v"(ga[8]), "+v"(ga[9]), "+v"(in_co.x), "+v"(in_co.y), "+v"(in_co.z), "+v"(in_co.w));
     asm("" : "+v"(in_m[0]), "+v"(in_m[1]), "+v"(in_m[2]), "+v"(in_c3[0]), "+v"(in_c3[1]), "+v"(in_c3[2]), "+v"(in_c3[3]), "+v"(in_c3[4]), "+v"(in_c3[5]), "+v"(in_q[0]), "+v"(in_q[1]), "+v"(in_q[2]), "+v"(in_q[3]), "+v"(in_s[0]), "+v"(in_s[1]), "+v"(in_s[2]), "+v"(in_cl), "+v"(in_qraw.x), "+v"(in_qraw.y), "+v"(in_qraw.z), "+v"(in_qraw.w));
+    if constexpr (ACC)
+        asm("" : "+v"(in_rmax), "+v"(old2d[0]), "+v"(old2d[1]), "+v"(oldop), "+v"(oldm[0]), "+v"(oldm[1]), "+v"(oldm[2]), "+v"(olddc[0]), "+v"(olddc[1]), "+v"(olddc[2]), "+v"(olds[0]), "+v"(olds[1]), "+v"(olds[2]), "+v"(oldq[0]), "+v"(oldq[1]), "+v"(oldq[2]), "+v"(oldq[3]));
     if (RAW) {
         in_qraw = make_float4(in_q[0], in_q[1], in_q[2], in_q[3]);
         // (opaque copies: the normalisation's backward below squares them again, contracted as act_rotations_raw's code is; were they
@@ -162,6 +212,25 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdArgs a)
     ga[3] *= -0.5f;
     ga[4] *= -0.5f;
 
+    if constexpr (ACC) {
+        // (the third component is the zero the first call stored)
+        float m2x = old2d[0], m2y = old2d[1];
+        if (vis) {
+            a.dmeans2D[3 * idx + 0] = m2x = acc_add(old2d[0], ga[0]);
+            a.dmeans2D[3 * idx + 1] = m2y = acc_add(old2d[1], ga[1]);
+        }
+        const int rmax = max(in_rmax, in_radius);
+        if (a.radii_max && in_radius > in_rmax) a.radii_max[idx] = in_radius;
+        if (a.st_accum && rmax > 0 && !(a.st_skip && *a.st_skip)) {
+            // densification statistics, once per batch (train_4DGS.py:203-204,227-229,266): mom_densify_stats on the merged radius and
+            // the SUMMED dL/d mean2D -- also for a Gaussian only an earlier camera of the batch saw
+            a.st_maxr[idx] = fmaxf(a.st_maxr[idx], (float)rmax);
+            // mom_grad_norm2d as mom_densify_stats' build contracts it -- fma(gx, gx, gy * gy) -- written out: with these operands
+            // (selects of a sum and a load) the contraction took the other product and the norm differed in its last bit
+            a.st_accum[idx] += sqrtf(__builtin_fmaf(m2x, m2x, m2y * m2y));
+            a.st_denom[idx] += 1.0f;
+        }
+    } else {
     a.dmeans2D[3 * idx + 0] = ga[0];
     a.dmeans2D[3 * idx + 1] = ga[1];
     a.dmeans2D[3 * idx + 2] = 0.f;
@@ -171,7 +240,11 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdArgs a)
         a.st_accum[idx] += mom_grad_norm2d(ga[0], ga[1]);
         a.st_denom[idx] += 1.0f;
     }
+    }
     // (act_rotations_raw / RAW: through the sigmoid, y (1 - y) of the opacity the forward kept in its record -- optim_loss.hip, act_bwd_kernel)
+    if constexpr (ACC) {
+        if (vis) a.dopacity[idx] = acc_add(oldop, through_act ? ga[5] * ((1.0f - in_co.w) * in_co.w) : ga[5]);
+    } else
     a.dopacity[idx] = through_act ? ga[5] * ((1.0f - in_co.w) * in_co.w) : ga[5];
     a.dcolors[3 * idx + 0] = ga[6];
     a.dcolors[3 * idx + 1] = ga[7];
@@ -277,8 +350,14 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdArgs a)
             const float dRGB[3] = {cl.x ? 0.f : ga[6], cl.y ? 0.f : ga[7], cl.z ? 0.f : ga[8]};
             float ddir[3] = {0.f, 0.f, 0.f};
 #define SH(i, c) sh[(i) * 3 + (c)]
-#define DSH(i, s) { const float s__ = (s); dshr[(i) * 3 + 0] = s__ * dRGB[0]; dshr[(i) * 3 + 1] = s__ * dRGB[1]; dshr[(i) * 3 + 2] = s__ * dRGB[2]; }
+            // (ACC: staged rows take the plain value -- the write-back adds; rows in place are added here)
+#define PUT(dst, v) { if constexpr (ACC && !STAGED) (dst) = acc_add((dst), (v)); else (dst) = (v); }
+#define DSH(i, s) { const float s__ = (s); PUT(dshr[(i) * 3 + 0], s__ * dRGB[0]); PUT(dshr[(i) * 3 + 1], s__ * dRGB[1]); PUT(dshr[(i) * 3 + 2], s__ * dRGB[2]); }
+            if constexpr (ACC) {
+                dsh[0] = acc_add(olddc[0], bSH_C0 * dRGB[0]); dsh[1] = acc_add(olddc[1], bSH_C0 * dRGB[1]); dsh[2] = acc_add(olddc[2], bSH_C0 * dRGB[2]);
+            } else {
             dsh[0] = bSH_C0 * dRGB[0]; dsh[1] = bSH_C0 * dRGB[1]; dsh[2] = bSH_C0 * dRGB[2];
+            }
             // the direction gradient READS the coefficients; the coefficient gradients below may overwrite them (staged rows)
             float xx = 0, yy = 0, zz = 0, xy = 0, yz = 0, xz = 0;
             if (a.D > 1) { xx = x * x; yy = y * y; zz = z * z; xy = x * y; yz = y * z; xz = x * z; }
@@ -331,9 +410,10 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdArgs a)
             }
             // coefficients above the active degree receive zero gradient
             const int used = (a.D + 1) * (a.D + 1);
-            for (int i = used; i < a.M; i++) { dshr[i * 3 + 0] = 0.f; dshr[i * 3 + 1] = 0.f; dshr[i * 3 + 2] = 0.f; }
+            for (int i = used; i < a.M; i++) { PUT(dshr[i * 3 + 0], 0.f); PUT(dshr[i * 3 + 1], 0.f); PUT(dshr[i * 3 + 2], 0.f); }
 #undef SH
 #undef DSH
+#undef PUT
             // through the normalisation of the view direction (auxiliary.h:107-117)
             const float sum2 = dox * dox + doy * doy + doz * doz;
             const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
@@ -376,13 +456,26 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdArgs a)
 #undef DM
         }
     }
+    if constexpr (!ACC) {
     if (dsh && !(vis && a.colors_from_sh)) {
         dsh[0] = dsh[1] = dsh[2] = 0.f;
         for (int i = 3; i < a.M * 3; i++) dshr[i] = 0.f;
     }
+    }
 
+    if constexpr (ACC) {
+        if (vis) {
+#pragma unroll
+            for (int i = 0; i < 3; i++) a.dmeans3D[3 * idx + i] = acc_add(oldm[i], dmean[i]);
+        }
+        if (a.dmeans3D2) {
+#pragma unroll
+            for (int i = 0; i < 3; i++) a.dmeans3D2[3 * idx + i] = dmean[i];
+        }
+    } else {
 #pragma unroll
     for (int i = 0; i < 3; i++) a.dmeans3D[3 * idx + i] = dmean[i];
+    }
 #pragma unroll
     for (int i = 0; i < 6; i++) a.dcov3D[6 * idx + i] = dcov[i];
     if (through_act) {
@@ -401,6 +494,16 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdArgs a)
         drot[2] = (g4[2] - u.z * dot) / n;
         drot[3] = (g4[3] - u.w * dot) / n;
     }
+    if constexpr (ACC) {
+        if (a.dscales && vis) {
+#pragma unroll
+            for (int i = 0; i < 3; i++) a.dscales[3 * idx + i] = acc_add(olds[i], dscale[i]);
+        }
+        if (a.drot && vis) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) a.drot[4 * idx + i] = acc_add(oldq[i], drot[i]);
+        }
+    } else {
     if (a.dscales) {
 #pragma unroll
         for (int i = 0; i < 3; i++) a.dscales[3 * idx + i] = dscale[i];
@@ -408,6 +511,7 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdArgs a)
     if (a.drot) {
 #pragma unroll
         for (int i = 0; i < 4; i++) a.drot[4 * idx + i] = drot[i];
+    }
     }
     if (a.dscales2) {
 #pragma unroll
@@ -422,14 +526,39 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(BwdArgs a)
         __syncthreads();
         float* __restrict__ dst = a.dsh_rest + (size_t)block0 * sh_stride;
         const int n4 = n_stage >> 2;
+        if constexpr (ACC) {
+            // old + value, the value read back from LDS (so: rounded as stored); four floats touch at most two rows, and only the
+            // rows of Gaussians this camera saw are written
+#pragma unroll
+            for (int k = 0; k < 12; k++) {
+                const int i = threadIdx.x + 256 * k;
+                if (i < n4) {
+                    const float4 v = reinterpret_cast<const float4*>(s_sh)[i], o = oldp[k];
+                    const int e = 4 * i, r0 = e / sh_stride, r1 = (e + 3) / sh_stride, split_at = (r0 + 1) * sh_stride - e;   // components >= split_at: row r1
+                    const bool v0 = s_vis[r0] != 0, v1 = s_vis[r1] != 0;
+                    const float4 w = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
+                    if (v0 && v1) reinterpret_cast<float4*>(dst)[i] = w;
+                    else if (v0 || v1) {
+                        const float wc[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+                        for (int c = 0; c < 4; c++)
+                            if (c < split_at ? v0 : v1) dst[e + c] = wc[c];
+                    }
+                }
+            }
+            for (int i = 4 * n4 + threadIdx.x; i < n_stage; i += 256)
+                if (s_vis[i / sh_stride]) dst[i] = dst[i] + s_sh[i];
+        } else {
         for (int i = threadIdx.x; i < n4; i += 256) reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(s_sh)[i];
         for (int i = 4 * n4 + threadIdx.x; i < n_stage; i += 256) dst[i] = s_sh[i];
+        }
     }
 }
 
 }  // namespace
 
-int mom_launch_preprocess_bwd(const MomRasterArgs* a, const int* radii, const GeomView& g, const MomRasterGrads* gr, hipStream_t s)
+int mom_launch_preprocess_bwd(const MomRasterArgs* a, const int* radii, const GeomView& g, const MomRasterGrads* gr, const MomRasterAccum* acc,
+                              hipStream_t s)
 {
     BwdArgs b;
     b.P = a->P; b.D = a->D; b.M = a->M; b.W = a->W; b.H = a->H;
@@ -449,18 +578,32 @@ int mom_launch_preprocess_bwd(const MomRasterArgs* a, const int* radii, const Ge
     b.rots_raw = gr->act_rotations_raw;                      // (raster_api.hip, check_grads: only with scales and rotations present)
     b.st_maxr = gr->stats_max_radii2D; b.st_accum = gr->stats_grad_accum; b.st_denom = gr->stats_denom;   // (check_grads: all or none)
     b.st_skip = gr->stats_skip_if_nonzero;
+    b.dmeans3D2 = acc ? acc->dL_dmeans3D_copy : nullptr;
+    b.radii_max = acc ? acc->radii_max : nullptr;
     MomProfScope ps(MOM_P_PRE_BWD, s);
     const int sh_stride = (a->M - 1) * 3;
     const bool staged = b.colors_from_sh && b.shs_rest && b.dsh_rest && (sh_stride & 1) && sh_stride <= 45 &&
                         ((uintptr_t)b.shs_rest & 15) == 0 && ((uintptr_t)b.dsh_rest & 15) == 0;
     const dim3 grid((a->P + 255) / 256);
-    if (staged && a->params_raw)
-        hipLaunchKernelGGL((preprocess_bwd_kernel<true, true>), grid, dim3(256), (size_t)256 * sh_stride * 4, s, b);
+    if (acc) {
+        // (the staged form keeps one byte per thread behind its rows: who saw its Gaussian)
+        const size_t lds = (size_t)256 * sh_stride * 4 + 256;
+        if (staged && a->params_raw)
+            hipLaunchKernelGGL((preprocess_bwd_kernel<true, true, true>), grid, dim3(256), lds, s, b);
+        else if (staged)
+            hipLaunchKernelGGL((preprocess_bwd_kernel<true, false, true>), grid, dim3(256), lds, s, b);
+        else if (a->params_raw)
+            hipLaunchKernelGGL((preprocess_bwd_kernel<false, true, true>), grid, dim3(256), 0, s, b);
+        else
+            hipLaunchKernelGGL((preprocess_bwd_kernel<false, false, true>), grid, dim3(256), 0, s, b);
+    }
+    else if (staged && a->params_raw)
+        hipLaunchKernelGGL((preprocess_bwd_kernel<true, true, false>), grid, dim3(256), (size_t)256 * sh_stride * 4, s, b);
     else if (staged)
-        hipLaunchKernelGGL((preprocess_bwd_kernel<true, false>), grid, dim3(256), (size_t)256 * sh_stride * 4, s, b);
+        hipLaunchKernelGGL((preprocess_bwd_kernel<true, false, false>), grid, dim3(256), (size_t)256 * sh_stride * 4, s, b);
     else if (a->params_raw)
-        hipLaunchKernelGGL((preprocess_bwd_kernel<false, true>), grid, dim3(256), 0, s, b);
+        hipLaunchKernelGGL((preprocess_bwd_kernel<false, true, false>), grid, dim3(256), 0, s, b);
     else
-        hipLaunchKernelGGL((preprocess_bwd_kernel<false, false>), grid, dim3(256), 0, s, b);
+        hipLaunchKernelGGL((preprocess_bwd_kernel<false, false, false>), grid, dim3(256), 0, s, b);
     return hipGetLastError() == hipSuccess ? MOM_OK : MOM_ELAUNCH;
 }

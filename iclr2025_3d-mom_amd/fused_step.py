@@ -2,12 +2,18 @@
 synchronisation.  FusedStep is the fine stage's, FusedCoarseStep the coarse stage's; _Step holds what they share.
 
 FusedStep computes exactly what `train.Trainer.step` computes through `render()` + `loss.backward()` (the reference's
-train_4DGS.py:149-297 with batch_size 1, stage "fine", L1 (+ lambda_dssim SSIM) loss, the shipped deformation config) and leaves the
+train_4DGS.py:149-297 with any batch_size on one GPU, stage "fine", L1 (+ lambda_dssim SSIM) loss, the shipped deformation config) and leaves the
 same `.grad` tensors behind, so the optimizer step, the densification statistics and everything downstream are shared
 with the autograd path.  `tests/test_fused_step_gpu.py` checks the two paths against each other.
 
 Order of launches: hexplane_fwd -> deform_fwd -> activations_fwd -> preprocess / binning / sort / render_fwd -> l1 ->
 render_bwd / preprocess_bwd -> activations_bwd -> deform_bwd (dx, dw) -> hexplane_bwd -> plane_reg -> adam.
+
+A batch of B cameras (forward_backward takes one camera or a list; train_4DGS.py:172-229) runs them one after the other, forward
+then backward of camera k, then k + 1, on the same scratch: memory does not grow with B.  The first camera's projection backward
+stores the gradients exactly as a single camera's does, every later one ADDS (mom_raster_backward_acc) and merges its radii into
+the first one's (max); every camera's gradient image carries 1 / B; the regulariser, the densification statistics and Adam run
+once.  A list of one camera is the single-camera step, launch for launch.  Batches on the multi-GPU paths are out of scope.
 """
 import ctypes as C
 import os
@@ -36,6 +42,8 @@ class _Step:
         self.next_tag = 1     # what a step leaves in the overflow word if its binning overflows (Trainer numbers the steps)
         self.cap = 0
         self._resize_next = False
+        self._bb = None            # what only the second and later cameras of a batch need (_batch_buffers)
+        self._exact_step = False   # every camera of this step sizes its binning buffer from its own count (exact_next)
         self._key = self._frame = None
 
     def _rows(self, P):
@@ -70,7 +78,9 @@ class _Step:
             self.sums = self.img[(-self.img.data_ptr()) % 256:][:256].view(torch.float32)[8:10]
             # the compositing forward's L1 epilogue leaves one pair of sums per TILE here (MomRasterArgs.l1_partials): added up
             # only when somebody reads the loss (LazyLoss / _TileSums)
-            self.l1_part = e(((W + 15) // 16) * ((H + 15) // 16), 2)
+            # (a batch: one such array per camera, _l1_parts)
+            self._l1_store = e(1, ((W + 15) // 16) * ((H + 15) // 16), 2)
+            self.l1_part = self._l1_store[0]
             self.ssim_dm = None                  # SSIM term: made on first use (lambda_dssim may be switched on later)
             self.binning = None
         self._per_gaussian(P, pad, dev, new_frame)
@@ -95,9 +105,44 @@ class _Step:
         P = g._xyz.shape[0]
         W, H = int(cam.image_width), int(cam.image_height)
         self._ensure(P, W, H, dev)
+        self._exact_step = self._resize_next
         if self._resize_next:                   # after a tile-row re-split, an overflow, or on request (exact_next)
             self.cap, self._resize_next = 0, False
         return P, W, H, dev
+
+    @staticmethod
+    def _cameras(cam):
+        """forward_backward's camera argument as a list: one camera, or the cameras of a batch (all of one image size)."""
+        cams = list(cam) if isinstance(cam, (list, tuple)) else [cam]
+        if not cams:
+            raise N.MomError("forward_backward needs at least one camera")
+        wh = {(int(c.image_width), int(c.image_height)) for c in cams}
+        if len(wh) != 1:
+            raise N.MomError(f"the cameras of a batch must share one image size, got {sorted(wh)}")
+        return cams
+
+    def _l1_parts(self, B):
+        """[B][tiles][2]: the compositing epilogue's per-tile L1 sums of every camera of the step (l1_part is camera 0's)."""
+        if self._l1_store.shape[0] < B:
+            self._l1_store = torch.empty((B,) + tuple(self._l1_store.shape[1:]), dtype=torch.float32, device=self._l1_store.device)
+            self.l1_part = self._l1_store[0]
+        return self._l1_store[:B]
+
+    def _ssim_sums(self, B):
+        """[B][slots]: the SSIM map sums of every camera of the step (ssim_sum is camera 0's)."""
+        self._ssim_win()
+        if self._ssim_store.shape[0] < B:
+            self._ssim_store = torch.empty(B, N.SSIM_SUM_SLOTS, dtype=torch.float64, device=self._ssim_store.device)
+            self.ssim_sum = self._ssim_store[0]
+        return self._ssim_store[:B]
+
+    def _batch_buffers(self, P, dev):
+        """What only the second and later cameras of a batch need, made on first use: the camera's own radii (the merged ones live in
+        ibucket) and a private d pts for its deformation backward (MomRasterAccum.dL_dmeans3D_copy)."""
+        b = self._bb
+        if b is None or b[0] != (P, dev):
+            b = self._bb = ((P, dev), torch.zeros(P, dtype=torch.int32, device=dev), torch.empty(P, 3, dtype=torch.float32, device=dev))
+        return b[1], b[2]
 
     def exact_next(self):
         """Size the binning buffer of the next step from that step's own instance count (one host sync): it cannot overflow."""
@@ -114,19 +159,22 @@ class _Step:
     def gather_moments(self):
         """Before an iteration that reads or restructures the optimizer state (FusedStep: sharded Adam).  Here the state is whole."""
 
-    def _raster_forward(self, a, P, W, H, dev, s):
+    def _raster_forward(self, a, P, W, H, dev, s, radii=None, first=True):
         """Projection + binning, then the compositing into color / depth, its overflow into the sticky word.  Async: the binning
-        capacity comes from an earlier iteration's instance count (cap == 0: from this frame's own, one sync)."""
+        capacity comes from an earlier iteration's instance count (cap == 0: from this frame's own, one sync).  radii: where the
+        projection leaves this camera's radii (default: the step's merged ones); first: the first camera of the step -- a later one
+        may grow the binning buffer but not shrink it, and after exact_next() sizes it from its own count too."""
         lib = self.lib
+        radii = self.radii if radii is None else radii
         # an earlier iteration's instance count (whichever copy landed last: a sizing hint, read without blocking)
         prev_R = int(self.nr_host[0])
-        N.check(lib.mom_raster_forward_geometry(C.byref(a), self.geom.data_ptr(), self.img.data_ptr(), self.radii.data_ptr(),
+        N.check(lib.mom_raster_forward_geometry(C.byref(a), self.geom.data_ptr(), self.img.data_ptr(), radii.data_ptr(),
                                                 self.nr_dev.data_ptr(), self.nr_host.data_ptr(), s), "raster_geometry")
-        if self.cap == 0:                       # first call: size exactly (one sync)
+        if self.cap == 0 or self._exact_step:   # first call: size exactly (one sync)
             torch.cuda.current_stream().synchronize()
             prev_R = int(self.nr_host[0])
         want = max(prev_R, int(prev_R * self.HEADROOM) + self.MARGIN)
-        if self.binning is None or want > self._bin_cap or want < self._bin_cap // 4:
+        if self.binning is None or want > self._bin_cap or (first and want < self._bin_cap // 4):
             self._bin_cap = want
             self.binning = torch.empty(lib.mom_raster_binning_bytes(P, W, H, want), dtype=torch.uint8, device=dev)
         self.cap = self._bin_cap          # the capacity every launch of this step is told (cap == 0 above: "size exactly")
@@ -139,17 +187,20 @@ class _Step:
         if self.ssim_dm is None:
             (W, H), dev = self._wh, self.color.device
             self.ssim_dm = torch.empty((3, 3, H, W), dtype=torch.float32, device=dev)
-            self.ssim_sum = torch.empty(N.SSIM_SUM_SLOTS, dtype=torch.float64, device=dev)   # [0] = the sum
+            self._ssim_store = torch.empty(1, N.SSIM_SUM_SLOTS, dtype=torch.float64, device=dev)
+            self.ssim_sum = self._ssim_store[0]                                                # [0] = the sum
         return ops._ssim_window()
 
-    def _ssim_full(self, gt, lam, s):
+    def _ssim_full(self, gt, lam, s, k=0, B=1):
         """loss += lambda_dssim * (1 - ssim(image, gt))  (train_4DGS.py:222-223) over the whole image: its gradient is added
-        into dimg, the map's sum is left in ssim_sum."""
+        into dimg, the map's sum is left in ssim_sum.  Camera k of a batch of B: ssim() of the [B,3,H,W] stack is the mean over all
+        of its elements, so the gradient carries 1 / B and the sum goes to the camera's own row of _ssim_sums."""
         win, (W, H), n = self._ssim_win(), self._wh, self.color.numel()
+        sums = self.ssim_sum if B == 1 else self._ssim_sums(B)[k]
         N.check(self.lib.mom_ssim_forward(3, H, W, win, self.color.data_ptr(), gt.data_ptr(), self.ssim_dm.data_ptr(),
-                                          self.ssim_sum.data_ptr(), s), "ssim_fwd")
+                                          sums.data_ptr(), s), "ssim_fwd")
         N.check(self.lib.mom_ssim_backward(3, H, W, win, self.color.data_ptr(), gt.data_ptr(), self.ssim_dm.data_ptr(),
-                                           -lam / n, None, self.dimg.data_ptr(), s), "ssim_bwd")
+                                           -lam / (n * B), None, self.dimg.data_ptr(), s), "ssim_bwd")
 
     def _set_grads(self):
         """.grad of the six Gaussian parameters = the step's own gradient buffers (they persist across steps)."""
@@ -158,11 +209,17 @@ class _Step:
                         (g._rotation, self.grot), (g._opacity, self.gop)):
             p.grad = gbuf
 
-    def _loss(self, l1, reg, lam, n):
+    def _loss(self, l1, reg, lam, n, B=1):
         """(loss, radii, screen-space gradient) of the step; the loss is formed when read (LazyLoss).  l1: a device scalar, or
-        None for the per-tile sums the compositing epilogue left."""
-        sums = _TileSums(self.l1_part) if l1 is None else self.sums
-        loss = LazyLoss(sums if l1 is None else None, l1, reg, self.ssim_sum if lam != 0 else None, lam, n)
+        None for the per-tile sums the compositing epilogue left.  n: elements of one image; a batch of B cameras is the mean over
+        all B n of them (train_4DGS.py:189-229), its sums added camera by camera, tile by tile, in a fixed order."""
+        ssim_sum = self.ssim_sum if lam != 0 else None
+        if B > 1:
+            sums, n = _TileSums(self._l1_parts(B).view(-1, 2)), n * B
+            ssim_sum = _BatchSum(self._ssim_sums(B)) if lam != 0 else None
+        else:
+            sums = _TileSums(self.l1_part) if l1 is None else self.sums
+        loss = LazyLoss(sums if l1 is None else None, l1, reg, ssim_sum if lam != 0 else None, lam, n)
         self.last = {"loss": loss, "mse_sum": _Lazy(sums, 1), "n": n}       # float(last["mse_sum"]): formed when read
         return loss, self.radii, self.g2d
 
@@ -323,21 +380,24 @@ class FusedStep(_Step):
 
     # ------------------------------------------------------------------ one iteration (forward + backward)
     def forward_backward(self, cam, delta_scale=1, early_adam=None):
-        """early_adam: callable(list of parameters) or None -- see EARLY_ADAM below; the caller promises that its optimizer step
-        for this iteration follows with nothing in between that reads or replaces those parameters."""
+        """cam: one camera, or the list of a batch's cameras (module docstring).  early_adam: callable(list of parameters) or None
+        -- see EARLY_ADAM below; the caller promises that its optimizer step for this iteration follows with nothing in between
+        that reads or replaces those parameters."""
         g, lib, s = self.g, self.lib, N.current_stream()
+        cams = self._cameras(cam)
+        B, cam = len(cams), cams[0]
+        if B > 1 and self.dist is not None:
+            raise N.MomError("FusedStep: a batch of cameras on the multi-GPU paths is not supported (one camera per rank)")
         P, W, H, dev = self._begin(cam)
         sharded = bool(self._chunk) and early_adam is not None and self.EARLY_ADAM     # this iteration takes the sharded-Adam path
         if self._chunk:
             self._rehome()
-        view, proj, campos, gt = cam.device_tensors(dev)
         dn = g._deformation.deformation_net
         field = dn.grid
         planes, mlp = self._deform_grads()
         xyz, f_dc, f_rest, scal, rot, opac = ops.gaussian_params(g, "FusedStep")
         flow = g._scene_flow if g._scene_flow.is_contiguous() else g._scene_flow.contiguous()
         lam = float(self.opt.lambda_dssim)
-        time = float(cam.time)
         order = field._processing_order(xyz)
         optr = None if order is None else order.data_ptr()
         porders = field._plane_orders(xyz)           # per-space-plane orders of the two-pass HexPlane backward
@@ -356,7 +416,6 @@ class FusedStep(_Step):
             self._desc = (hp, keep, md)
             self._desc_key, self._reg_arr = dkey, None
         hp, keep, md = self._desc
-        coef = float(delta_scale * cam.frame_num)
         # ---- second stream, first job: clear the deformation field's gradient bucket and run the plane regularisers (value +
         # gradient; they depend on the planes only, so they need not wait for the backward) while this stream renders.  The
         # backward's kernels then ADD into what the regulariser left; this stream waits for the event before its first write
@@ -404,256 +463,284 @@ class FusedStep(_Step):
         # this step's forward and backward (scene/hexplane.py: prefetch_if_due)
         if dc is None or dc.mode == "camera":
             field.prefetch_if_due(xyz, side)
-        # HexPlane lookup + MLP + the activations (exp / normalize / sigmoid) in one kernel (csrc/deform_field.hip)
-        dc = self.dist
-        sl = None
-        if dc is not None and dc.mode == "tile-row":
-            # the deformation field is half of a step and does not care which rank computes which Gaussian: every rank takes a
-            # contiguous slice [g0, g1) of them, forward and backward, and the ranks all-gather the deformed state (what the
-            # replicated projection needs of ALL Gaussians: 15 floats each) while nothing else is in flight
-            S = dc.slice_rows(P)
-            g0 = min(P, dc.rank * S)
-            g1 = min(P, g0 + S)
-            sl = (S, g0, g1)
-            # The five tensors of the deformed state are gathered IN PLACE, each in its own [world * S, k] array (the slice's
-            # field kernel writes this rank's rows directly), as ONE grouped submission on the direct RCCL transport
-            # (ncclGroupStart / End: one launch).  Round 5 packed them into one slab per rank for a single torch.distributed call
-            # (40-50 us of host each) and paid five strided copies behind the gather at every world size; with the collectives
-            # behind the C ABI a call costs 0.6 us and the copies are gone.  (torch.distributed, the fallback and the CPU tests'
-            # transport, issues the five gathers one after the other.)
-            if g1 > g0:
-                v = lambda t: t[g0:g1]
-                so = field._slice_order(xyz, g0, g1)
-                lines_kept = ops.field_forward(hp, md, g1 - g0, v(xyz), time, so, v(scal), v(rot), v(flow), coef, v(self.pts), v(self.sc_d),
-                                  v(self.rot_d), v(self.feat), v(self.a0), v(opac), v(self.sc), v(self.rot), v(self.op), s)
-            grp = None
-            if hasattr(dc, "group"):
-                with dc.group() as grp:
-                    dc.start_gather([self.pts, self.sc, self.rot, self.op, self.rot_d], S)
-            else:
-                dc.start_gather([self.pts, self.sc, self.rot, self.op, self.rot_d], S)
-            if grp is not None and getattr(grp, "work", None) is not None:
-                dc._pending.append(grp.work)
-            dc.finish()
-        else:
-            lines_kept = ops.field_forward(hp, md, P, xyz, time, order, scal, rot, flow, coef, self.pts, self.sc_d, self.rot_d, self.feat, self.a0,
-                              opac, self.sc, self.rot, self.op, s)
-        # ---- rasterizer forward (async: capacity from the previous iterations, checked below)
-        a = ops.raster_args(cam, view, proj, campos, self.bg, P, g.active_sh_degree, self.pts, f_dc, f_rest, self.op, self.sc, self.rot,
-                            False, 1.0, False, self.keep_all_tiles)
-        a.accum_cleared = 1                     # on the second stream, above
-        # L1 (its gradient image and its sums) in the compositing kernel's epilogue, one pair of sums per tile.  A tile-row shard too,
-        # unless its forward renders a halo (SSIM term): the kernel runs this rank's tiles only, and the rank adds up ITS rows
-        tr_rows = dc is not None and dc.mode == "tile-row"
-        l1_scaled = False
-        fuse_l1 = not tr_rows or lam == 0
-        if fuse_l1:
-            a.l1_target, a.l1_grad, a.l1_partials = gt.data_ptr(), self.dimg.data_ptr(), self.l1_part.data_ptr()
-            # camera-batch shard: the batch loss is the mean over the ranks' cameras, every gradient carries 1 / world (below)
-            # -- in the epilogue itself when the loss is L1 alone (with the SSIM term the whole gradient image is scaled once, below)
-            l1_scaled = dc is not None and dc.mode == "camera" and lam == 0
-            a.l1_grad_scale = 1.0 / dc.world if l1_scaled else 0.0
-        a.overflow_tag = self.next_tag          # what this step leaves in the sticky word if its binning overflows (Trainer numbers the steps)
-        rows = fwd_rows = None
-        if dc is not None and dc.mode == "tile-row":
-            # every rank renders this same camera, restricted to its rows of 16-pixel tiles.  With the SSIM term the forward
-            # also renders one tile row of halo on each side: the 11x11 window makes an owned pixel depend on map pixels up to
-            # 5 rows outside, and those on image pixels up to 10 rows outside -- all inside the 16-row halo, so nothing is
-            # exchanged (the neighbour composites the same rows to the same bits).  The backward covers the own rows only.
-            gy = (H + 15) // 16
-            rows = dc.rows(gy)
-            halo = 1 if (lam != 0 and rows[1] > rows[0]) else 0
-            fwd_rows = (max(rows[0] - halo, 0), min(rows[1] + halo, gy))
-            a.tile_row0, a.tile_row1 = fwd_rows
-        self._raster_forward(a, P, W, H, dev, s)
-        early_works = []                        # camera-batch shard: what the early Adam launch must see reduced (below)
-        if dc is not None and dc.mode != "camera":
-            early_works.append(dc.start(self.flags, "max"))         # every rank skips (and later replays) the same steps
-            # (a camera-batch shard agrees on the word together with the radii, behind its own backward: below)
-        # ---- loss: L1 (+ its gradient image) ; regulariser value and gradient
-        n = self.color.numel()
-        if not fuse_l1:
-            N.check(lib.mom_l1_loss_acc(n, self.color.data_ptr(), gt.data_ptr(), self.dimg.data_ptr(), self.sums.data_ptr(), s), "l1")
-        # camera-batch shard: the batch loss is the mean over the ranks' cameras (train_4DGS.py:189-229), so every
-        # gradient carries 1/world and the all-reduces below are plain sums (1/2, 1/4, 1/8 are exact in fp32)
-        inv_world = 1.0 / dc.world if (dc is not None and dc.mode == "camera") else 1.0
-        # tile-row shard: the ranks' deformation gradients are SUMMED (each holds its slice's share); the regulariser's gradient,
-        # which every rank computes in full, must enter that sum once
-        reg_scale = 1.0 / dc.world if dc is not None else 1.0
-        if lam != 0:
-            # loss += lambda_dssim * (1 - ssim(image, gt))  (train_4DGS.py:222-223): its gradient is added into dimg
-            if rows is None:
-                self._ssim_full(gt, lam, s)
-            elif rows[1] > rows[0]:
-                # the slab this rank rendered (own rows + halo), as a pitched view of the full buffers: map rows of the own
-                # tile rows count toward the sum; derivative maps are kept 5 rows beyond them (up to the image's own edges,
-                # where zero padding is the reference's behaviour) and are zero elsewhere
-                win = self._ssim_win()
-                ys0, ys1 = fwd_rows[0] * 16, min(H, fwd_rows[1] * 16)
-                y0, y1 = rows[0] * 16, min(H, rows[1] * 16)
-                off = ys0 * W * 4
-                N.check(lib.mom_ssim_forward_slab(3, ys1 - ys0, W, H * W, y0 - ys0, y1 - ys0, max(0, y0 - 5) - ys0,
-                                                  min(H, y1 + 5) - ys0, win, self.color.data_ptr() + off, gt.data_ptr() + off,
-                                                  self.ssim_dm.data_ptr() + off, self.ssim_sum.data_ptr(), s), "ssim_fwd_slab")
-                N.check(lib.mom_ssim_backward_slab(3, ys1 - ys0, W, H * W, win, self.color.data_ptr() + off, gt.data_ptr() + off,
-                                                   self.ssim_dm.data_ptr() + off, -lam / n, None, self.dimg.data_ptr() + off, s),
-                        "ssim_bwd_slab")
-            else:
-                self._ssim_win()
-                self.ssim_sum.zero_()
-        if dc is not None and dc.mode == "camera" and not (fuse_l1 and l1_scaled):
-            self.dimg.mul_(inv_world)            # (L1 alone: the forward's epilogue wrote the gradient image with the factor in it)
-        # ---- rasterizer backward
-        ops.stream_wait_mark(s, ops.MARK_BUCKET)      # the gradient bucket is cleared and holds the regulariser's share
-        gr = ops.raster_grads(self.g2d, self.gcol, self.gop, self.gxyz, self.gcov, self.gdc, self.grest, self.gsc, self.grot)
-        # scale / rotation / opacity gradients leave the projection backward already through exp / normalize / sigmoid
-        # (MomRasterGrads.act_rotations_raw): no activation-backward launch behind it
-        gr.act_rotations_raw = self.rot_d.data_ptr()
-        if dc is not None and dc.mode == "camera":
-            # the deformation backward still reads this rank's own d_sc / d_rot while the bucket that holds them is being reduced in
-            # place: its private copies (7 floats per Gaussian) come out of the same kernel
-            gr.dL_dscales_copy, gr.dL_drotations_copy = self._loc[0].data_ptr(), self._loc[1].data_ptr()
-        if rows is None:
-            N.check(lib.mom_raster_backward(C.byref(a), self.radii.data_ptr(), self.geom.data_ptr(), self.binning.data_ptr(),
-                                            self.cap, self.img.data_ptr(), self.dimg.data_ptr(), None, C.byref(gr), s), "raster_bwd")
-        else:
-            # tile-row shard: the compositing backward covers this rank's rows only (dimg outside them is never read); the
-            # per-Gaussian record it leaves is summed over the ranks, after which the projection backward -- linear in that
-            # record -- and everything downstream give the same gradients on every rank, with nothing left to exchange
-            if hasattr(dc, "rebalance_due") and dc.rebalance_due():
-                # instance counts per tile row of the rows this rank owns -> agreed weights for the next splits; after a
-                # re-split the local instance count can jump, so the next step sizes its binning buffer exactly again
-                gx_ = (W + 15) // 16
-                lay = N.MomRasterLayout()
-                lib.mom_raster_layout(P, W, H, 0, C.byref(lay))
-                base = self.img[(-self.img.data_ptr()) % 256:]
-                per_row = base[lay.img_tile_counts:lay.img_tile_counts + gx_ * gy * 4].view(torch.int32).view(gy, gx_).sum(1).float()
-                own = torch.zeros_like(per_row)
-                own[rows[0]:rows[1]] = per_row[rows[0]:rows[1]]
-                if dc.rebalance_rows(own):
-                    # the local instance count can jump with the new rows: size the NEXT step's buffer exactly.  This step's
-                    # backward below still runs on the buffer (and capacity) its forward filled.
-                    self._resize_next = True
-            a.tile_row0, a.tile_row1 = rows          # own rows only (the forward may have covered a halo)
-            N.check(lib.mom_raster_backward_render(C.byref(a), self.geom.data_ptr(), self.binning.data_ptr(), self.cap,
-                                                   self.img.data_ptr(), self.dimg.data_ptr(), None, s), "raster_bwd_render")
-            dc.start(self._gacc_view(P, W, H), "sum")
-            dc.finish()
-            N.check(lib.mom_raster_backward_geometry(C.byref(a), self.radii.data_ptr(), self.geom.data_ptr(), C.byref(gr), s),
-                    "raster_bwd_geometry")
-        if dc is not None and dc.mode == "camera":
-            # densification statistics (train_4DGS.py:203-204,227-229): largest radius, mean 2-D gradient
-            # (this rank's backward has read its OWN radii by now; the overflow word rides in the same integer bucket.  Every
-            # torch.distributed call costs the host 40-50 us and the host paces a rank: three collectives per step, not five)
-            early_works.append(dc.start(self.ibucket, "max"))
-        d_sc, d_rot = self.gsc, self.grot       # also the gradients w.r.t. the MLP's scale / rotation outputs
-        if dc is not None and dc.mode == "camera":      # 56 of the 59 floats per Gaussian travel underneath the deformation backward
-            d_sc, d_rot = self._loc            # private copies, written by the projection backward (above)
-            if sharded:
-                # reduce-scatter of the appearance gradients (this rank keeps the sum of ITS chunk) + the small all-reduce of the
-                # screen-space gradients every rank's statistics need in full: one launch on the direct path
-                with dc.group() as grp:
-                    w_rs = dc.start_reduce_scatter(self.app_flat, self._chunk, "sum")
-                    w_g2 = dc.start(self.g2d_flat, "sum")
-                if grp.work is not None:
-                    dc._pending.append(grp.work)
-                    early_works.append(grp.work)
-                else:
-                    early_works += [w_rs, w_g2]
-            else:
-                early_works.append(dc.start(self.early_bucket, "sum"))     # appearance gradients + mean 2-D gradients
-        # ---- deformation backward: pts = xyz + dx(...) so d xyz starts as d pts (already in gxyz); the HexPlane adds its share
-        # the MLP's weight-gradient kernel (matrix pipe) runs on a second stream beside the HexPlane backward (vector issue,
-        # memory latency); joined below, before anything reads the weight gradients
-        side = self.side.cuda_stream if self.OVERLAP_DW else s
-        early_cam = None
-        if early_adam is not None and self.EARLY_ADAM:
-            # The appearance parameters' gradients (SH, scaling, rotation, opacity: 56 of a Gaussian's 59 floats) are final here.
-            # Their Adam update -- a pure HBM stream, 335 of Adam's 412 MB -- goes to the second stream now and runs underneath the
-            # MLP backward (matrix pipe, 2 TB/s); nothing on this stream reads those parameters again before the join below.
-            for p, gbuf in ((g._features_dc, self.gdc), (g._features_rest, self.grest), (g._scaling, self.gsc),
-                            (g._rotation, self.grot), (g._opacity, self.gop)):
-                p.grad = gbuf
-            if dc is None or dc.mode == "tile-row":
-                # (a tile-row shard's gradients are already the full sums here: the ranks summed the compositing backward's record,
-                # and projection / activation backward ran replicated on it)
+        # ---- the cameras, one after the other: forward and backward of camera k, then k + 1, on the same scratch
+        for k, cam in enumerate(cams):
+            view, proj, campos, gt = cam.device_tensors(dev)
+            time = float(cam.time)
+            coef = float(delta_scale * cam.frame_num)
+            radii_k, d_pts, gmark = self.radii, self.gxyz, None
+            if k > 0:
+                # the camera's own radii and d pts (the merged radii / the running sum of d xyz stay in the buckets), and the
+                # compositing accumulator cleared again -- on the second stream, behind camera k - 1's projection backward, its
+                # last reader (this stream has joined the second one at the end of that camera)
+                radii_k, d_pts = self._batch_buffers(P, dev)
                 ops.stream_wait_stream(self.side.cuda_stream, s)
-                early_adam([g._features_dc, g._features_rest, g._scaling, g._rotation, g._opacity], stream=self.side.cuda_stream)
+                ops.zero_async(self._gacc_cache[1], self.side.cuda_stream)
+                gmark = ops.next_ring_mark(self.side.cuda_stream)
+            # HexPlane lookup + MLP + the activations (exp / normalize / sigmoid) in one kernel (csrc/deform_field.hip)
+            dc = self.dist
+            sl = None
+            if dc is not None and dc.mode == "tile-row":
+                # the deformation field is half of a step and does not care which rank computes which Gaussian: every rank takes a
+                # contiguous slice [g0, g1) of them, forward and backward, and the ranks all-gather the deformed state (what the
+                # replicated projection needs of ALL Gaussians: 15 floats each) while nothing else is in flight
+                S = dc.slice_rows(P)
+                g0 = min(P, dc.rank * S)
+                g1 = min(P, g0 + S)
+                sl = (S, g0, g1)
+                # The five tensors of the deformed state are gathered IN PLACE, each in its own [world * S, k] array (the slice's
+                # field kernel writes this rank's rows directly), as ONE grouped submission on the direct RCCL transport
+                # (ncclGroupStart / End: one launch).  Round 5 packed them into one slab per rank for a single torch.distributed call
+                # (40-50 us of host each) and paid five strided copies behind the gather at every world size; with the collectives
+                # behind the C ABI a call costs 0.6 us and the copies are gone.  (torch.distributed, the fallback and the CPU tests'
+                # transport, issues the five gathers one after the other.)
+                if g1 > g0:
+                    v = lambda t: t[g0:g1]
+                    so = field._slice_order(xyz, g0, g1)
+                    lines_kept = ops.field_forward(hp, md, g1 - g0, v(xyz), time, so, v(scal), v(rot), v(flow), coef, v(self.pts), v(self.sc_d),
+                                      v(self.rot_d), v(self.feat), v(self.a0), v(opac), v(self.sc), v(self.rot), v(self.op), s)
+                grp = None
+                if hasattr(dc, "group"):
+                    with dc.group() as grp:
+                        dc.start_gather([self.pts, self.sc, self.rot, self.op, self.rot_d], S)
+                else:
+                    dc.start_gather([self.pts, self.sc, self.rot, self.op, self.rot_d], S)
+                if grp is not None and getattr(grp, "work", None) is not None:
+                    dc._pending.append(grp.work)
+                dc.finish()
             else:
-                # camera-batch shard: the launch needs the REDUCED bucket (and, for the densification statistics it carries, the
-                # reduced radii / screen-space gradients and the agreed overflow word).  The second stream waits for exactly those
-                # collectives -- each was begun behind the kernels that produced its buffer, so it orders the stream behind them
-                # too -- and not for this stream, which goes on with the deformation backward.  Enqueued BELOW, after that
-                # backward: on RCCL wait() only makes the waiting stream wait, but gloo (the tests) blocks the host in it, and the
-                # host should block with the GPU's work already queued.
-                early_cam = list(early_works)
-
-        def launch_early_cam():
-            """Camera-batch shard: the second stream waits for the early collectives, then takes the appearance parameters' Adam
-            launch (sharded: this rank's 1/world of it, then the in-place all-gather of the UPDATED parameters behind it -- begun from
-            inside the second stream's context, so it is ordered behind that stream's Adam launch; the caller's DistContext.finish()
-            makes the main stream wait for it before anything reads a parameter)."""
-            app = [g._features_dc, g._features_rest, g._scaling, g._rotation, g._opacity]
-            if getattr(dc, "direct", None) is not None and not sharded:
-                # direct RCCL path: a wait is one hipStreamWaitEvent on the second stream's raw handle (no torch stream context: ~10 us)
-                dc.wait_for(early_cam, stream=self.side.cuda_stream)
-                early_adam(app, stream=self.side.cuda_stream)
-                return
-            with torch.cuda.stream(self.side):          # (torch.distributed's wait() orders the CURRENT torch stream)
-                dc.wait_for(early_cam)
+                lines_kept = ops.field_forward(hp, md, P, xyz, time, order, scal, rot, flow, coef, self.pts, self.sc_d, self.rot_d, self.feat, self.a0,
+                                  opac, self.sc, self.rot, self.op, s)
+            # ---- rasterizer forward (async: capacity from the previous iterations, checked below)
+            a = ops.raster_args(cam, view, proj, campos, self.bg, P, g.active_sh_degree, self.pts, f_dc, f_rest, self.op, self.sc, self.rot,
+                                False, 1.0, False, self.keep_all_tiles)
+            a.accum_cleared = 1                     # on the second stream, above
+            # L1 (its gradient image and its sums) in the compositing kernel's epilogue, one pair of sums per tile.  A tile-row shard too,
+            # unless its forward renders a halo (SSIM term): the kernel runs this rank's tiles only, and the rank adds up ITS rows
+            tr_rows = dc is not None and dc.mode == "tile-row"
+            l1_scaled = False
+            fuse_l1 = not tr_rows or lam == 0
+            if fuse_l1:
+                a.l1_target, a.l1_grad, a.l1_partials = gt.data_ptr(), self.dimg.data_ptr(), self._l1_parts(B)[k].data_ptr()
+                # camera-batch shard: the batch loss is the mean over the ranks' cameras, every gradient carries 1 / world (below)
+                # -- in the epilogue itself when the loss is L1 alone (with the SSIM term the whole gradient image is scaled once, below)
+                l1_scaled = dc is not None and dc.mode == "camera" and lam == 0
+                a.l1_grad_scale = 1.0 / dc.world if l1_scaled else 0.0
+                if B > 1:
+                    a.l1_grad_scale = 1.0 / B           # the batch loss is the mean over its cameras (the SSIM term: _ssim_full)
+            a.overflow_tag = self.next_tag          # what this step leaves in the sticky word if its binning overflows (Trainer numbers the steps)
+            rows = fwd_rows = None
+            if dc is not None and dc.mode == "tile-row":
+                # every rank renders this same camera, restricted to its rows of 16-pixel tiles.  With the SSIM term the forward
+                # also renders one tile row of halo on each side: the 11x11 window makes an owned pixel depend on map pixels up to
+                # 5 rows outside, and those on image pixels up to 10 rows outside -- all inside the 16-row halo, so nothing is
+                # exchanged (the neighbour composites the same rows to the same bits).  The backward covers the own rows only.
+                gy = (H + 15) // 16
+                rows = dc.rows(gy)
+                halo = 1 if (lam != 0 and rows[1] > rows[0]) else 0
+                fwd_rows = (max(rows[0] - halo, 0), min(rows[1] + halo, gy))
+                a.tile_row0, a.tile_row1 = fwd_rows
+            self._raster_forward(a, P, W, H, dev, s, radii_k, k == 0)
+            early_works = []                        # camera-batch shard: what the early Adam launch must see reduced (below)
+            if dc is not None and dc.mode != "camera":
+                early_works.append(dc.start(self.flags, "max"))         # every rank skips (and later replays) the same steps
+                # (a camera-batch shard agrees on the word together with the radii, behind its own backward: below)
+            # ---- loss: L1 (+ its gradient image) ; regulariser value and gradient
+            n = self.color.numel()
+            if not fuse_l1:
+                N.check(lib.mom_l1_loss_acc(n, self.color.data_ptr(), gt.data_ptr(), self.dimg.data_ptr(), self.sums.data_ptr(), s), "l1")
+            # camera-batch shard: the batch loss is the mean over the ranks' cameras (train_4DGS.py:189-229), so every
+            # gradient carries 1/world and the all-reduces below are plain sums (1/2, 1/4, 1/8 are exact in fp32)
+            inv_world = 1.0 / dc.world if (dc is not None and dc.mode == "camera") else 1.0
+            # tile-row shard: the ranks' deformation gradients are SUMMED (each holds its slice's share); the regulariser's gradient,
+            # which every rank computes in full, must enter that sum once
+            reg_scale = 1.0 / dc.world if dc is not None else 1.0
+            if lam != 0:
+                # loss += lambda_dssim * (1 - ssim(image, gt))  (train_4DGS.py:222-223): its gradient is added into dimg
+                if rows is None:
+                    self._ssim_full(gt, lam, s, k, B)
+                elif rows[1] > rows[0]:
+                    # the slab this rank rendered (own rows + halo), as a pitched view of the full buffers: map rows of the own
+                    # tile rows count toward the sum; derivative maps are kept 5 rows beyond them (up to the image's own edges,
+                    # where zero padding is the reference's behaviour) and are zero elsewhere
+                    win = self._ssim_win()
+                    ys0, ys1 = fwd_rows[0] * 16, min(H, fwd_rows[1] * 16)
+                    y0, y1 = rows[0] * 16, min(H, rows[1] * 16)
+                    off = ys0 * W * 4
+                    N.check(lib.mom_ssim_forward_slab(3, ys1 - ys0, W, H * W, y0 - ys0, y1 - ys0, max(0, y0 - 5) - ys0,
+                                                      min(H, y1 + 5) - ys0, win, self.color.data_ptr() + off, gt.data_ptr() + off,
+                                                      self.ssim_dm.data_ptr() + off, self.ssim_sum.data_ptr(), s), "ssim_fwd_slab")
+                    N.check(lib.mom_ssim_backward_slab(3, ys1 - ys0, W, H * W, win, self.color.data_ptr() + off, gt.data_ptr() + off,
+                                                       self.ssim_dm.data_ptr() + off, -lam / n, None, self.dimg.data_ptr() + off, s),
+                            "ssim_bwd_slab")
+                else:
+                    self._ssim_win()
+                    self.ssim_sum.zero_()
+            if dc is not None and dc.mode == "camera" and not (fuse_l1 and l1_scaled):
+                self.dimg.mul_(inv_world)            # (L1 alone: the forward's epilogue wrote the gradient image with the factor in it)
+            # ---- rasterizer backward
+            # the gradient bucket is cleared and holds the regulariser's share (a later camera: its accumulator record is cleared)
+            ops.stream_wait_mark(s, ops.MARK_BUCKET if k == 0 else gmark)
+            gr = ops.raster_grads(self.g2d, self.gcol, self.gop, self.gxyz, self.gcov, self.gdc, self.grest, self.gsc, self.grot)
+            # scale / rotation / opacity gradients leave the projection backward already through exp / normalize / sigmoid
+            # (MomRasterGrads.act_rotations_raw): no activation-backward launch behind it
+            gr.act_rotations_raw = self.rot_d.data_ptr()
+            if dc is not None and dc.mode == "camera":
+                # the deformation backward still reads this rank's own d_sc / d_rot while the bucket that holds them is being reduced in
+                # place: its private copies (7 floats per Gaussian) come out of the same kernel
+                gr.dL_dscales_copy, gr.dL_drotations_copy = self._loc[0].data_ptr(), self._loc[1].data_ptr()
+            if k > 0:
+                # cameras 2..B ADD their gradients to the first one's and merge their radii into its (train_4DGS.py:203-204,217-229);
+                # the deformation backward of THIS camera reads its own d pts / d scales / d rotations, private plain stores
+                gr.dL_dscales_copy, gr.dL_drotations_copy = self._loc[0].data_ptr(), self._loc[1].data_ptr()
+                acc = N.MomRasterAccum()
+                acc.dL_dmeans3D_copy, acc.radii_max = d_pts.data_ptr(), self.radii.data_ptr()
+                N.check(lib.mom_raster_backward_acc(C.byref(a), radii_k.data_ptr(), self.geom.data_ptr(), self.binning.data_ptr(),
+                                                    self.cap, self.img.data_ptr(), self.dimg.data_ptr(), None, C.byref(gr),
+                                                    C.byref(acc), s), "raster_bwd_acc")
+            elif rows is None:
+                N.check(lib.mom_raster_backward(C.byref(a), self.radii.data_ptr(), self.geom.data_ptr(), self.binning.data_ptr(),
+                                                self.cap, self.img.data_ptr(), self.dimg.data_ptr(), None, C.byref(gr), s), "raster_bwd")
+            else:
+                # tile-row shard: the compositing backward covers this rank's rows only (dimg outside them is never read); the
+                # per-Gaussian record it leaves is summed over the ranks, after which the projection backward -- linear in that
+                # record -- and everything downstream give the same gradients on every rank, with nothing left to exchange
+                if hasattr(dc, "rebalance_due") and dc.rebalance_due():
+                    # instance counts per tile row of the rows this rank owns -> agreed weights for the next splits; after a
+                    # re-split the local instance count can jump, so the next step sizes its binning buffer exactly again
+                    gx_ = (W + 15) // 16
+                    lay = N.MomRasterLayout()
+                    lib.mom_raster_layout(P, W, H, 0, C.byref(lay))
+                    base = self.img[(-self.img.data_ptr()) % 256:]
+                    per_row = base[lay.img_tile_counts:lay.img_tile_counts + gx_ * gy * 4].view(torch.int32).view(gy, gx_).sum(1).float()
+                    own = torch.zeros_like(per_row)
+                    own[rows[0]:rows[1]] = per_row[rows[0]:rows[1]]
+                    if dc.rebalance_rows(own):
+                        # the local instance count can jump with the new rows: size the NEXT step's buffer exactly.  This step's
+                        # backward below still runs on the buffer (and capacity) its forward filled.
+                        self._resize_next = True
+                a.tile_row0, a.tile_row1 = rows          # own rows only (the forward may have covered a halo)
+                N.check(lib.mom_raster_backward_render(C.byref(a), self.geom.data_ptr(), self.binning.data_ptr(), self.cap,
+                                                       self.img.data_ptr(), self.dimg.data_ptr(), None, s), "raster_bwd_render")
+                dc.start(self._gacc_view(P, W, H), "sum")
+                dc.finish()
+                N.check(lib.mom_raster_backward_geometry(C.byref(a), self.radii.data_ptr(), self.geom.data_ptr(), C.byref(gr), s),
+                        "raster_bwd_geometry")
+            if dc is not None and dc.mode == "camera":
+                # densification statistics (train_4DGS.py:203-204,227-229): largest radius, mean 2-D gradient
+                # (this rank's backward has read its OWN radii by now; the overflow word rides in the same integer bucket.  Every
+                # torch.distributed call costs the host 40-50 us and the host paces a rank: three collectives per step, not five)
+                early_works.append(dc.start(self.ibucket, "max"))
+            d_sc, d_rot = self.gsc, self.grot       # also the gradients w.r.t. the MLP's scale / rotation outputs
+            if k > 0:
+                d_sc, d_rot = self._loc
+            if dc is not None and dc.mode == "camera":      # 56 of the 59 floats per Gaussian travel underneath the deformation backward
+                d_sc, d_rot = self._loc            # private copies, written by the projection backward (above)
                 if sharded:
-                    ranges = {id(p_): r for p_, r in zip(app, dc.shard_ranges(self._cut, self._chunk))}
-                    early_adam(app, stream=self.side.cuda_stream, ranges=ranges)
-                    dc.start_gather_flat(self.pflat, self._chunk)
-            if not sharded:
-                early_adam(app, stream=self.side.cuda_stream)
-
-        if early_cam is not None and not getattr(dc, "host_blocking", False):
-            # On RCCL (either transport) a wait only orders streams: the launch goes to the second stream NOW, ahead of the MLP
-            # backward's reduction kernel that is about to be queued there, and runs underneath that backward as in the unsharded
-            # step.  (Queued behind the reduction it ran beside the HexPlane gather instead, which it slows from 83 to 116 us.)
-            launch_early_cam()
+                    # reduce-scatter of the appearance gradients (this rank keeps the sum of ITS chunk) + the small all-reduce of the
+                    # screen-space gradients every rank's statistics need in full: one launch on the direct path
+                    with dc.group() as grp:
+                        w_rs = dc.start_reduce_scatter(self.app_flat, self._chunk, "sum")
+                        w_g2 = dc.start(self.g2d_flat, "sum")
+                    if grp.work is not None:
+                        dc._pending.append(grp.work)
+                        early_works.append(grp.work)
+                    else:
+                        early_works += [w_rs, w_g2]
+                else:
+                    early_works.append(dc.start(self.early_bucket, "sum"))     # appearance gradients + mean 2-D gradients
+            # ---- deformation backward: pts = xyz + dx(...) so d xyz starts as d pts (already in gxyz); the HexPlane adds its share
+            # the MLP's weight-gradient kernel (matrix pipe) runs on a second stream beside the HexPlane backward (vector issue,
+            # memory latency); joined below, before anything reads the weight gradients
+            side = self.side.cuda_stream if self.OVERLAP_DW else s
             early_cam = None
-        if sl is None:
-            N.check(lib.mom_deform_backward_split(C.byref(md), P, self.feat.data_ptr(), self.a0.data_ptr(), self.gxyz.data_ptr(),
-                                                  d_sc.data_ptr(), d_rot.data_ptr(), self.dfeat.data_ptr(),
-                                                  self.dh_scratch.data_ptr(), s, side), "deform_bwd")
-            if porders is not None:
-                self._hex_scratch_for(hp, P, dev)
-            if porders is not None and lines_kept:      # the forward's time lines are still in the field scratch
-                N.check(lib.mom_hexplane_backward_lines(C.byref(hp), P, xyz.data_ptr(), time, optr, self.dfeat.data_ptr(),
-                                                        self.gxyz.data_ptr(), porders[0].data_ptr(), porders[1].data_ptr(),
-                                                        self._hex_scratch.data_ptr(), ops.field_scratch(hp, dev).data_ptr(), s),
-                        "hexplane_bwd")
+            if early_adam is not None and self.EARLY_ADAM and k == B - 1:       # (a batch: behind the LAST camera's projection backward)
+                # The appearance parameters' gradients (SH, scaling, rotation, opacity: 56 of a Gaussian's 59 floats) are final here.
+                # Their Adam update -- a pure HBM stream, 335 of Adam's 412 MB -- goes to the second stream now and runs underneath the
+                # MLP backward (matrix pipe, 2 TB/s); nothing on this stream reads those parameters again before the join below.
+                for p, gbuf in ((g._features_dc, self.gdc), (g._features_rest, self.grest), (g._scaling, self.gsc),
+                                (g._rotation, self.grot), (g._opacity, self.gop)):
+                    p.grad = gbuf
+                if dc is None or dc.mode == "tile-row":
+                    # (a tile-row shard's gradients are already the full sums here: the ranks summed the compositing backward's record,
+                    # and projection / activation backward ran replicated on it)
+                    ops.stream_wait_stream(self.side.cuda_stream, s)
+                    early_adam([g._features_dc, g._features_rest, g._scaling, g._rotation, g._opacity], stream=self.side.cuda_stream)
+                else:
+                    # camera-batch shard: the launch needs the REDUCED bucket (and, for the densification statistics it carries, the
+                    # reduced radii / screen-space gradients and the agreed overflow word).  The second stream waits for exactly those
+                    # collectives -- each was begun behind the kernels that produced its buffer, so it orders the stream behind them
+                    # too -- and not for this stream, which goes on with the deformation backward.  Enqueued BELOW, after that
+                    # backward: on RCCL wait() only makes the waiting stream wait, but gloo (the tests) blocks the host in it, and the
+                    # host should block with the GPU's work already queued.
+                    early_cam = list(early_works)
+
+            def launch_early_cam():
+                """Camera-batch shard: the second stream waits for the early collectives, then takes the appearance parameters' Adam
+                launch (sharded: this rank's 1/world of it, then the in-place all-gather of the UPDATED parameters behind it -- begun from
+                inside the second stream's context, so it is ordered behind that stream's Adam launch; the caller's DistContext.finish()
+                makes the main stream wait for it before anything reads a parameter)."""
+                app = [g._features_dc, g._features_rest, g._scaling, g._rotation, g._opacity]
+                if getattr(dc, "direct", None) is not None and not sharded:
+                    # direct RCCL path: a wait is one hipStreamWaitEvent on the second stream's raw handle (no torch stream context: ~10 us)
+                    dc.wait_for(early_cam, stream=self.side.cuda_stream)
+                    early_adam(app, stream=self.side.cuda_stream)
+                    return
+                with torch.cuda.stream(self.side):          # (torch.distributed's wait() orders the CURRENT torch stream)
+                    dc.wait_for(early_cam)
+                    if sharded:
+                        ranges = {id(p_): r for p_, r in zip(app, dc.shard_ranges(self._cut, self._chunk))}
+                        early_adam(app, stream=self.side.cuda_stream, ranges=ranges)
+                        dc.start_gather_flat(self.pflat, self._chunk)
+                if not sharded:
+                    early_adam(app, stream=self.side.cuda_stream)
+
+            if early_cam is not None and not getattr(dc, "host_blocking", False):
+                # On RCCL (either transport) a wait only orders streams: the launch goes to the second stream NOW, ahead of the MLP
+                # backward's reduction kernel that is about to be queued there, and runs underneath that backward as in the unsharded
+                # step.  (Queued behind the reduction it ran beside the HexPlane gather instead, which it slows from 83 to 116 us.)
+                launch_early_cam()
+                early_cam = None
+            if sl is None:
+                N.check(lib.mom_deform_backward_split(C.byref(md), P, self.feat.data_ptr(), self.a0.data_ptr(), d_pts.data_ptr(),
+                                                      d_sc.data_ptr(), d_rot.data_ptr(), self.dfeat.data_ptr(),
+                                                      self.dh_scratch.data_ptr(), s, side), "deform_bwd")
+                if porders is not None:
+                    self._hex_scratch_for(hp, P, dev)
+                if porders is not None and lines_kept:      # the forward's time lines are still in the field scratch
+                    N.check(lib.mom_hexplane_backward_lines(C.byref(hp), P, xyz.data_ptr(), time, optr, self.dfeat.data_ptr(),
+                                                            self.gxyz.data_ptr(), porders[0].data_ptr(), porders[1].data_ptr(),
+                                                            self._hex_scratch.data_ptr(), ops.field_scratch(hp, dev).data_ptr(), s),
+                            "hexplane_bwd")
+                else:
+                    N.check(lib.mom_hexplane_backward(C.byref(hp), P, xyz.data_ptr(), None, time, optr, self.dfeat.data_ptr(),
+                                                      self.gxyz.data_ptr(), None if porders is None else porders[0].data_ptr(),
+                                                      None if porders is None else porders[1].data_ptr(),
+                                                      None if porders is None else self._hex_scratch.data_ptr(), s), "hexplane_bwd")
             else:
-                N.check(lib.mom_hexplane_backward(C.byref(hp), P, xyz.data_ptr(), None, time, optr, self.dfeat.data_ptr(),
-                                                  self.gxyz.data_ptr(), None if porders is None else porders[0].data_ptr(),
-                                                  None if porders is None else porders[1].data_ptr(),
-                                                  None if porders is None else self._hex_scratch.data_ptr(), s), "hexplane_bwd")
-        else:
-            # tile-row shard: the deformation backward of this rank's slice only.  Its weight / plane gradients are partial sums
-            # (summed over the ranks below); its position gradients complete gxyz for the slice's rows, which the ranks then
-            # all-gather -- the other rows hold d pts only, replicated by the projection backward.
-            S, g0, g1 = sl
-            ns = g1 - g0
-            if ns > 0:
-                v = lambda t: t[g0:g1]
-                N.check(lib.mom_deform_backward_split(C.byref(md), ns, v(self.feat).data_ptr(), v(self.a0).data_ptr(),
-                                                      v(self.gxyz).data_ptr(), v(d_sc).data_ptr(), v(d_rot).data_ptr(),
-                                                      v(self.dfeat).data_ptr(), self.dh_scratch.data_ptr(), s, side), "deform_bwd")
-                so = field._slice_order(xyz, g0, g1, bump=False)      # the forward's order of this step
-                spo = field._slice_plane_orders(xyz, g0, g1)
-                if spo is not None:
-                    self._hex_scratch_for(hp, ns, dev)
-                N.check(lib.mom_hexplane_backward(C.byref(hp), ns, v(xyz).data_ptr(), None, time, None if so is None else so.data_ptr(),
-                                                  v(self.dfeat).data_ptr(), v(self.gxyz).data_ptr(),
-                                                  None if spo is None else spo[0].data_ptr(), None if spo is None else spo[1].data_ptr(),
-                                                  None if spo is None else self._hex_scratch.data_ptr(), s), "hexplane_bwd")
-            dc.start_gather([self.gxyz_rows], S)
-        if early_cam is not None:
-            launch_early_cam()          # (gloo: its wait() blocks the host, so only now, with the deformation backward queued)
-        if self.side is not None:
-            ops.stream_wait_stream(s, self.side.cuda_stream)
+                # tile-row shard: the deformation backward of this rank's slice only.  Its weight / plane gradients are partial sums
+                # (summed over the ranks below); its position gradients complete gxyz for the slice's rows, which the ranks then
+                # all-gather -- the other rows hold d pts only, replicated by the projection backward.
+                S, g0, g1 = sl
+                ns = g1 - g0
+                if ns > 0:
+                    v = lambda t: t[g0:g1]
+                    N.check(lib.mom_deform_backward_split(C.byref(md), ns, v(self.feat).data_ptr(), v(self.a0).data_ptr(),
+                                                          v(self.gxyz).data_ptr(), v(d_sc).data_ptr(), v(d_rot).data_ptr(),
+                                                          v(self.dfeat).data_ptr(), self.dh_scratch.data_ptr(), s, side), "deform_bwd")
+                    so = field._slice_order(xyz, g0, g1, bump=False)      # the forward's order of this step
+                    spo = field._slice_plane_orders(xyz, g0, g1)
+                    if spo is not None:
+                        self._hex_scratch_for(hp, ns, dev)
+                    N.check(lib.mom_hexplane_backward(C.byref(hp), ns, v(xyz).data_ptr(), None, time, None if so is None else so.data_ptr(),
+                                                      v(self.dfeat).data_ptr(), v(self.gxyz).data_ptr(),
+                                                      None if spo is None else spo[0].data_ptr(), None if spo is None else spo[1].data_ptr(),
+                                                      None if spo is None else self._hex_scratch.data_ptr(), s), "hexplane_bwd")
+                dc.start_gather([self.gxyz_rows], S)
+            if early_cam is not None:
+                launch_early_cam()          # (gloo: its wait() blocks the host, so only now, with the deformation backward queued)
+            if self.side is not None:
+                ops.stream_wait_stream(s, self.side.cuda_stream)
         if dc is not None and dc.mode == "camera":
             dc.start(self._dg_flat, "sum")     # xyz + deformation field; the caller waits (DistContext.finish) before Adam
         elif sl is not None:
@@ -687,7 +774,7 @@ class FusedStep(_Step):
             if lam != 0:
                 self.ssim_sum[:1].copy_(self._tr_sums[2:3])
             l1 = self._tr_sums[0] / n
-        return self._loss(l1, reg, lam, n)
+        return self._loss(l1, reg, lam, n, B)
 
 
 class FusedCoarseStep(_Step):
@@ -724,36 +811,55 @@ class FusedCoarseStep(_Step):
         self.g2d, self.gcol, self.gcov = e(P, 3), e(P, 3), e(P, 6)
 
     def forward_backward(self, cam, delta_scale=1, early_adam=None, stats=False):
-        """One coarse iteration up to (not including) the optimizer step.  stats: update the densification statistics in the
-        projection backward (the caller's iteration is below densify_until_iter).  early_adam is ignored: there is no deformation
-        backward to hide Adam under.  Returns (loss, radii, screen-space gradient) like FusedStep.forward_backward."""
+        """One coarse iteration up to (not including) the optimizer step.  cam: one camera, or the list of a batch's cameras (the
+        first one's projection backward stores, the others add: module docstring).  stats: update the densification statistics in
+        the projection backward (the caller's iteration is below densify_until_iter) -- of a batch: in the LAST camera's, from the
+        merged radii and the summed screen-space gradient.  early_adam is ignored: there is no deformation backward to hide Adam
+        under.  Returns (loss, radii, screen-space gradient) like FusedStep.forward_backward."""
         g, lib, s = self.g, self.lib, N.current_stream()
-        P, W, H, dev = self._begin(cam)
-        view, proj, campos, gt = cam.device_tensors(dev)
+        cams = self._cameras(cam)
+        B = len(cams)
+        if B > 1 and self.dist is not None:
+            raise N.MomError("FusedCoarseStep: a batch of cameras on the multi-GPU paths is not supported")
+        P, W, H, dev = self._begin(cams[0])
         xyz, f_dc, f_rest, scal, rot, opac = ops.gaussian_params(g, "FusedCoarseStep")
-        # the raw parameters: the projection applies exp / normalize / sigmoid itself (gaussian_renderer/__init__.py:130-132)
-        a = ops.raster_args(cam, view, proj, campos, self.bg, P, g.active_sh_degree, xyz, f_dc, f_rest, opac, scal, rot, True, 1.0,
-                            False, self.keep_all_tiles)
-        a.l1_target, a.l1_grad, a.l1_partials = gt.data_ptr(), self.dimg.data_ptr(), self.l1_part.data_ptr()
-        a.overflow_tag = self.next_tag
-        self._raster_forward(a, P, W, H, dev, s)
         lam = float(self.opt.lambda_dssim)
-        if lam != 0:
-            self._ssim_full(gt, lam, s)
-        gr = ops.raster_grads(self.g2d, self.gcol, self.gop, self.gxyz, self.gcov, self.gdc, self.grest, self.gsc, self.grot)
         if stats:
             # train_4DGS.py:266 in the projection backward's epilogue; a step whose binning overflowed leaves them alone (the replay
             # makes them), as mom_densify_stats does with the same word
             for t in (g.max_radii2D, g.xyz_gradient_accum, g.denom):
                 if t.numel() != P or not t.is_contiguous() or t.dtype != torch.float32:
                     raise N.MomError("FusedCoarseStep: the densification accumulators must be contiguous float32, one per Gaussian")
-            gr.stats_max_radii2D, gr.stats_grad_accum = g.max_radii2D.data_ptr(), g.xyz_gradient_accum.data_ptr()
-            gr.stats_denom, gr.stats_skip_if_nonzero = g.denom.data_ptr(), self.flags.data_ptr()
-        N.check(lib.mom_raster_backward(C.byref(a), self.radii.data_ptr(), self.geom.data_ptr(), self.binning.data_ptr(),
-                                        self.cap, self.img.data_ptr(), self.dimg.data_ptr(), None, C.byref(gr), s), "raster_bwd")
+        for k, cam in enumerate(cams):
+            view, proj, campos, gt = cam.device_tensors(dev)
+            # the raw parameters: the projection applies exp / normalize / sigmoid itself (gaussian_renderer/__init__.py:130-132)
+            a = ops.raster_args(cam, view, proj, campos, self.bg, P, g.active_sh_degree, xyz, f_dc, f_rest, opac, scal, rot, True, 1.0,
+                                False, self.keep_all_tiles)
+            a.l1_target, a.l1_grad, a.l1_partials = gt.data_ptr(), self.dimg.data_ptr(), self._l1_parts(B)[k].data_ptr()
+            if B > 1:
+                a.l1_grad_scale = 1.0 / B           # the batch loss is the mean over its cameras (the SSIM term: _ssim_full)
+            a.overflow_tag = self.next_tag          # one tag per STEP: any camera's overflow makes the whole step a no-op
+            radii_k = self.radii if k == 0 else self._batch_buffers(P, dev)[0]
+            self._raster_forward(a, P, W, H, dev, s, radii_k, k == 0)
+            if lam != 0:
+                self._ssim_full(gt, lam, s, k, B)
+            gr = ops.raster_grads(self.g2d, self.gcol, self.gop, self.gxyz, self.gcov, self.gdc, self.grest, self.gsc, self.grot)
+            if stats and k == B - 1:
+                gr.stats_max_radii2D, gr.stats_grad_accum = g.max_radii2D.data_ptr(), g.xyz_gradient_accum.data_ptr()
+                gr.stats_denom, gr.stats_skip_if_nonzero = g.denom.data_ptr(), self.flags.data_ptr()
+            if k == 0:
+                N.check(lib.mom_raster_backward(C.byref(a), self.radii.data_ptr(), self.geom.data_ptr(), self.binning.data_ptr(),
+                                                self.cap, self.img.data_ptr(), self.dimg.data_ptr(), None, C.byref(gr), s), "raster_bwd")
+            else:
+                # cameras 2..B add their gradients to the first one's and merge their radii into its (train_4DGS.py:203-204,217-229)
+                acc = N.MomRasterAccum()
+                acc.radii_max = self.radii.data_ptr()
+                N.check(lib.mom_raster_backward_acc(C.byref(a), radii_k.data_ptr(), self.geom.data_ptr(), self.binning.data_ptr(),
+                                                    self.cap, self.img.data_ptr(), self.dimg.data_ptr(), None, C.byref(gr),
+                                                    C.byref(acc), s), "raster_bwd_acc")
         self.stats_done = bool(stats)
         self._set_grads()
-        return self._loss(None, None, lam, self.color.numel())
+        return self._loss(None, None, lam, self.color.numel(), B)
 
 
 class _TileSums:
@@ -768,6 +874,16 @@ class _TileSums:
         if self._t is None:
             self._t = self._part.sum(0)
         return self._t[k]
+
+
+class _BatchSum:
+    """sums[0] = the cameras' SSIM map sums added up (rows of _Step._ssim_sums), formed when asked for."""
+
+    def __init__(self, rows):
+        self._rows = rows
+
+    def __getitem__(self, k):
+        return self._rows[:, k].sum()
 
 
 class _Lazy:

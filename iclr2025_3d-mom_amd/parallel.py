@@ -489,6 +489,10 @@ def attach(trainer, rank, world, seed=6666, mode="camera", shard_adam=None):
         # the coarse fused step (fused_step.FusedCoarseStep) is single-GPU: a sharded coarse stage runs on the autograd path with
         # sync_param_grads, as without fused=True
         fused = trainer.fused = None
+    if fused is not None and trainer.opt.batch_size > 1:
+        # a batch of cameras per rank is not a fused multi-GPU path (fused_step.py): such a trainer is what it was before the fused
+        # step took batches -- no fused step at all, every iteration on the autograd path with its own drain / replay protocol
+        fused = trainer.fused = None
     if shard_adam and (fused is None or mode != "camera"):
         raise ValueError("shard_adam needs the fused step and the camera-batch shard")
     trainer.dist = DistContext(rank, world, seed, mode, shard_adam=shard_adam)

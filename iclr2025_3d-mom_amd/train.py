@@ -28,12 +28,14 @@ class Trainer:
         self.last = {}
         self.dist = None     # set by parallel.attach(): camera-batch shard, one camera per rank
         # fused=True: the iteration runs as an explicit launch sequence (fused_step.py: FusedStep, coarse stage FusedCoarseStep)
-        # instead of render()+autograd
+        # instead of render()+autograd -- for any opt.batch_size: the cameras of a batch run one after the other inside one fused step
+        # (train_4DGS.py:172-229).  Multi-GPU x batch is not supported by the fused step: parallel.attach() on a trainer with
+        # batch_size > 1 drops the fused step again, so that trainer is on the autograd path throughout, as it always was.
         self.fused = None
-        if fused and stage in ("fine", "coarse") and opt.batch_size == 1:
+        if fused and stage in ("fine", "coarse"):
             from .fused_step import FusedCoarseStep, FusedStep
             self.fused = (FusedStep if stage == "fine" else FusedCoarseStep)(gaussians, opt, hyper, self.background)
-        # every fused step since the last verified one: (serial, iteration, camera); and the overflow-word read-backs in flight:
+        # every fused step since the last verified one: (serial, iteration, cameras); and the overflow-word read-backs in flight:
         # (serial of the last step they cover, ring slot, event)
         self._log = deque()
         self._checks = deque()
@@ -109,10 +111,10 @@ class Trainer:
         redo = entries[first:]
         self.g.optimizer.rewind(len(redo))      # the host counted steps the device skipped
         self.fused.flags.zero_()
-        for _, it, cam in redo:
+        for _, it, cams in redo:            # every skipped step with ALL its cameras
             self.g.update_learning_rate(it)
             self.fused.exact_next()
-            self._step_fused(it, cam, replay=True)
+            self._step_fused(it, cams, replay=True)
             self.replayed += 1
 
     def _draw(self):
@@ -142,8 +144,8 @@ class Trainer:
         if iteration % 1000 == 0:
             g.oneupSHdegree()
         cams = cams or self._draw()
-        if self.fused is not None and len(cams) == 1:
-            return self._step_fused(iteration, cams[0])
+        if self.fused is not None and (len(cams) == 1 or self.dist is None):
+            return self._step_fused(iteration, list(cams))
         if RC._state["mode"] == "async":
             # the rasterizer sizes its binning buffer from earlier frames and reports an overflow a few forwards later (render()
             # raises BinningOverflow): replay what the overflow skipped (_recover_autograd), then take this iteration again
@@ -249,7 +251,8 @@ class Trainer:
             self.g.update_densification_stats(self.fused.radii, self.fused.g2d, skip_flag=self.fused.flags, stream=stream)
             self._stats_done = True
 
-    def _step_fused(self, iteration, cam, replay=False):
+    def _step_fused(self, iteration, cams, replay=False):
+        cam = cams[0] if len(cams) == 1 else cams       # (one camera: handed over bare, as ever)
         with torch.no_grad():
             if not replay:
                 self._serial += 1
@@ -298,7 +301,7 @@ class Trainer:
         loss = self._after_backward(iteration, loss, radii, visibility, vsp_grad)
         self._skip = None
         if not replay:
-            self._log.append((self._serial, iteration, cam))
+            self._log.append((self._serial, iteration, cams))
         return loss
 
     def _after_backward(self, iteration, loss, radii, visibility, vsp_grad):

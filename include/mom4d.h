@@ -63,7 +63,7 @@ typedef void* mom_stream_t; /* hipStream_t */
 int mom_abi_version(void);
 enum {
     MOM_STRUCT_RASTER_ARGS = 0, MOM_STRUCT_RASTER_GRADS, MOM_STRUCT_RASTER_LAYOUT, MOM_STRUCT_HEXPLANE, MOM_STRUCT_ADAM_TENSOR,
-    MOM_STRUCT_ROW_SELECT, MOM_STRUCT_REG_PLANE, MOM_STRUCT_DEFORM_MLP, MOM_STRUCT_COUNT
+    MOM_STRUCT_ROW_SELECT, MOM_STRUCT_REG_PLANE, MOM_STRUCT_DEFORM_MLP, MOM_STRUCT_RASTER_ACCUM, MOM_STRUCT_COUNT
 };
 size_t mom_abi_sizeof(int which);   /* 0 for an unknown id */
 
@@ -238,6 +238,33 @@ int mom_raster_backward_render(const MomRasterArgs* a, void* geom, void* binning
                                const float* dL_dout_color, const float* dL_dout_depth, mom_stream_t stream);
 int mom_raster_backward_geometry(const MomRasterArgs* a, const int* radii, void* geom, const MomRasterGrads* grads,
                                  mom_stream_t stream);
+
+/* A batch of cameras on one GPU (train_4DGS.py:172-229: every camera of opt.batch_size is rendered, ONE loss is taken over the
+ * [B,3,H,W] stack, backward() runs once, so a parameter's gradient is the SUM over the cameras; :203-204,227-229 merge the radii with
+ * max and the screen-space gradients with a sum).  The first camera's backward is mom_raster_backward: it stores.  Every later camera's
+ * is the _acc form, which ADDS into the same MomRasterGrads: dL_dmeans2D, dL_dmeans3D, dL_dsh / dL_dsh_rest, dL_dscales, dL_drotations
+ * and dL_dopacity become old + value -- one fp32 add of exactly the value the store form writes -- for the Gaussians with radius > 0
+ * in THIS camera; a Gaussian with radius 0 here has none of them written.  dL_dcolors, dL_dcov3D, dL_dscales_copy and
+ * dL_drotations_copy stay per-call outputs, fully written.  The statistics epilogue (stats_*) then performs mom_densify_stats' update
+ * on the MERGED radius max(radii_max[i], radii[i]) and the accumulated dL_dmeans2D: given to the LAST camera's call it is the
+ * once-per-step update of train_4DGS.py:266. */
+typedef struct MomRasterAccum {
+    uint32_t struct_size;    /* = sizeof(MomRasterAccum); anything else: MOM_EINVAL */
+    /* null, or [P,3]: this call's own dL_dmeans3D (zeros for radius 0), plain stores -- what a deformation backward of THIS camera
+     * reads while dL_dmeans3D holds the running sum (gaussian_renderer/__init__.py:96-99: pts = xyz + dx depends on the camera's time) */
+    float* dL_dmeans3D_copy;
+    /* null, or [P]: radii_max[i] = max(radii_max[i], radii[i]) (train_4DGS.py:203 `radii = torch.cat(radii_list, 0).max(dim=0).values`);
+     * `radii`, the camera's own, stays what the backward reads.  Must not alias `radii`. */
+    int* radii_max;
+} MomRasterAccum;
+/* mom_raster_backward / mom_raster_backward_geometry with the accumulating projection backward.  MOM_EINVAL, before anything is
+ * launched: accum null or of another struct_size, a tile-row shard (a->tile_row0 / tile_row1 set: a shard of a batch is not
+ * supported), and everything the store forms refuse (act_rotations_raw with params_raw, statistics pointers given in part, ...). */
+int mom_raster_backward_acc(const MomRasterArgs* a, const int* radii, void* geom, void* binning, size_t capacity,
+                            void* image, const float* dL_dout_color, const float* dL_dout_depth,
+                            const MomRasterGrads* g, const MomRasterAccum* accum, mom_stream_t stream);
+int mom_raster_backward_geometry_acc(const MomRasterArgs* a, const int* radii, void* geom, const MomRasterGrads* grads,
+                                     const MomRasterAccum* accum, mom_stream_t stream);
 
 /* checkFrustum (rasterizer_impl.cu:54-66): present[i] = p_view.z > 0.2 */
 int mom_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,

@@ -4,6 +4,7 @@
     python tools/isa_scan.py                      # per-kernel totals: VALU / MFMA / DS / VMEM / SALU, registers
     python tools/isa_scan.py render_bwd           # mnemonic histogram of the kernels whose name contains the pattern
     python tools/isa_scan.py --packed             # every packed-fp32 instruction (v_pk_*_f32) by kernel
+    python tools/isa_scan.py --diff OTHER.so      # kernels of another build of the library against this one: same instruction sequence or not
 
 The library holds one clang offload bundle per translation unit (section .hip_fatbin); each bundle's gfx950 entry is an
 ELF code object that llvm-objdump disassembles.  tests/test_isa.py uses this to keep packed fp32 arithmetic out of
@@ -41,8 +42,8 @@ def code_objects(path=LIB, arch="gfx950"):
         at += len(MAGIC)
 
 
-def disassemble(image):
-    """{kernel symbol: [mnemonic, ...]} of one code object."""
+def disassemble(image, operands=False):
+    """{kernel symbol: [mnemonic, ...]} of one code object (operands: the whole instruction text, registers and offsets included)."""
     with tempfile.NamedTemporaryFile(suffix=".co") as f:
         f.write(image)
         f.flush()
@@ -56,7 +57,7 @@ def disassemble(image):
             continue
         m = re.match(r"^\s+([a-z_0-9]+)\b", line)
         if m and cur is not None:
-            cur.append(m.group(1))
+            cur.append(" ".join(re.sub(r"//.*", "", line).split()) if operands else m.group(1))
     return kernels
 
 
@@ -74,10 +75,10 @@ def classify(mn):
     return "other"
 
 
-def all_kernels(path=LIB):
+def all_kernels(path=LIB, operands=False):
     ks = {}
     for image in code_objects(path):
-        ks.update(disassemble(image))
+        ks.update(disassemble(image, operands))
     return ks
 
 
@@ -91,9 +92,44 @@ def packed_fp32(ks):
     return out
 
 
+def _template_free(name):
+    """A kernel's symbol with its LAST template argument dropped if that is `false` (ILb1ELb0ELb0EE -> ILb1ELb0EE)."""
+    return re.sub(r"ELb0EE(?=E|v)", "EE", name, count=1)
+
+
+def diff(other):
+    """Compare every kernel of `other` (an older build) with this build's kernel of the same name: the whole instruction text,
+    operands, registers and argument offsets included.  A kernel of `other` whose name is gone is matched to the ONE kernel of this
+    build whose name differs from it only by one more, trailing, `false` template argument (a template that gained a parameter which is off
+    in the old form); names present in both builds are never rewritten."""
+    new = {k: v for k, v in all_kernels(operands=True).items() if not k.endswith(".kd")}
+    old = {k: v for k, v in all_kernels(other, operands=True).items() if not k.endswith(".kd")}
+    same, matched = 0, set()
+    for k in sorted(old):
+        n = k
+        if k not in new:
+            cands = [c for c in new if c not in old and _template_free(c) == k]
+            if len(cands) != 1:
+                print("removed  ", k)
+                continue
+            n = cands[0]
+        matched.add(n)
+        if new[n] == old[k]:
+            same += 1
+        else:
+            print("changed  ", k, len(old[k]), "->", len(new[n]), "instructions")
+    for k in sorted(new):
+        if k not in matched:
+            print("added    ", k, len(new[k]), "instructions")
+    print(f"{same} of {len(old)} kernels of {other} have identical instructions (operands included) in this build")
+
+
 def main():
-    ks = all_kernels()
     args = sys.argv[1:]
+    if len(args) == 2 and args[0] == "--diff":
+        diff(args[1])
+        return
+    ks = all_kernels()
     if args and args[0] == "--packed":
         for name, c in sorted(packed_fp32(ks).items()):
             print(name, dict(c))
