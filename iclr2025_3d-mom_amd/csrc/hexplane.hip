@@ -18,35 +18,6 @@
 
 namespace {
 
-struct PlaneSample {
-    int i00, i01, i10, i11;      // texel indices (row-major over [H][W]), -1 when out of bounds
-    float w00, w01, w10, w11;    // nw, ne, sw, se
-    float gx_mul, gy_mul;        // d(ix)/d(coord) incl. border-clip mask
-    float ix, iy;
-    int ixn, iyn;
-};
-
-__device__ __forceinline__ PlaneSample make_sample(float cx, float cy, int Wd, int Hd)
-{
-    PlaneSample s;
-    s.ix = unnorm_clip(cx, Wd, s.gx_mul);
-    s.iy = unnorm_clip(cy, Hd, s.gy_mul);
-    const float fx = floorf(s.ix), fy = floorf(s.iy);
-    const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-    s.ixn = x0;
-    s.iyn = y0;
-    s.w00 = ((float)x1 - s.ix) * ((float)y1 - s.iy);
-    s.w01 = (s.ix - (float)x0) * ((float)y1 - s.iy);
-    s.w10 = ((float)x1 - s.ix) * (s.iy - (float)y0);
-    s.w11 = (s.ix - (float)x0) * (s.iy - (float)y0);
-    const bool x0in = x0 >= 0 && x0 < Wd, x1in = x1 >= 0 && x1 < Wd, y0in = y0 >= 0 && y0 < Hd, y1in = y1 >= 0 && y1 < Hd;
-    s.i00 = (x0in && y0in) ? y0 * Wd + x0 : -1;
-    s.i01 = (x1in && y0in) ? y0 * Wd + x1 : -1;
-    s.i10 = (x0in && y1in) ? y1 * Wd + x0 : -1;
-    s.i11 = (x1in && y1in) ? y1 * Wd + x1 : -1;
-    return s;
-}
-
 // grid: one half-wave per (Gaussian, level); blockDim 256 = 8 half-waves
 __global__ void __launch_bounds__(256) hexplane_fwd_kernel(HexArgs a, const float* __restrict__ xyz, float* __restrict__ feat)
 {
@@ -197,11 +168,6 @@ __device__ __forceinline__ Corner4 decode4(const float4 r, int Wd)
     return c;
 }
 
-__device__ __forceinline__ float ld_f32(const float* __restrict__ base, unsigned byte_off)
-{
-    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);     // uniform base + 32-bit lane offset
-}
-
 // Forward record of one (point, plane), ready to use: the four corners' byte offsets and their four weights.  Decoding the
 // compact record above cost every channel lane a dozen instructions per (point, plane) -- half of the forward kernel's
 // instruction stream (25.5 M wave instructions per launch on 76 % of the issue cycles); it is done once per point here.
@@ -282,9 +248,6 @@ hexplane_fwd4_kernel(HexArgs a, int nchunks, const float* __restrict__ xyz, floa
 // permutation) is done in phase A, so phase B is loads, a dozen FMAs per plane and the stores.
 // =================================================================================================================
 constexpr int kChunk5 = 32;            // points per wave and chunk in pass 1: each half-wave walks 16
-
-// order slot (0: (x,y), 1: (x,z), 2: (y,z)) whose sorted position a plane's gv row is stored at
-__device__ __forceinline__ constexpr int order_slot_of_plane(int p) { return p == 0 ? 0 : (p == 1 ? 1 : (p == 2 ? 0 : (p == 3 ? 2 : (p == 4 ? 2 : 1)))); }
 
 // pass-1 record of one (point, plane): R1 = {byte offset of texel (y0, x0), byte step to x0+1 (0 if outside), byte step to
 // y0+1 (0 if outside), byte offset of the point's gv row}; R2 = {bx, by, gx, gy}: the fractions and d(ix)/d(world coordinate)
@@ -662,16 +625,25 @@ invert_perm_kernel(int n, const unsigned* __restrict__ order, unsigned* __restri
 int mom_sort_pairs_u32(int n, int bits, unsigned* keys[2], unsigned* vals[2], unsigned* counts, hipStream_t s);
 size_t mom_sort_pairs_counts_bytes(int n);
 
+// hexplane16.hip: the same calls for 16-channel planes (a group of 16 lanes per (point, level))
+int mom_launch_hexplane16_forward(const MomHexPlane* hp, int P, const float* xyz, const float* times, float time, const uint32_t* order,
+                                  float* feat, hipStream_t s);
+int mom_launch_hexplane16_backward(const MomHexPlane* hp, int P, const float* xyz, const float* times, float time, const uint32_t* order,
+                                   const float* dfeat, float* dxyz, const uint32_t* plane_order, const uint32_t* plane_inverse,
+                                   void* scratch, hipStream_t s);
+static bool channels_ok(const MomHexPlane* hp) { return hp->channels == 32 || hp->channels == 16; }
+
 extern "C" int mom_hexplane_forward(const MomHexPlane* hp, int P, const float* xyz, const float* times, float time,
                                     const uint32_t* order, float* feat, mom_stream_t stream)
 {
-    if (!hp || hp->channels != 32 || hp->levels < 1 || hp->levels > 4 || P < 0) return MOM_EINVAL;
+    if (!hp || !channels_ok(hp) || hp->levels < 1 || hp->levels > 4 || P < 0) return MOM_EINVAL;
     if (P == 0) return MOM_OK;
     if (!xyz || !feat) return MOM_EINVAL;
+    MomProfScope ps(MOM_P_HEX_FWD, (hipStream_t)stream);
+    if (hp->channels == 16) return mom_launch_hexplane16_forward(hp, P, xyz, times, time, order, feat, (hipStream_t)stream);
     HexArgs a;
     fill_args(hp, P, times, time, order, false, &a);
     const long long units = (long long)P * hp->levels;
-    MomProfScope ps(MOM_P_HEX_FWD, (hipStream_t)stream);
     if (!times) {
         const int nchunks = (P + kChunkF - 1) / kChunkF;
         int blocks = (nchunks + 3) / 4;
@@ -731,11 +703,12 @@ int mom_launch_hexplane_gather6(const MomHexPlane* hp, int P, const float* xyz, 
                                 float* dxyz, const uint32_t* plane_inverse, float* gvbuf, float* lines, bool lines_ready, hipStream_t s);
 extern "C" int mom_deform_field_supported(const MomHexPlane* hp);
 
-static size_t gv_bytes(const MomHexPlane* hp, int P) { return mom_align_up((size_t)6 * (size_t)P * (size_t)hp->levels * 32 * sizeof(float)); }
+// six gv rows of `channels` floats per (point, level)
+static size_t gv_bytes(const MomHexPlane* hp, int P) { return mom_align_up((size_t)6 * (size_t)P * (size_t)hp->levels * (size_t)hp->channels * sizeof(float)); }
 
 extern "C" size_t mom_hexplane_backward_scratch_bytes(const MomHexPlane* hp, int P)
 {
-    if (!hp || P <= 0) return MOM_ALIGN;
+    if (!hp || !channels_ok(hp) || P <= 0) return MOM_ALIGN;
     return gv_bytes(hp, P) + mom_hexplane_lines_bytes(hp) + MOM_ALIGN;    // gv rows | this frame's time lines
 }
 
@@ -756,6 +729,7 @@ extern "C" int mom_hexplane_backward_lines(const MomHexPlane* hp, int P, const f
                                            mom_stream_t stream)
 {
     if (!field_scratch || !plane_order || !plane_inverse || !scratch) return MOM_EINVAL;
+    if (!hp || hp->channels != 32) return MOM_EINVAL;     // the time lines it reuses exist for 32-channel fields only
     return hexplane_backward(hp, P, xyz, nullptr, time, order, dfeat, dxyz, plane_order, plane_inverse, scratch, field_scratch, stream);
 }
 
@@ -763,7 +737,7 @@ static int hexplane_backward(const MomHexPlane* hp, int P, const float* xyz, con
                              const uint32_t* order, const float* dfeat, float* dxyz, const uint32_t* plane_order,
                              const uint32_t* plane_inverse, void* scratch, const void* field_scratch, mom_stream_t stream)
 {
-    if (!hp || hp->channels != 32 || hp->levels < 1 || hp->levels > 4 || P < 0) return MOM_EINVAL;
+    if (!hp || !channels_ok(hp) || hp->levels < 1 || hp->levels > 4 || P < 0) return MOM_EINVAL;
     if (P == 0) return MOM_OK;
     if (!xyz || !dfeat) return MOM_EINVAL;
     HexArgs a;
@@ -773,6 +747,9 @@ static int hexplane_backward(const MomHexPlane* hp, int P, const float* xyz, con
             if (!a.planes[l][p] || !a.grads[l][p]) return MOM_EINVAL;
     const long long units = (long long)P * hp->levels;
     MomProfScope ps(MOM_P_HEX_BWD, (hipStream_t)stream);
+    if (hp->channels == 16)
+        return mom_launch_hexplane16_backward(hp, P, xyz, times, time, order, dfeat, dxyz, plane_order, plane_inverse, scratch,
+                                              (hipStream_t)stream);
     int wmax = 0;
     for (int l = 0; l < hp->levels; l++)
         for (int k = 0; k < 3; k++)

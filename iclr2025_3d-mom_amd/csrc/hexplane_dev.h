@@ -50,6 +50,36 @@ __device__ __forceinline__ void norm_coords(const HexArgs& a, const float* __res
     c[3] = a.times ? a.times[g] : a.time;
 }
 
+// ---- the generic (one lane group per (point, level)) kernels' sample -------------------------------------------
+struct PlaneSample {
+    int i00, i01, i10, i11;      // texel indices (row-major over [H][W]), -1 when out of bounds
+    float w00, w01, w10, w11;    // nw, ne, sw, se
+    float gx_mul, gy_mul;        // d(ix)/d(coord) incl. border-clip mask
+    float ix, iy;
+    int ixn, iyn;
+};
+
+__device__ __forceinline__ PlaneSample make_sample(float cx, float cy, int Wd, int Hd)
+{
+    PlaneSample s;
+    s.ix = unnorm_clip(cx, Wd, s.gx_mul);
+    s.iy = unnorm_clip(cy, Hd, s.gy_mul);
+    const float fx = floorf(s.ix), fy = floorf(s.iy);
+    const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
+    s.ixn = x0;
+    s.iyn = y0;
+    s.w00 = ((float)x1 - s.ix) * ((float)y1 - s.iy);
+    s.w01 = (s.ix - (float)x0) * ((float)y1 - s.iy);
+    s.w10 = ((float)x1 - s.ix) * (s.iy - (float)y0);
+    s.w11 = (s.ix - (float)x0) * (s.iy - (float)y0);
+    const bool x0in = x0 >= 0 && x0 < Wd, x1in = x1 >= 0 && x1 < Wd, y0in = y0 >= 0 && y0 < Hd, y1in = y1 >= 0 && y1 < Hd;
+    s.i00 = (x0in && y0in) ? y0 * Wd + x0 : -1;
+    s.i01 = (x1in && y0in) ? y0 * Wd + x1 : -1;
+    s.i10 = (x0in && y1in) ? y1 * Wd + x0 : -1;
+    s.i11 = (x1in && y1in) ? y1 * Wd + x1 : -1;
+    return s;
+}
+
 // ---- helpers shared by the chunked kernels -------------------------------------------------------------------
 __device__ __forceinline__ int time_sample(float c, int size, int& i0, int& i1, float& w0, float& w1)
 {
@@ -62,6 +92,14 @@ __device__ __forceinline__ int time_sample(float c, int size, int& i0, int& i1, 
     i1 = (x1 >= 0 && x1 < size) ? x1 : -1;
     return 0;
 }
+
+__device__ __forceinline__ float ld_f32(const float* __restrict__ base, unsigned byte_off)
+{
+    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);     // uniform base + 32-bit lane offset
+}
+
+// order slot (0: (x,y), 1: (x,z), 2: (y,z)) whose sorted position a plane's gv row is stored at
+__device__ __forceinline__ constexpr int order_slot_of_plane(int p) { return p == 0 ? 0 : (p == 1 ? 1 : (p == 2 ? 0 : (p == 3 ? 2 : (p == 4 ? 2 : 1)))); }
 
 }  // namespace
 

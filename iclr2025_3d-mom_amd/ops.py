@@ -31,7 +31,8 @@ def plane_storage(p):
 
 
 def make_plane(C_, H, W, device=None):
-    """A [1,C,H,W] tensor whose memory is channel-last ([H][W][C]) -- the layout libmom4d's kernels read."""
+    """A [1,C,H,W] tensor whose memory is channel-last ([H][W][C]) -- the layout libmom4d's kernels read: one texel is one
+    row of C floats (C = 32: a 128-byte line; C = 16: half of one)."""
     return torch.empty(1, H, W, C_, device=device).permute(0, 3, 1, 2)
 
 
@@ -49,6 +50,9 @@ def _hexplane_desc(planes_by_level, aabb, grads_by_level=None, aabb_host=None):
             st = plane_storage(planes[p])
             if st is None:
                 raise N.MomError("HexPlane planes must be channel-last (use ops.make_plane)")
+            if st.shape[2] != d.channels:
+                raise N.MomError(f"HexPlane planes disagree in channel count: {st.shape[2]} at level {l}, {d.channels} at level 0 "
+                                 "(one count, 16 or 32, for every plane of a field)")
             res[a], res[b] = st.shape[1], st.shape[0]
             d.planes[l][p] = st.data_ptr()
             keep.append(st)
@@ -65,7 +69,8 @@ def _hexplane_desc(planes_by_level, aabb, grads_by_level=None, aabb_host=None):
 
 
 class HexPlaneFunction(torch.autograd.Function):
-    """features[P, L*32] = HexPlaneField(xyz, t) (reference scene/hexplane.py:160-183)."""
+    """features[P, L*C] = HexPlaneField(xyz, t) (reference scene/hexplane.py:160-183), level-major; C = the planes' channel
+    count, 32 or 16 (csrc/hexplane.hip, csrc/hexplane16.hip; any other count is a MomError from the library)."""
 
     @staticmethod
     def forward(ctx, xyz, time, aabb, n_levels, order, aabb_host, plane_orders, *planes):
@@ -76,7 +81,7 @@ class HexPlaneFunction(torch.autograd.Function):
         ctx.aabb_host = aabb_host
         xyz_c = xyz.detach().contiguous().float()
         P = xyz_c.shape[0]
-        feat = torch.empty((P, n_levels * 32), dtype=torch.float32, device=xyz.device)
+        feat = torch.empty((P, n_levels * d.channels), dtype=torch.float32, device=xyz.device)
         # one timestamp per camera (a python float) or per-point timestamps (a tensor, as the reference passes)
         times = time.detach().reshape(-1).contiguous().float() if torch.is_tensor(time) else None
         tval = 0.0 if times is not None else float(time)
@@ -546,6 +551,15 @@ def _buffers_free(views, held_by_cache=1):
     return all(sys.getrefcount(v) <= held_by_cache + 2 for v in views)      # + the loop variable and getrefcount's argument
 
 
+def _reg_row_units(st):
+    """MomRegPlane.W of a channel-last [H, W, C] plane.  The regulariser differences along H for every float of a row and never
+    looks at where a texel ends, and it counts a row in units of 32 floats: W for 32-channel planes, W / 2 for 16-channel ones."""
+    n = st.shape[1] * st.shape[2]
+    if n % 32:
+        raise N.MomError(f"plane_regulation: a plane row of {st.shape[1]} texels x {st.shape[2]} channels is no multiple of 32 floats")
+    return n // 32
+
+
 class PlaneRegFunction(torch.autograd.Function):
     """value = sum_p  w_smooth[p] * smooth2(plane_p) + w_l1[p] * mean|1 - plane_p|."""
 
@@ -561,7 +575,7 @@ class PlaneRegFunction(torch.autograd.Function):
             for i, p in enumerate(planes):
                 st = plane_storage(p)
                 arr[i].plane, arr[i].grad = st.data_ptr(), None
-                arr[i].H, arr[i].W = st.shape[0], st.shape[1]
+                arr[i].H, arr[i].W = st.shape[0], _reg_row_units(st)
                 arr[i].w_smooth, arr[i].w_l1, arr[i].grad_scale = float(w_smooth[i]), float(w_l1[i]), 0.0
             c = PlaneRegFunction._fwd_cache = (key, arr)
         arr = c[1]
@@ -617,7 +631,7 @@ class PlaneRegFunction(torch.autograd.Function):
                 grads.append(gv.permute(2, 0, 1).unsqueeze(0))
                 target = plane_storage(held[i]) if in_place[i] else gv
                 arr[i].plane, arr[i].grad = st.data_ptr(), target.data_ptr()
-                arr[i].H, arr[i].W = st.shape[0], st.shape[1]
+                arr[i].H, arr[i].W = st.shape[0], _reg_row_units(st)
                 arr[i].w_smooth, arr[i].w_l1, arr[i].grad_scale = float(w_smooth[i]), float(w_l1[i]), 1.0
             val = torch.empty(1, dtype=torch.float32, device=planes[0].device)
             c = (key, flat, grads, arr, val)

@@ -80,7 +80,10 @@ class Deformation(nn.Module):
 
     def _fusable(self):
         a = self.args
-        return (self.W == 64 and self.D == 0 and self.grid.feat_dim == 64 and self.grid_pe == 0 and not a.no_grid
+        # 64 features from exactly two levels = 32 channels per plane: the shape mom_deform_field_supported accepts and the fused
+        # kernels assume (16 channels x 4 levels also gives 64 features, and goes op by op)
+        return (self.W == 64 and self.D == 0 and self.grid.feat_dim == 64 and len(self.grid.grids) == 2 and self.grid_pe == 0
+                and not a.no_grid
                 and not a.static_mlp and not a.no_dx and not a.no_ds and not a.no_dr and a.no_do and a.no_dshs
                 and not a.apply_rotation)
 

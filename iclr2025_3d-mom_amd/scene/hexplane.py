@@ -1,9 +1,12 @@
 """HexPlaneField with the reference's constructor, parameter names and numerics
 (reference scene/hexplane.py:109-183), whose forward/backward run as two fused HIP kernels
-(csrc/hexplane.hip) instead of 12 grid_sample launches per direction.
+(csrc/hexplane.hip for 32-channel planes, csrc/hexplane16.hip for 16-channel ones) instead of 12 grid_sample
+launches per direction.
 
 Planes keep the reference's logical shape [1, C, H, W] (regularisers, state_dict and the optimizer see
-exactly what they see in the reference) but live in memory channel-last, so one texel is one 128-byte line."""
+exactly what they see in the reference) but live in memory channel-last, so one texel is one row of C floats:
+a 128-byte line at output_coordinate_dim = 32, half a line at 16.  Other channel counts construct (feat_dim
+follows the planes) but the lookup raises: there is no fallback behind the ops."""
 import itertools
 from typing import Optional, Sequence
 

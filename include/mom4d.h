@@ -305,21 +305,24 @@ int mom_knn_mean_dist2(int P, const float* points /* [P,3] */, float* mean_dist2
  * the raw timestamp used as the 4th grid coordinate (gaussian_renderer/__init__.py:56). */
 typedef struct MomHexPlane {
     int levels;            /* 1..4 */
-    int channels;          /* must be 32 */
+    int channels;          /* 32 or 16 (every plane of the field) */
     int res[4][4];         /* per level: resolution along x, y, z, t */
     const float* planes[4][6];
     float* grads[4][6];    /* backward only: same layout as planes, ACCUMULATED into (+=, float atomics) */
     float aabb[6];
 } MomHexPlane;
-/* feat [P, levels*32] row-major.  times: optional per-point timestamps [P]; null -> `time` for all points
- * (render() uses one timestamp per camera). */
+/* Planes are channel-last, [H][W][channels] floats.  feat [P, levels*channels] row-major, level-major within a row.  times:
+ * optional per-point timestamps [P]; null -> `time` for all points (render() uses one timestamp per camera).  channels must be
+ * 32 or 16 (MOM_EINVAL otherwise): 32 lanes own one (point, level) at 32 channels, 16 lanes at 16 (csrc/hexplane16.hip). */
 int mom_hexplane_forward(const MomHexPlane* hp, int P, const float* xyz, const float* times, float time,
                          const uint32_t* order, float* feat, mom_stream_t stream);
-/* dfeat [P, levels*32]; plane gradients accumulate into hp->grads; dxyz [P,3] (may be null) is ACCUMULATED into.
+/* dfeat [P, levels*channels]; plane gradients accumulate into hp->grads; dxyz [P,3] (may be null) is ACCUMULATED into.
  * plane_order / plane_inverse ([3][levels][P] each, from mom_hexplane_orders) and scratch (mom_hexplane_backward_scratch_bytes)
  * select the two-pass path (times == null only): pass 1 gathers in `order` and stores each space plane's per-point gradient
  * row at the point's position in that plane's order, pass 2 walks each space plane in its order and turns runs of points of
- * one texel cell into one row of float atomics.  Any of the three null: the generic path (24 atomic rows per point and level). */
+ * one texel cell into one row of float atomics.  Any of the three null: the generic path (24 atomic rows per point and level).
+ * Both paths exist for 32 and for 16 channels; the scratch size follows the channel count (six rows of `channels` floats per
+ * point and level). */
 size_t mom_hexplane_backward_scratch_bytes(const MomHexPlane* hp, int P);
 int mom_hexplane_backward(const MomHexPlane* hp, int P, const float* xyz, const float* times, float time,
                           const uint32_t* order, const float* dfeat, float* dxyz, const uint32_t* plane_order,
@@ -439,7 +442,8 @@ int mom_ssim_backward_slab(int C, int H, int W, size_t chan_stride, const float*
 /* ---- HexPlane regularisers (scene/gaussian_model.py:730-769, scene/regulation.py:22-28) ----
  * value = sum over planes of w_smooth * mean((p[h+2]-2p[h+1]+p[h])^2) + w_l1 * mean|1-p|
  * (second difference along H, the reference's dim -2); if grad != null, grad_scale * d value / d plane is
- * ADDED into it.  Channel-last [H][W][32] planes as above. */
+ * ADDED into it.  Channel-last planes as above; a row is W * 32 floats, and the differences run along H per float: a [H][W][32]
+ * plane passes its W, a [H][W][16] plane W / 2 (W even). */
 #define MOM_REG_MAX_PLANES 24
 typedef struct MomRegPlane {
     const float* plane;
