@@ -206,6 +206,12 @@ def _sig(lib):
     lib.mom_deform_backward_scratch_bytes.argtypes = [i32]
     lib.mom_deform_backward.argtypes = [C.POINTER(MomDeformMLP), i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mom_deform_backward_split.argtypes = [C.POINTER(MomDeformMLP), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    # the same four with in_features (64, or 32: csrc/deform_mlp32.hip) after P
+    lib.mom_deform_forward_n.argtypes = [C.POINTER(MomDeformMLP), i32, i32, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]
+    lib.mom_deform_forward_activated_n.argtypes = [C.POINTER(MomDeformMLP), i32, i32, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp,
+                                                   vp, vp, vp, vp]
+    lib.mom_deform_backward_n.argtypes = [C.POINTER(MomDeformMLP), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mom_deform_backward_split_n.argtypes = [C.POINTER(MomDeformMLP), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mom_deform_field_supported.argtypes = [C.POINTER(MomHexPlane)]
     lib.mom_deform_field_scratch_bytes.restype = sz
     lib.mom_deform_field_scratch_bytes.argtypes = [C.POINTER(MomHexPlane), i32]
@@ -260,6 +266,7 @@ EXPORTS = [
     "mom_comm_world", "mom_comm_rank", "mom_comm_group_start", "mom_comm_group_end", "mom_comm_all_reduce", "mom_comm_all_gather",
     "mom_comm_reduce_scatter",
     "mom_raster_backward_acc", "mom_raster_backward_geometry_acc",
+    "mom_deform_forward_n", "mom_deform_forward_activated_n", "mom_deform_backward_n", "mom_deform_backward_split_n",
 ]
 
 

@@ -267,8 +267,27 @@ class DeformMLPFunction(torch.autograd.Function):
         return d
 
     @staticmethod
+    def check_shapes(feat, params):
+        """The trunk width (32 or 64) of a call, from feat [P,width]; MomError unless W0 is [64,width] and the other 13 tensors
+        have the shapes _desc hands to the kernels as raw pointers (a narrower tensor would be read past its end)."""
+        if feat.dim() != 2 or feat.shape[1] not in (32, 64):
+            raise N.MomError(f"deform_mlp: feat must be [P,32] or [P,64], got {tuple(feat.shape)}")
+        n_in = int(feat.shape[1])
+        want = [(64, n_in), (64,)]
+        for nout in (3, 3, 4):
+            want += [(64, 64), (64,), (nout, 64), (nout,)]
+        if len(params) != len(want):
+            raise N.MomError(f"deform_mlp: {len(want)} parameter tensors expected, got {len(params)}")
+        for i, (p, w) in enumerate(zip(params, want)):
+            if tuple(p.shape) != w or p.dtype != torch.float32:
+                raise N.MomError(f"deform_mlp: parameter {i} must be float32 {w} for {n_in} features, "
+                                 f"got {p.dtype} {tuple(p.shape)}")
+        return n_in
+
+    @staticmethod
     def forward(ctx, feat, xyz, scaling, rotation, scene_flow, flow_coef, *params):
         _need_cuda(feat, "deform_mlp")
+        n_in = DeformMLPFunction.check_shapes(feat, params)
         lib = N.lib()
         P = feat.shape[0]
         ps = [p.detach().contiguous() for p in params]
@@ -280,10 +299,10 @@ class DeformMLPFunction(torch.autograd.Function):
         ro = torch.empty_like(rotation)
         xyz_c, scal_c, rot_c, flow_c = (t.detach().contiguous() for t in (xyz, scaling, rotation, scene_flow))
         need_bwd = any(ctx.needs_input_grad)
-        a0 = torch.empty_like(feat_c) if need_bwd else None
-        N.check(lib.mom_deform_forward(C.byref(d), P, feat_c.data_ptr(), xyz_c.data_ptr(), scal_c.data_ptr(), rot_c.data_ptr(),
-                                       flow_c.data_ptr(), float(flow_coef), pts.data_ptr(), sc.data_ptr(), ro.data_ptr(),
-                                       None if a0 is None else a0.data_ptr(), s), "mom_deform_forward")
+        a0 = torch.empty((P, 64), dtype=torch.float32, device=feat_c.device) if need_bwd else None      # relu(h0), whatever the trunk reads
+        N.check(lib.mom_deform_forward_n(C.byref(d), P, n_in, feat_c.data_ptr(), xyz_c.data_ptr(), scal_c.data_ptr(), rot_c.data_ptr(),
+                                         flow_c.data_ptr(), float(flow_coef), pts.data_ptr(), sc.data_ptr(), ro.data_ptr(),
+                                         None if a0 is None else a0.data_ptr(), s), "mom_deform_forward_n")
         ctx.save_for_backward(feat_c, a0 if a0 is not None else feat_c, *ps)
         return pts, sc, ro
 
@@ -295,11 +314,11 @@ class DeformMLPFunction(torch.autograd.Function):
         grads = [torch.zeros_like(p) for p in ps]
         d = DeformMLPFunction._desc(ps, grads)
         dpts, dsc, dro = dpts.contiguous(), dsc.contiguous(), dro.contiguous()
-        dfeat = torch.empty_like(feat_c)
+        dfeat = torch.empty_like(feat_c)                # [P,32] or [P,64]: the trunk's width
         scratch = torch.empty(lib.mom_deform_backward_scratch_bytes(P), dtype=torch.uint8, device=feat_c.device)
-        N.check(lib.mom_deform_backward(C.byref(d), P, feat_c.data_ptr(), a0.data_ptr(), dpts.data_ptr(), dsc.data_ptr(),
-                                        dro.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), N.current_stream()),
-                "mom_deform_backward")
+        N.check(lib.mom_deform_backward_n(C.byref(d), P, feat_c.shape[1], feat_c.data_ptr(), a0.data_ptr(), dpts.data_ptr(),
+                                          dsc.data_ptr(), dro.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), N.current_stream()),
+                "mom_deform_backward_n")
         # identity paths: pts = xyz + ..., scales = scaling + ..., rots = rotation + ...; scene_flow has no grad
         return (dfeat, dpts, dsc, dro, None, None, *grads)
 

@@ -87,6 +87,20 @@ class Deformation(nn.Module):
                 and not a.static_mlp and not a.no_dx and not a.no_ds and not a.no_dr and a.no_do and a.no_dshs
                 and not a.apply_rotation)
 
+    def _mlp_fusable(self):
+        """The fused MLP op (ops.deform_mlp) applies: the _fusable() model, or the same network on 32 features from exactly two
+        levels of 16 channels (dnerf/eulerian_150_16; csrc/deform_mlp32.hip).  Wider than _fusable() on purpose: the fused step,
+        the fused autograd path and the render pool key on _fusable() and keep declining 16-channel fields."""
+        if self._fusable():
+            return True
+        a = self.args
+        g = self.grid
+        return (self.W == 64 and self.D == 0 and g.feat_dim == 32 and len(g.grids) == 2
+                and all(p.shape[1] == 16 for lv in g.grids for p in lv) and self.grid_pe == 0
+                and not a.no_grid
+                and not a.static_mlp and not a.no_dx and not a.no_ds and not a.no_dr and a.no_do and a.no_dshs
+                and not a.apply_rotation)
+
     def _fused_params(self):
         """The 14 tensors of the trunk and the three heads, in the kernels' order.  Cached while the first and the last are the
         objects they were (walking four nn.Sequential containers costs 33 us per call, and a training step asks once)."""
@@ -101,8 +115,9 @@ class Deformation(nn.Module):
 
     def forward_dynamic(self, rays_pts_emb, scales_emb, rotations_emb, opacity_emb, shs_emb, time_feature, time_emb,
                         scene_flow, frame_num, delta_scale):
-        if self._fusable():
-            # shipped configuration: HexPlane lookup + trunk + three heads + residuals as two fused HIP ops
+        if self._mlp_fusable():
+            # shipped configuration, or its network on two levels of 16 channels: HexPlane lookup + trunk + three heads + residuals
+            # as two fused HIP ops
             from .. import ops
             t = time_emb[:, :1] if torch.is_tensor(time_emb) else time_emb
             feat = self.grid(rays_pts_emb[:, :3], t)

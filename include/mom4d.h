@@ -463,7 +463,7 @@ int mom_plane_regulation_grad(const MomRegPlane* planes, int count, float* value
  * (flow_coef = delta_scale * frame_num, deformation.py:114).  Weights are nn.Linear tensors ([out,in] row-major);
  * both kernels are persistent and keep all four 64x64 matrices in LDS. */
 typedef struct MomDeformMLP {
-    const float *W0, *b0;            /* feature_out.0: [64,64], [64] */
+    const float *W0, *b0;            /* feature_out.0: [64,64], [64]  ([64,in_features] for the _n entry points below) */
     const float *W1[3], *b1[3];      /* {pos,scales,rotations}_deform.1: [64,64], [64] */
     const float *W2[3], *b2[3];      /* {pos,scales,rotations}_deform.3: [3|3|4,64], [3|3|4] */
     float *dW0, *db0, *dW1[3], *db1[3], *dW2[3], *db2[3];   /* backward only: ACCUMULATED into (+=) */
@@ -497,6 +497,25 @@ int mom_deform_backward(const MomDeformMLP* w, int P, const float* feat, const f
 int mom_deform_backward_split(const MomDeformMLP* w, int P, const float* feat, const float* a0, const float* dpts,
                               const float* dscales, const float* drots, float* dfeat, void* scratch, mom_stream_t stream,
                               mom_stream_t dw_stream);
+/* The four calls above for a trunk of `in_features` inputs (csrc/deform_mlp32.hip).  MomDeformMLP keeps its layout; W0 and dW0 point
+ * at [64,in_features] tensors, feat and dfeat are [P,in_features], everything else (a0 [P,64], the heads, the scratch size) is as above.
+ *   in_features == 64: exactly the call without _n.
+ *   in_features == 32 (two HexPlane levels of 16 channels, dnerf/eulerian_150_16): fp32 kernels of their own.  The backward is the
+ *     two-kernel f32 form whatever MOM_MLP_BWD says -- unset, empty, "b3" or "split"; there is no bf16 one-kernel form for this
+ *     shape -- with the stream contract of that form; any other value is MOM_EINVAL as above.
+ *   anything else: MOM_EINVAL, before anything is launched. */
+int mom_deform_forward_n(const MomDeformMLP* w, int P, int in_features, const float* feat /* [P,in_features] */, const float* xyz,
+                         const float* scaling, const float* rotation, const float* scene_flow, float flow_coef, float* pts,
+                         float* scales, float* rots, float* a0_save, mom_stream_t stream);
+int mom_deform_forward_activated_n(const MomDeformMLP* w, int P, int in_features, const float* feat, const float* xyz,
+                                   const float* scaling, const float* rotation, const float* scene_flow, float flow_coef, float* pts,
+                                   float* scales, float* rots, float* a0_save, const float* opacity_raw, float* scales_act,
+                                   float* rots_act, float* opacity_act, mom_stream_t stream);
+int mom_deform_backward_n(const MomDeformMLP* w, int P, int in_features, const float* feat, const float* a0, const float* dpts,
+                          const float* dscales, const float* drots, float* dfeat, void* scratch, mom_stream_t stream);
+int mom_deform_backward_split_n(const MomDeformMLP* w, int P, int in_features, const float* feat, const float* a0, const float* dpts,
+                                const float* dscales, const float* drots, float* dfeat, void* scratch, mom_stream_t stream,
+                                mom_stream_t dw_stream);
 
 /* ---- deformation field in one pass (the render() case: ONE timestamp for every point) ----
  * deform_network.forward = HexPlaneField lookup + trunk + heads (scene/deformation.py:97-153, scene/hexplane.py:160-183) as a

@@ -1,0 +1,290 @@
+"""The fused deformation MLP with a 32-feature trunk (csrc/deform_mlp32.hip; dnerf/eulerian_150_16: two HexPlane levels of
+16 channels) on the GPU: against oracle.torch_ref.deform_mlp on the CPU, against the 64-feature kernels on the same features
+padded with zero columns (the same k-ascending fp32 chain: equal bits), its activated and two-stream forms, its refusals, the
+routing of a model of that shape, and determinism.
+
+Tolerances of the parity test are those of tests/test_ops_gpu.py::test_fused_deform_mlp_forward_backward, with its rule for the
+per-Gaussian gradients: a hidden unit whose pre-activation is within rounding of zero may take the other ReLU branch, which
+changes that Gaussian's gradient rows, so they may differ on at most 2 Gaussians.  That cap is a condition on the inputs: with
+the seeds used here (seed = P) the reference in fp64 on the CPU has a pre-activation within 2^-24 * sum |terms| of zero (the
+worst rounding of an fp32 chain in any order, inherited error of relu(h0) included) on 0, 0, 0, 0, 0 and 2 Gaussians at the six
+sizes (smallest |pre-activation| 1.3e-6 at P = 20011, 8.4e-6 at P = 1000), and the reference in fp32 against itself in fp64
+flips no ReLU and has no gradient row beyond the tolerance at any size."""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import torch_ref as tr
+
+pytestmark = pytest.mark.gpu
+
+pkg = "iclr2025_3d-mom_amd"
+ops = importlib.import_module(pkg + ".ops")
+N = importlib.import_module(pkg + "._native")
+
+
+def _params(mk, n_in=32):
+    ps = [mk(64, n_in), mk(64)]
+    for nout in (3, 3, 4):
+        ps += [mk(64, 64), mk(64), mk(nout, 64), mk(nout)]
+    return ps
+
+
+def _state(P, seed):
+    g = torch.Generator().manual_seed(seed)
+    mk = lambda *s: (torch.randn(*s, generator=g) * 0.3).cuda()
+    return _params(mk), mk
+
+
+def _row_tol(b):
+    return 2e-4 * np.abs(b) + 2e-5 * max(1.0, float(np.abs(b).max()))
+
+
+@pytest.mark.parametrize("P", [1, 31, 64, 65, 1000, 20011])
+def test_forward_and_every_gradient_match_the_cpu_reference(P):
+    g = torch.Generator().manual_seed(P)
+    mk = lambda *s: (torch.randn(*s, generator=g) * 0.3)
+    params = _params(mk)
+    feat, xyz, scal, rot, flow = mk(P, 32) * 3, mk(P, 3), mk(P, 3), mk(P, 4), mk(P, 3)
+    ws = [mk(P, 3), mk(P, 3), mk(P, 4)]
+
+    def run(dev, fn):
+        ps = [p.clone().to(dev).requires_grad_(True) for p in params]
+        ins = [t.clone().to(dev).requires_grad_(True) for t in (feat, xyz, scal, rot)]
+        o = fn(ins[0], ins[1], ins[2], ins[3], flow.to(dev), 0.7, ps)
+        sum((a * w.to(dev)).sum() for a, w in zip(o, ws)).backward()
+        return [t.detach().cpu().numpy() for t in o], [t.grad.cpu().numpy() for t in ins], [p.grad.cpu().numpy() for p in ps]
+
+    o_ref, gi_ref, gp_ref = run("cpu", tr.deform_mlp)
+    o, gi, gp = run("cuda", ops.deform_mlp)
+    assert gi[0].shape == (P, 32) and gp[0].shape == (64, 32)
+    for a, b in zip(o, o_ref):
+        np.testing.assert_allclose(a, b, rtol=2e-5, atol=2e-5)
+    for a, b in zip(gi, gi_ref):
+        bad_rows = (np.abs(a - b) > _row_tol(b)).reshape(P, -1).any(1).sum()
+        print("per-Gaussian gradient", a.shape, "rows beyond tolerance:", int(bad_rows), "max |diff| %.3e" % float(np.abs(a - b).max()))
+        assert bad_rows <= 2, (a.shape, int(bad_rows))
+    for a, b in zip(gp, gp_ref):
+        rel = np.linalg.norm(a.astype(np.float64) - b) / (np.linalg.norm(b) + 1e-30)
+        print("parameter gradient", a.shape, "relative norm %.3e" % rel)
+        assert rel <= 2e-3, (a.shape, rel)
+
+
+def _forward(lib, d, P, n_in, feat, xyz, scal, rot, flow, a0=True):
+    pts, sc_d, rot_d = (torch.full((P, k), float("nan"), device="cuda") for k in (3, 3, 4))
+    a0_t = torch.full((P, 64), float("nan"), device="cuda") if a0 else None
+    N.check(lib.mom_deform_forward_n(C.byref(d), P, n_in, feat.data_ptr(), xyz.data_ptr(), scal.data_ptr(), rot.data_ptr(),
+                                     flow.data_ptr(), 0.7, pts.data_ptr(), sc_d.data_ptr(), rot_d.data_ptr(),
+                                     None if a0_t is None else a0_t.data_ptr(), N.current_stream()), "fwd")
+    return pts, sc_d, rot_d, a0_t
+
+
+@pytest.mark.parametrize("P", [1, 31, 65, 1000, 20011])
+def test_same_bits_as_the_64_feature_kernels_on_zero_padded_features(P, monkeypatch):
+    """feat [P,32] | 0 and W0 [64,32] | 0 through the 64-feature forward: its k-ascending chain gains only + 0 * 0 terms, so
+    pts, scales, rots and relu(h0) are equal; with the f32 backward on both sides dfeat is the padded run's first 32 columns."""
+    monkeypatch.setenv("MOM_MLP_BWD", "split")
+    params, mk = _state(P, 40 + P)
+    feat, xyz, scal, rot, flow = mk(P, 32) * 3, mk(P, 3), mk(P, 3), mk(P, 4), mk(P, 3)
+    dpts, dsc, drot = mk(P, 3), mk(P, 3), mk(P, 4)
+    lib, s = N.lib(), N.current_stream()
+    feat_pad = torch.cat([feat, torch.zeros(P, 32, device="cuda")], 1).contiguous()
+    params_pad = [torch.cat([params[0], torch.zeros(64, 32, device="cuda")], 1).contiguous()] + params[1:]
+    scratch = torch.empty(lib.mom_deform_backward_scratch_bytes(P), dtype=torch.uint8, device="cuda")
+
+    def run(n_in, f, ps):
+        grads = [torch.zeros_like(p) for p in ps]
+        d = ops.DeformMLPFunction._desc(ps, grads)
+        if n_in == 64:       # the entry points as they were
+            pts, sc_d, rot_d, a0 = (torch.full((P, k), float("nan"), device="cuda") for k in (3, 3, 4, 64))
+            N.check(lib.mom_deform_forward(C.byref(d), P, f.data_ptr(), xyz.data_ptr(), scal.data_ptr(), rot.data_ptr(), flow.data_ptr(),
+                                           0.7, pts.data_ptr(), sc_d.data_ptr(), rot_d.data_ptr(), a0.data_ptr(), s), "fwd64")
+        else:
+            pts, sc_d, rot_d, a0 = _forward(lib, d, P, 32, f, xyz, scal, rot, flow)
+        dfeat = torch.full((P, n_in), float("nan"), device="cuda")
+        N.check(lib.mom_deform_backward_n(C.byref(d), P, n_in, f.data_ptr(), a0.data_ptr(), dpts.data_ptr(), dsc.data_ptr(),
+                                          drot.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), s), "bwd")
+        torch.cuda.synchronize()
+        return (pts, sc_d, rot_d, a0), dfeat, grads
+
+    o32, df32, g32 = run(32, feat, params)
+    o64, df64, g64 = run(64, feat_pad, params_pad)
+    for name, a, b in zip(("pts", "scales", "rots", "a0"), o32, o64):
+        assert bool(torch.isfinite(a).all()) and torch.equal(a, b), name
+    assert float(o32[3].max()) > 0 and float(o32[3].min()) == 0          # relu(h0): both branches taken
+    assert bool((df64[:, 32:] == 0).all())                              # zero weights: exactly zero
+    a, b = df32.cpu().numpy(), df64[:, :32].cpu().numpy()
+    bad_rows = (np.abs(a - b) > _row_tol(b)).reshape(P, -1).any(1).sum()
+    print("dfeat rows beyond tolerance:", int(bad_rows), "max |diff| %.3e" % float(np.abs(a - b).max()))
+    assert np.isfinite(a).all() and bad_rows <= 2, int(bad_rows)
+    assert g32[0].shape == (64, 32) and bool((g64[0][:, 32:] == 0).all())
+    g64[0] = g64[0][:, :32]
+    for i, (x, y) in enumerate(zip(g32, g64)):      # the same terms through float atomics in another order
+        rel = float((x.double() - y.double()).norm() / (y.double().norm() + 1e-30))
+        assert rel <= 2e-3, (i, rel)
+
+
+@pytest.mark.parametrize("P", [1, 65, 1000])
+def test_activated_form_equals_the_plain_form_plus_the_activation_kernel(P):
+    params, mk = _state(P, 100 + P)
+    feat, xyz, scal, rot, flow, opac = mk(P, 32) * 3, mk(P, 3), mk(P, 3), mk(P, 4), mk(P, 3), mk(P, 1)
+    d = ops.DeformMLPFunction._desc(params)
+    lib, s = N.lib(), N.current_stream()
+    e = lambda *sh: torch.full(sh, float("nan"), device="cuda")
+    pts, sc_d, rot_d, _ = _forward(lib, d, P, 32, feat, xyz, scal, rot, flow, a0=False)
+    sc, rt, op = e(P, 3), e(P, 4), e(P, 1)
+    N.check(lib.mom_activations_forward(P, sc_d.data_ptr(), rot_d.data_ptr(), opac.data_ptr(), sc.data_ptr(), rt.data_ptr(),
+                                        op.data_ptr(), s), "act")
+    pts2, sc_d2, rot_d2, sc2, rt2, op2 = e(P, 3), e(P, 3), e(P, 4), e(P, 3), e(P, 4), e(P, 1)
+    N.check(lib.mom_deform_forward_activated_n(C.byref(d), P, 32, feat.data_ptr(), xyz.data_ptr(), scal.data_ptr(), rot.data_ptr(),
+                                               flow.data_ptr(), 0.7, pts2.data_ptr(), sc_d2.data_ptr(), rot_d2.data_ptr(), None,
+                                               opac.data_ptr(), sc2.data_ptr(), rt2.data_ptr(), op2.data_ptr(), s), "fwd_act")
+    torch.cuda.synchronize()
+    for a, b in ((pts, pts2), (sc_d, sc_d2), (rot_d, rot_d2), (sc, sc2), (rt, rt2), (op, op2)):
+        assert torch.isfinite(b).all() and torch.equal(a, b)
+    # the same bits with relu(h0) saved (a grad-mode render() and a no-grad one show the same image)
+    pts3, sc_d3, rot_d3, a0 = _forward(lib, d, P, 32, feat, xyz, scal, rot, flow, a0=True)
+    torch.cuda.synchronize()
+    assert torch.equal(pts, pts3) and torch.equal(sc_d, sc_d3) and torch.equal(rot_d, rot_d3) and bool(torch.isfinite(a0).all())
+    # opacity_act without opacity_raw is refused
+    assert lib.mom_deform_forward_activated_n(C.byref(d), P, 32, feat.data_ptr(), xyz.data_ptr(), scal.data_ptr(), rot.data_ptr(),
+                                              flow.data_ptr(), 0.7, pts2.data_ptr(), sc_d2.data_ptr(), rot_d2.data_ptr(), None, None,
+                                              None, None, op2.data_ptr(), s) == N.MOM_EINVAL
+
+
+def test_backward_on_a_second_stream_equals_the_single_stream_call():
+    P = 7001
+    params, mk = _state(P, 7)
+    feat, xyz, scal, rot, flow = mk(P, 32) * 3, mk(P, 3), mk(P, 3), mk(P, 4), mk(P, 3)
+    dpts, dsc, drot = mk(P, 3), mk(P, 3), mk(P, 4)
+    lib, s = N.lib(), N.current_stream()
+    side = torch.cuda.Stream()
+
+    def run(second):
+        grads = [torch.zeros_like(p) for p in params]
+        d = ops.DeformMLPFunction._desc(params, grads)
+        pts, sc_d, rot_d, a0 = _forward(lib, d, P, 32, feat, xyz, scal, rot, flow)
+        dfeat = torch.empty(P, 32, device="cuda")
+        scratch = torch.empty(lib.mom_deform_backward_scratch_bytes(P), dtype=torch.uint8, device="cuda")
+        N.check(lib.mom_deform_backward_split_n(C.byref(d), P, 32, feat.data_ptr(), a0.data_ptr(), dpts.data_ptr(), dsc.data_ptr(),
+                                                drot.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), s,
+                                                side.cuda_stream if second else s), "bwd")
+        if second:
+            torch.cuda.current_stream().wait_stream(side)      # the caller's join
+        torch.cuda.synchronize()
+        return dfeat, grads
+
+    f1, g1 = run(False)
+    f2, g2 = run(True)
+    assert torch.equal(f1, f2) and float(f1.abs().max()) > 0
+    for a, b in zip(g1, g2):         # float atomics: same terms, possibly another order
+        assert float(a.abs().max()) > 0
+        assert float((a - b).abs().max()) <= 1e-5 * max(1.0, float(a.abs().max()))
+
+
+def test_every_valid_name_of_the_backward_form_runs_the_f32_kernels_and_an_unknown_one_is_refused(monkeypatch):
+    P = 1000
+    params, mk = _state(P, 3)
+    feat, a0, dpts, dsc, drot = mk(P, 32), mk(P, 64).relu(), mk(P, 3), mk(P, 3), mk(P, 4)
+    lib, s = N.lib(), N.current_stream()
+    scratch = torch.empty(lib.mom_deform_backward_scratch_bytes(P), dtype=torch.uint8, device="cuda")
+    seen = []
+    for mode, want in ((None, N.MOM_OK), ("", N.MOM_OK), ("b3", N.MOM_OK), ("split", N.MOM_OK), ("fused", N.MOM_EINVAL), ("f32", N.MOM_EINVAL)):
+        if mode is None:
+            monkeypatch.delenv("MOM_MLP_BWD", raising=False)
+        else:
+            monkeypatch.setenv("MOM_MLP_BWD", mode)
+        grads = [torch.zeros_like(p) for p in params]          # (kept alive: the descriptor holds raw pointers)
+        d = ops.DeformMLPFunction._desc(params, grads)
+        dfeat = torch.full((P, 32), float("nan"), device="cuda")
+        rc = lib.mom_deform_backward_split_n(C.byref(d), P, 32, feat.data_ptr(), a0.data_ptr(), dpts.data_ptr(), dsc.data_ptr(),
+                                             drot.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), s, s)
+        torch.cuda.synchronize()
+        assert rc == want, (mode, rc)
+        assert bool(torch.isfinite(dfeat).all()) == (want == N.MOM_OK), mode       # refused before any launch: dfeat untouched
+        if want == N.MOM_OK:
+            seen.append(dfeat)
+    for other in seen[1:]:           # one form behind every valid name
+        assert torch.equal(seen[0], other)
+
+
+def test_refusals():
+    P = 33
+    params, mk = _state(P, 5)
+    xyz, scal, rot, flow = mk(P, 3), mk(P, 3), mk(P, 4), mk(P, 3)
+    for width in (16, 48):
+        g = torch.Generator().manual_seed(width)
+        ps = _params(lambda *s: (torch.randn(*s, generator=g) * 0.3).cuda(), width)
+        with pytest.raises(N.MomError):
+            ops.deform_mlp(mk(P, width), xyz, scal, rot, flow, 0.7, ps)
+    params64, _ = _state(P, 6)
+    params64[0] = mk(64, 64)
+    with pytest.raises(N.MomError):
+        ops.deform_mlp(mk(P, 32), xyz, scal, rot, flow, 0.7, params64)         # W0 [64,64] with feat [P,32]
+    with pytest.raises(N.MomError):
+        ops.deform_mlp(mk(P, 64), xyz, scal, rot, flow, 0.7, params)           # W0 [64,32] with feat [P,64]
+    # the C entry: in_features = 48 is refused before any launch (the outputs keep their NaNs)
+    lib, s = N.lib(), N.current_stream()
+    d = ops.DeformMLPFunction._desc(params, [torch.zeros_like(p) for p in params])
+    feat = mk(P, 64)
+    e = lambda *sh: torch.full(sh, float("nan"), device="cuda")
+    pts, sc_d, rot_d, a0, dfeat = e(P, 3), e(P, 3), e(P, 4), e(P, 64), e(P, 64)
+    scratch = torch.empty(lib.mom_deform_backward_scratch_bytes(P), dtype=torch.uint8, device="cuda")
+    assert lib.mom_deform_forward_n(C.byref(d), P, 48, feat.data_ptr(), xyz.data_ptr(), scal.data_ptr(), rot.data_ptr(), flow.data_ptr(),
+                                    0.7, pts.data_ptr(), sc_d.data_ptr(), rot_d.data_ptr(), a0.data_ptr(), s) == N.MOM_EINVAL
+    assert lib.mom_deform_backward_n(C.byref(d), P, 48, feat.data_ptr(), mk(P, 64).data_ptr(), mk(P, 3).data_ptr(), mk(P, 3).data_ptr(),
+                                     mk(P, 4).data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), s) == N.MOM_EINVAL
+    torch.cuda.synchronize()
+    for t in (pts, sc_d, rot_d, a0, dfeat):
+        assert bool(torch.isnan(t).all())
+
+
+def test_a_model_of_the_eulerian_150_16_shape_runs_the_fused_mlp_kernels():
+    """render() + backward of a 16 x 2 model: the profile slots of the MLP kernels count launches (none while its deformation
+    network ran as nn.Linear modules)."""
+    from test_hexplane16_gpu import _model16
+    T = importlib.import_module(pkg + ".train")
+    render = importlib.import_module(pkg + ".gaussian_renderer").render
+    lib = N.lib()
+    slots = {lib.mom_profile_name(k).decode(): k for k in range(32) if lib.mom_profile_name(k)}
+    scene, g, op, pp, hp = _model16(torch.device("cuda"))
+    net = g._deformation.deformation_net
+    assert net._mlp_fusable() and not net._fusable()
+    trainer = T.Trainer(scene, g, op, hp, pp, stage="fine", delta_scale=1, sync_every_step=False, fused=False)
+    assert trainer.fused is None
+    counts = {}
+    try:
+        for name in ("mlp_fwd", "mlp_bwd"):
+            N.check(lib.mom_profile_enable(slots[name], 1), "profile")
+        out = render(trainer.cams[1], g, pp, trainer.background, stage="fine", delta_scale=1)
+        out["render"].sum().backward()
+        torch.cuda.synchronize()
+        for name in ("mlp_fwd", "mlp_bwd"):
+            ms, cnt = C.c_double(), C.c_longlong()
+            N.check(lib.mom_profile_read(slots[name], C.byref(ms), C.byref(cnt), 1), "profile")
+            counts[name] = (int(cnt.value), ms.value)
+    finally:
+        for name in ("mlp_fwd", "mlp_bwd"):
+            lib.mom_profile_enable(slots[name], 0)
+    assert counts["mlp_fwd"][0] >= 1 and counts["mlp_bwd"][0] >= 1, counts
+    assert counts["mlp_fwd"][1] > 0 and counts["mlp_bwd"][1] > 0, counts
+    w0 = net.feature_out[0].weight
+    assert w0.shape == (64, 32) and w0.grad is not None and float(w0.grad.abs().max()) > 0
+
+
+def test_forward_is_deterministic():
+    P = 5000
+    params, mk = _state(P, 9)
+    feat, xyz, scal, rot, flow = mk(P, 32) * 3, mk(P, 3), mk(P, 3), mk(P, 4), mk(P, 3)
+    lib = N.lib()
+    d = ops.DeformMLPFunction._desc(params)
+    first = _forward(lib, d, P, 32, feat, xyz, scal, rot, flow)
+    for _ in range(19):
+        again = _forward(lib, d, P, 32, feat, xyz, scal, rot, flow)
+        torch.cuda.synchronize()
+        for a, b in zip(first, again):
+            assert torch.equal(a, b)
+    assert all(bool(torch.isfinite(t).all()) for t in first) and float(first[0].abs().max()) > 0
