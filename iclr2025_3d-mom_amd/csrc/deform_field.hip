@@ -82,10 +82,13 @@ __device__ __forceinline__ int res_of(const HexArgs& a, int lvl, int k)
     r = lvl == 3 ? r3 : r;
     return r;
 }
+// kForward: the fused forward's records (coordinates as norm_coords_fwd32 has them); the gather of the backward takes norm_coords'
+template <bool kForward>
 __device__ __forceinline__ void make_record(const HexArgs& a, const float* __restrict__ xyz, int g, int lvl, uint4& R0, float4& R1)
 {
     float c[4];
-    norm_coords(a, xyz, g, c);
+    if (kForward) norm_coords_fwd32(a, xyz, g, c);
+    else norm_coords(a, xyz, g, c);
     int i0[3];
     float b[3];
     bool hn[3];
@@ -125,7 +128,7 @@ __device__ __forceinline__ void gather_tile(const HexArgs& a, const LineTab& lt,
         const int lvl = lane >> 5;
         uint4 R0 = make_uint4(0, 0, 0, 0);
         float4 R1 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (g_mine >= 0 && lvl < a.levels) make_record(a, xyz, g_mine, lvl, R0, R1);
+        if (g_mine >= 0 && lvl < a.levels) make_record<true>(a, xyz, g_mine, lvl, R0, R1);
         rec[2 * lane] = R0;
         rec[2 * lane + 1] = make_uint4(__float_as_uint(R1.x), __float_as_uint(R1.y), __float_as_uint(R1.z), 0u);
     }
@@ -456,7 +459,7 @@ hexplane_bwd6_gather_kernel(HexArgs a, LineTab lt, int nchunks, const float* __r
                 uint32_t iv[3];
 #pragma unroll
                 for (int k = 0; k < 3; k++) iv[k] = inv[((size_t)k * a.levels + lvl) * a.P + g_mine];
-                make_record(a, xyz, g_mine, lvl, R0, R1);
+                make_record<false>(a, xyz, g_mine, lvl, R0, R1);
                 float cc[4];
                 norm_coords(a, xyz, g_mine, cc);
                 asm volatile("" :: "v"(iv[0]), "v"(iv[1]), "v"(iv[2]), "v"(cc[0]), "v"(cc[1]), "v"(cc[2]));

@@ -27,7 +27,7 @@ __global__ void __launch_bounds__(256) hexplane_fwd_kernel(HexArgs a, const floa
     if (gi >= a.P) return;
     const int g = a.order ? (int)a.order[gi] : gi;   // spatially sorted processing order (speed only)
     float c[4];
-    norm_coords(a, xyz, g, c);
+    norm_coords_fwd32(a, xyz, g, c);
     float prod = 1.f;
 #pragma unroll
     for (int p = 0; p < 6; p++) {
@@ -193,7 +193,7 @@ hexplane_fwd4_kernel(HexArgs a, int nchunks, const float* __restrict__ xyz, floa
         __builtin_amdgcn_wave_barrier();
         if (g_mine >= 0) {
             float c[4];
-            norm_coords(a, xyz, g_mine, c);
+            norm_coords_fwd32(a, xyz, g_mine, c);
 #pragma unroll
             for (int p = 0; p < 6; p++)
                 make_rec_fwd(c[kCombA[p]], c[kCombB[p]], a.res[lvl][kCombA[p]], a.res[lvl][kCombB[p]], s_off[wv][lane][p], s_wt[wv][lane][p]);
@@ -449,7 +449,7 @@ hexplane_bwd5_scatter_kernel(HexArgs a, int per_half, const float* __restrict__ 
         {
             const bool on = ch < npts;
             const int g = (int)ord[base + (on ? ch : 0)];
-            const float cx = (xyz[3 * g + ca] - lo_a) * sc_a - 1.0f, cy = (xyz[3 * g + cb] - lo_b) * sc_b - 1.0f;
+            const float cx = norm_coord(xyz[3 * g + ca], lo_a, sc_a), cy = norm_coord(xyz[3 * g + cb], lo_b, sc_b);
             float gxm, gym;
             const float ix = unnorm_clip(cx, Wd, gxm), iy = unnorm_clip(cy, Hd, gym);
             const int x0 = (int)floorf(ix), y0 = (int)floorf(iy);
@@ -601,8 +601,8 @@ plane_key_kernel(HexArgs a, int ca, int cb, int Wd, int Hd, const float* __restr
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.P) return;
-    const float cx = (xyz[3 * i + ca] - a.a0[ca]) * (2.0f / (a.a1[ca] - a.a0[ca])) - 1.0f;
-    const float cy = (xyz[3 * i + cb] - a.a0[cb]) * (2.0f / (a.a1[cb] - a.a0[cb])) - 1.0f;
+    const float cx = norm_coord(xyz[3 * i + ca], a.a0[ca], 2.0f / (a.a1[ca] - a.a0[ca]));
+    const float cy = norm_coord(xyz[3 * i + cb], a.a0[cb], 2.0f / (a.a1[cb] - a.a0[cb]));
     float gm;
     const int x0 = (int)floorf(unnorm_clip(cx, Wd, gm)), y0 = (int)floorf(unnorm_clip(cy, Hd, gm));
     keys[i] = spread16((unsigned)x0) | (spread16((unsigned)y0) << 1);

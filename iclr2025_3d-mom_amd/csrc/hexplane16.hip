@@ -20,23 +20,6 @@ namespace {
 constexpr int kC = 16;                       // channels = floats of one texel row
 constexpr unsigned kRowB = kC * 4u;          // bytes of one texel row / one gv row
 
-// normalize_aabb as torch evaluates it: the product and the difference rounded one after the other.  (norm_coords of hexplane_dev.h
-// leaves the expression to the compiler, which contracts it into one fma.  The result differs by an ulp at most, and that is
-// visible in one place: a point that DEFINES the box -- set_aabb takes the cloud's extremes -- comes out at 1 - ulp in torch and
-// at exactly 1 contracted, where the border clip takes its position gradient away.)
-__device__ __forceinline__ float norm_coord(float x, float lo, float scale)
-{
-#pragma clang fp contract(off)
-    const float m = (x - lo) * scale;
-    return m - 1.0f;
-}
-__device__ __forceinline__ void norm_coords16(const HexArgs& a, const float* __restrict__ xyz, int g, float c[4])
-{
-#pragma unroll
-    for (int k = 0; k < 3; k++) c[k] = norm_coord(xyz[3 * g + k], a.a0[k], 2.0f / (a.a1[k] - a.a0[k]));
-    c[3] = a.times ? a.times[g] : a.time;
-}
-
 __device__ __forceinline__ float group_sum(float v)
 {
     // sum over the 16 lanes of this group (xor butterflies never cross bit 4)
@@ -54,7 +37,7 @@ __global__ void __launch_bounds__(256) hexplane16_fwd_kernel(HexArgs a, const fl
     if (gi >= a.P) return;
     const int g = a.order ? (int)a.order[gi] : gi;
     float c[4];
-    norm_coords16(a, xyz, g, c);
+    norm_coords(a, xyz, g, c);
     float prod = 1.f;
 #pragma unroll
     for (int p = 0; p < 6; p++) {
@@ -81,7 +64,7 @@ hexplane16_bwd_kernel(HexArgs a, const float* __restrict__ xyz, const float* __r
     const int g = (int)(unit / a.levels), lvl = (int)(unit % a.levels);
     if (g >= a.P) return;
     float c[4];
-    norm_coords16(a, xyz, g, c);
+    norm_coords(a, xyz, g, c);
     PlaneSample s[6];
     float v[6], t00[6], t01[6], t10[6], t11[6];
 #pragma unroll
@@ -179,7 +162,7 @@ hexplane16_fwd4_kernel(HexArgs a, int nchunks, const float* __restrict__ xyz, fl
         __builtin_amdgcn_wave_barrier();
         if (g_mine >= 0) {
             float c[4];
-            norm_coords16(a, xyz, g_mine, c);
+            norm_coords(a, xyz, g_mine, c);
 #pragma unroll
             for (int p = 0; p < 6; p++)
                 make_rec_fwd(c[kCombA[p]], c[kCombB[p]], a.res[lvl][kCombA[p]], a.res[lvl][kCombB[p]], s_off[wv][rec_idx(lane, p)],
@@ -261,7 +244,7 @@ hexplane16_gather_kernel(HexArgs a, int nchunks, const float* __restrict__ xyz, 
         __builtin_amdgcn_wave_barrier();
         if (g_mine >= 0) {
             float c[4];
-            norm_coords16(a, xyz, g_mine, c);
+            norm_coords(a, xyz, g_mine, c);
             unsigned pos[3];
 #pragma unroll
             for (int k = 0; k < 3; k++) pos[k] = inv[((size_t)k * a.levels + lvl) * a.P + g_mine] * (2u * kRowB);   // a slot's two rows are adjacent

@@ -1,5 +1,5 @@
-// Device helpers of the HexPlane kernels shared by hexplane.hip and deform_field.hip: ATen's grid_sampler_2d coordinate
-// arithmetic (align_corners=True, padding_mode='border'), the kernel argument block and its host-side fill.
+// Device helpers of the HexPlane kernels shared by hexplane.hip, hexplane16.hip and deform_field.hip: normalize_aabb and ATen's
+// grid_sampler_2d coordinate arithmetic (align_corners=True, padding_mode='border'), the kernel argument block and its host-side fill.
 #pragma once
 #include "mom_common.h"
 
@@ -43,7 +43,32 @@ struct LineTab {
 __constant__ int kCombA[6] = {0, 0, 0, 1, 1, 2};
 __constant__ int kCombB[6] = {1, 2, 3, 2, 3, 3};
 
+// normalize_aabb as torch evaluates it: the product and the difference rounded one after the other.  Left to the compiler the
+// expression contracts into one fma; the result differs by an ulp at most, and that is visible in one place: a point that DEFINES
+// the box -- set_aabb takes the cloud's extremes -- comes out at 1 - ulp in torch and at exactly 1 contracted, where the border
+// clip takes its position gradient away.  Every backward kernel, the plane-order keys and the 16-channel forward normalise here.  (`scale` = 2.0f / (a1 - a0):
+// torch forms reciprocal(a1 - a0) * 2, the same value, doubling being exact.)
+__device__ __forceinline__ float norm_coord(float x, float lo, float scale)
+{
+#pragma clang fp contract(off)
+    const float m = (x - lo) * scale;
+    return m - 1.0f;
+}
+
 __device__ __forceinline__ void norm_coords(const HexArgs& a, const float* __restrict__ xyz, int g, float c[4])
+{
+#pragma unroll
+    for (int k = 0; k < 3; k++) c[k] = norm_coord(xyz[3 * g + k], a.a0[k], 2.0f / (a.a1[k] - a.a0[k]));
+    c[3] = a.times ? a.times[g] : a.time;
+}
+
+// The 32-channel FORWARD kernels (hexplane_fwd, hexplane_fwd4, the fused field forward's make_record) keep the expression as the
+// compiler contracts it.  A feature is continuous in the coordinate -- across the border clip and across a cell boundary alike --
+// so an ulp of the coordinate is an ulp of the feature, whichever rounding it has; what is NOT continuous is the position gradient
+// (the clip's mask, the cell's slope), and every backward kernel takes both from norm_coord above.  Kept because the features, and
+// with them every deformed position, stay bit for bit what they were: which (pixel, splat) pairs fall on the other side of a
+// compositing threshold than in the CPU oracle follows those last bits.
+__device__ __forceinline__ void norm_coords_fwd32(const HexArgs& a, const float* __restrict__ xyz, int g, float c[4])
 {
 #pragma unroll
     for (int k = 0; k < 3; k++) c[k] = (xyz[3 * g + k] - a.a0[k]) * (2.0f / (a.a1[k] - a.a0[k])) - 1.0f;

@@ -30,7 +30,7 @@ def _field(res=(8, 8, 8, 5), multires=(1, 2), seed=0):
 def _points(n, seed=1):
     g = torch.Generator().manual_seed(seed)
     pts = (torch.rand(n, 3, generator=g) * 2 - 1) * torch.tensor([1.1, 1.3, 1.5])   # some outside the box
-    pts[0] = torch.tensor([1.0, 1.2, 1.4])      # exact corners
+    pts[0] = torch.tensor([1.0, 1.2, 1.4])      # exact corners (this symmetric box cannot see a wrong border clip: tests/test_hexplane_box_gpu.py)
     pts[1] = torch.tensor([-1.0, -1.2, -1.4])
     return pts
 
