@@ -217,6 +217,12 @@ def _sig(lib):
     lib.mom_deform_field_scratch_bytes.argtypes = [C.POINTER(MomHexPlane), i32]
     lib.mom_deform_field_forward.argtypes = [C.POINTER(MomHexPlane), C.POINTER(MomDeformMLP), i32, vp, C.c_float, vp, vp, vp, vp,
                                              C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    # the same trio for two levels of 16 channels (csrc/deform_field16.hip)
+    lib.mom_deform_field16_supported.argtypes = [C.POINTER(MomHexPlane)]
+    lib.mom_deform_field16_scratch_bytes.restype = sz
+    lib.mom_deform_field16_scratch_bytes.argtypes = [C.POINTER(MomHexPlane), i32]
+    lib.mom_deform_field16_forward.argtypes = [C.POINTER(MomHexPlane), C.POINTER(MomDeformMLP), i32, vp, C.c_float, vp, vp, vp, vp,
+                                               C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mom_densify_stats.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp]
     lib.mom_select_scratch_bytes.restype = sz
     lib.mom_select_scratch_bytes.argtypes = [i32]
@@ -267,6 +273,7 @@ EXPORTS = [
     "mom_comm_reduce_scatter",
     "mom_raster_backward_acc", "mom_raster_backward_geometry_acc",
     "mom_deform_forward_n", "mom_deform_forward_activated_n", "mom_deform_backward_n", "mom_deform_backward_split_n",
+    "mom_deform_field16_supported", "mom_deform_field16_scratch_bytes", "mom_deform_field16_forward",
 ]
 
 

@@ -5,6 +5,11 @@ model has the shipped configuration (the case of render_4DGS.py and of every eva
 fused training step, no SH concatenation (the rasterizer reads the DC and the rest coefficients through two pointers), no
 gradient holder, no per-op allocation of intermediates.  Only the returned image, depth and radii are fresh tensors --
 callers keep them.
+
+A model of two levels of 16-channel planes (Deformation._field16_fusable) takes the same sequence with its own field kernel
+(csrc/deform_field16.hip: HexPlane + MLP in one launch) and ONE exception to the above: its three activations are the model's own
+torch functions on the kernel's raw outputs, three more launches and three fresh [P,3] / [P,4] / [P,1] tensors per frame, because
+such a frame has to be the gradient-mode frame bit for bit (see _deform).
 """
 import ctypes as C
 from collections import deque
@@ -34,9 +39,14 @@ class FusedRender:
             return
         self.key = (P, W, H, dev)
         e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        self.feat = e(P, 64)
+        # the two-kernel route's feature buffer (ops.field_forward's scratch_feat); a 16 x 2 field's one-launch kernel keeps its
+        # features in LDS
+        dn = getattr(getattr(self.g, "_deformation", None), "deformation_net", None)
+        f16 = dn is not None and dn._field16_fusable()
+        self.feat = None if f16 else e(P, 64)
         self.pts, self.sc_d, self.rot_d = e(P, 3), e(P, 3), e(P, 4)
-        self.sc, self.rot, self.op = e(P, 3), e(P, 4), e(P, 1)
+        # (a 16 x 2 model's activated values are fresh tensors of the model's own activation functions, see _deform)
+        self.sc, self.rot, self.op = (None, None, None) if f16 else (e(P, 3), e(P, 4), e(P, 1))
         self.geom = torch.empty(self.lib.mom_raster_geom_bytes(P), dtype=torch.uint8, device=dev)
         self.img = torch.empty(self.lib.mom_raster_image_bytes(W, H), dtype=torch.uint8, device=dev)
         self.nr_dev = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -117,13 +127,25 @@ class FusedRender:
                                           aabb_host=field.aabb_host())
             md = ops.DeformMLPFunction._desc([p.detach() for p in mlp], None)
             self._desc, self._desc_key = (hp, keep, md), dkey
+            self._f16 = dn._field16_fusable()    # (walks every plane: asked once per descriptor, not per frame)
         hp, keep, md = self._desc
+        f16 = self._f16                  # (the predicate _ensure sized the buffers by; ops.field16_forward raises if the library disagrees)
+        scratch_bytes = lib.mom_deform_field16_scratch_bytes if f16 else lib.mom_deform_field_scratch_bytes
         # this renderer's OWN field scratch (time-line table + feature buffer): a FusedRenderPool keeps one frame per slot in flight
         # on unsynchronised streams, and the per-device scratch of ops.field_scratch would be rewritten by frame k+1's line kernel
         # while frame k's field kernel still reads it
-        need = lib.mom_deform_field_scratch_bytes(C.byref(hp), P)
+        need = scratch_bytes(C.byref(hp), P)
         if getattr(self, "_fscratch", None) is None or self._fscratch.numel() < need or self._fscratch.device != dev:
             self._fscratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        if f16:
+            # The gradient-mode render() of such a model is op by op, and a no-grad frame has to be ITS image bit for bit
+            # (tests/test_hexplane16_gpu.py).  The kernel's raw outputs are the two ops' bits; its activated copies (expf, the
+            # uncontracted quaternion norm) differ from torch's exp / normalize in last bits, as on the 32 x 2 path.  So the raw
+            # outputs go through the model's own activation functions, exactly as in render()'s op-by-op branch.
+            ops.field16_forward(hp, md, P, xyz, float(cam.time), order, scal, rot, flow, float(delta_scale * cam.frame_num), self.pts,
+                                self.sc_d, self.rot_d, None, None, None, None, None, None, s, scratch=self._fscratch)
+            self.sc, self.rot, self.op = g.scaling_activation(self.sc_d), g.rotation_activation(self.rot_d), g.opacity_activation(opac)
+            return
         ops.field_forward(hp, md, P, xyz, float(cam.time), order, scal, rot, flow, float(delta_scale * cam.frame_num), self.pts,
                           self.sc_d, self.rot_d, None, None, opac, self.sc, self.rot, self.op, s, scratch_feat=self.feat,
                           scratch=self._fscratch)

@@ -29,10 +29,12 @@ def render_streams():
     return _RENDER_STREAMS
 
 
-def _fused_path_applies(cam, pc, pipe, stage, override_color, cam_type):
+def _fused_path_applies(cam, pc, pipe, stage, override_color, cam_type, forward_only=False):
     """Whether this frame can take a fused launch sequence (fused_render.py without gradients, fused_autograd.py with them): fine
     stage with the shipped deformation configuration or coarse stage, SH colours and covariances computed by the rasterizer, an
-    ordinary camera, everything on the GPU.  (Grad mode and pipe.per_op_autograd are for the caller to check.)"""
+    ordinary camera, everything on the GPU.  (Grad mode and pipe.per_op_autograd are for the caller to check.)
+    forward_only: the question of the no-grad branch, which also takes the same network on two levels of 16-channel planes
+    (Deformation._field16_fusable; fused_render.py has a field kernel for it, the gradient paths have none)."""
     if stage not in ("fine", "coarse") or override_color is not None or cam_type == "PanopticSports":
         return False
     if pipe.compute_cov3D_python or pipe.convert_SHs_python or not hasattr(cam, "device_tensors"):
@@ -42,7 +44,9 @@ def _fused_path_applies(cam, pc, pipe, stage, override_color, cam_type):
     if stage == "coarse":
         return True
     dn = getattr(pc._deformation, "deformation_net", None)
-    return dn is not None and hasattr(dn, "_fusable") and dn._fusable()
+    if dn is None or not hasattr(dn, "_fusable"):
+        return False
+    return dn._fusable() or (forward_only and dn._field16_fusable())
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, stage="fine",
@@ -55,8 +59,9 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         # gaussian_renderer/__init__.py:101-103): None raises there, so it raises here, on every path
         raise TypeError("unsupported operand type(s) for *: 'NoneType' and 'Tensor' (render(): delta_scale is required "
                         "outside the coarse stage)")
-    fused = _fused_path_applies(viewpoint_camera, pc, pipe, stage, override_color, cam_type)
-    if fused and not torch.is_grad_enabled():
+    no_grad = not torch.is_grad_enabled()
+    fused = _fused_path_applies(viewpoint_camera, pc, pipe, stage, override_color, cam_type, forward_only=no_grad)
+    if fused and no_grad:
         # forward-only launch sequence (fused_render.py)
         if _RENDER_STREAMS > 1:
             pool = getattr(pc, "_fused_render_pool", None)

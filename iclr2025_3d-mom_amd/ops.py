@@ -203,6 +203,22 @@ def field_forward(hp, md, P, xyz, time, order, scal, rot, flow, coef, pts, sc_d,
     return False
 
 
+def field16_forward(hp, md, P, xyz, time, order, scal, rot, flow, coef, pts, sc_d, rot_d, feat, a0, opac, sc, rot_act, op, s,
+                    scratch=None):
+    """field_forward for two levels of 16-channel planes (csrc/deform_field16.hip): HexPlane gather, trunk, heads, residuals and
+    activations in one launch, the bits of mom_hexplane_forward + mom_deform_forward_activated_n.  feat [P,32] / a0 [P,64] and the
+    activated outputs sc / rot_act / op (with opac) are optional.  A field mom_deform_field16_supported refuses is a MomError: the
+    caller routes (Deformation._field16_fusable), nothing falls back here."""
+    lib = N.lib()
+    q = lambda t: None if t is None else t.data_ptr()
+    if not lib.mom_deform_field16_supported(C.byref(hp)):
+        raise N.MomError(f"field16_forward: {hp.levels} levels of {hp.channels} channels (needs 2 of 16, resolutions <= 1024)")
+    N.check(lib.mom_deform_field16_forward(C.byref(hp), C.byref(md), P, xyz.data_ptr(), float(time), q(order), scal.data_ptr(),
+                                           rot.data_ptr(), flow.data_ptr(), float(coef), pts.data_ptr(), sc_d.data_ptr(),
+                                           rot_d.data_ptr(), q(feat), q(a0), q(opac), q(sc), q(rot_act), q(op), q(scratch), s),
+            "deform_field16_fwd")
+
+
 # --------------------------------------------------------------------------- rasterizer arguments (the fused paths)
 def gaussian_params(g, who):
     """(xyz, f_dc, f_rest, scaling, rotation, opacity) of model g, detached; MomError unless every one is contiguous (the kernels

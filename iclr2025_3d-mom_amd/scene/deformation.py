@@ -101,6 +101,16 @@ class Deformation(nn.Module):
                 and not a.static_mlp and not a.no_dx and not a.no_ds and not a.no_dr and a.no_do and a.no_dshs
                 and not a.apply_rotation)
 
+    FIELD16_MAX_RES = 1024      # the kernel's limit on a plane's resolution (mom_deform_field16_supported, csrc/deform_field16.hip)
+
+    def _field16_fusable(self):
+        """The one-launch field forward for 16-channel planes (ops.field16_forward, csrc/deform_field16.hip) applies: the
+        _mlp_fusable() network on a field that is not the shipped 32 x 2 one -- that is 32 features from exactly two levels of 16
+        channels -- with every plane inside the kernel's resolution limit.  gaussian_renderer.render() asks for this or _fusable()
+        in its no-grad branch only; a field beyond the limit keeps rendering op by op."""
+        return (self._mlp_fusable() and not self._fusable()
+                and all(max(p.shape[2], p.shape[3]) <= self.FIELD16_MAX_RES for lv in self.grid.grids for p in lv))
+
     def _fused_params(self):
         """The 14 tensors of the trunk and the three heads, in the kernels' order.  Cached while the first and the last are the
         objects they were (walking four nn.Sequential containers costs 33 us per call, and a training step asks once)."""

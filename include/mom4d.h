@@ -533,6 +533,22 @@ int mom_deform_field_forward(const MomHexPlane* hp, const MomDeformMLP* w, int P
                              const float* opacity_raw, float* scales_act, float* rots_act, float* opacity_act, void* scratch,
                              mom_stream_t stream);
 
+/* The same for a field of two levels of 16-channel planes (dnerf/eulerian_150_16; csrc/deform_field16.hip): ONE persistent fp32
+ * kernel computes what mom_hexplane_forward (channels 16) followed by mom_deform_forward_activated_n (in_features 32) computes, bit
+ * for bit; a tile's 32 features go from the gather to the trunk layer through LDS and reach memory only if the caller asks for a
+ * copy.  Argument list of mom_deform_field_forward with feat_save [P,32] and a0_save [P,64], both optional, as are the three
+ * activated outputs (opacity_raw is required exactly when opacity_act is given).  Needs channels == 16, levels == 2 and resolutions
+ * <= 1024 (mom_deform_field16_supported: 0 for everything else, 32 channels and 16 x 3 / 16 x 4 levels included); an unsupported
+ * field or a missing argument is MOM_EINVAL before anything is launched, P == 0 does nothing.  Nothing is staged in memory:
+ * mom_deform_field16_scratch_bytes is one aligned block and `scratch` is not read (it may be null). */
+int mom_deform_field16_supported(const MomHexPlane* hp);
+size_t mom_deform_field16_scratch_bytes(const MomHexPlane* hp, int P);
+int mom_deform_field16_forward(const MomHexPlane* hp, const MomDeformMLP* w, int P, const float* xyz, float time,
+                               const uint32_t* order, const float* scaling, const float* rotation, const float* scene_flow,
+                               float flow_coef, float* pts, float* scales, float* rots, float* feat_save, float* a0_save,
+                               const float* opacity_raw, float* scales_act, float* rots_act, float* opacity_act, void* scratch,
+                               mom_stream_t stream);
+
 /* ---- rendered image -> 8-bit interleaved RGB (render_4DGS.py:64 torchvision.utils.save_image: x * 255 + 0.5, clamp, truncate;
  * CHW -> HWC) in one pass, so that a frame can leave the device as the bytes a PNG encoder takes.  img [C,H,W] floats, out [H,W,C]
  * bytes; C <= 4. */
