@@ -14,6 +14,10 @@ then backward of camera k, then k + 1, on the same scratch: memory does not grow
 stores the gradients exactly as a single camera's does, every later one ADDS (mom_raster_backward_acc) and merges its radii into
 the first one's (max); every camera's gradient image carries 1 / B; the regulariser, the densification statistics and Adam run
 once.  A list of one camera is the single-camera step, launch for launch.  Batches on the multi-GPU paths are out of scope.
+
+Two model shapes have a fine step (step_features, fine_step): the shipped field, two HexPlane levels of 32 channels = 64 features, is
+FusedStep's; two levels of 16 channels = 32 features (dnerf/eulerian_150_16) is FusedStep16's -- the same sequence on the 16-channel
+kernels, one GPU only.
 """
 import ctypes as C
 import os
@@ -224,13 +228,35 @@ class _Step:
         return loss, self.radii, self.g2d
 
 
+def step_features(dn):
+    """Width of the HexPlane feature row the fused fine step runs a deformation net on, or 0 if it cannot take the model: 64 for the
+    shipped field (two levels of 32 channels, Deformation._fusable), 32 for two levels of 16 channels inside the one-launch field
+    kernel's resolution limit (dnerf/eulerian_150_16, Deformation._field16_fusable).  Pure: asks the module, needs no GPU and no
+    library."""
+    if dn._fusable():
+        return 64
+    if dn._field16_fusable():
+        return 32
+    return 0
+
+
 class FusedStep(_Step):
-    """One fine-stage iteration (module docstring)."""
+    """One fine-stage iteration (module docstring) of the shipped model: two HexPlane levels of 32 channels, F = 64 features.  Every
+    other model is refused, a 16 x 2 one too: that one is FusedStep16's, and fine_step() picks between the two."""
+
+    WIDTHS = (64,)        # the feature widths (step_features) this class takes
 
     def __init__(self, gaussians, opt, hyper, background):
         dn = gaussians._deformation.deformation_net
-        if not dn._fusable():
-            raise N.MomError("FusedStep needs the shipped deformation configuration (W=64, D=0, no_do, no_dshs)")
+        self.F = step_features(dn)
+        if self.F not in self.WIDTHS:
+            raise N.MomError("%s needs the shipped deformation configuration (W=64, D=0, no_do, no_dshs) on two HexPlane levels of %s "
+                             "(fused_step.fine_step picks the step for a model: 32 channels FusedStep, 16 channels with every plane "
+                             "resolution <= %d FusedStep16)" % (type(self).__name__, " or ".join("%d channels" % (w // 2) for w in self.WIDTHS),
+                                                               dn.FIELD16_MAX_RES))
+        if self.F != 64:      # feat / dfeat rows are F floats wide; the shipped model keeps the class's table as it is
+            self._ROW_BUFFERS = tuple((name, self.F if name in ("feat", "dfeat") else cols, padded)
+                                      for name, cols, padded in type(self)._ROW_BUFFERS)
         super().__init__(gaussians, opt, hyper, background)
 
     # ------------------------------------------------------------------ buffers (re-made when P changes)
@@ -388,6 +414,8 @@ class FusedStep(_Step):
         B, cam = len(cams), cams[0]
         if B > 1 and self.dist is not None:
             raise N.MomError("FusedStep: a batch of cameras on the multi-GPU paths is not supported (one camera per rank)")
+        if self.F == 32 and self.dist is not None:
+            raise N.MomError("FusedStep16 on 16-channel fields: single GPU only")
         P, W, H, dev = self._begin(cam)
         sharded = bool(self._chunk) and early_adam is not None and self.EARLY_ADAM     # this iteration takes the sharded-Adam path
         if self._chunk:
@@ -448,7 +476,7 @@ class FusedStep(_Step):
                 for i, p in enumerate(planes):
                     st, gs = ops.plane_storage(p.detach()), ops.plane_storage(self._dg_planes[i])
                     arr[i].plane, arr[i].grad = st.data_ptr(), gs.data_ptr()
-                    arr[i].H, arr[i].W = st.shape[0], st.shape[1]
+                    arr[i].H, arr[i].W = st.shape[0], ops._reg_row_units(st)      # rows in units of 32 floats: W, or W / 2 at 16 channels
                     tplane = (i % 6) in (2, 4, 5)
                     arr[i].w_smooth = hy.time_smoothness_weight if tplane else hy.plane_tv_weight
                     arr[i].w_l1 = hy.l1_time_planes if tplane else 0.0
@@ -508,6 +536,19 @@ class FusedStep(_Step):
                 if grp is not None and getattr(grp, "work", None) is not None:
                     dc._pending.append(grp.work)
                 dc.finish()
+            elif self.F == 32:
+                # two levels of 16 channels: the one-launch field of csrc/deform_field16.hip; it stages no time lines.  Its raw outputs
+                # only: the activated copies are torch's exp / normalize / sigmoid, as in FusedRender and for the same reason -- the
+                # autograd path of such a model is op by op, and the kernel's expf / quaternion norm differ from torch's in last bits,
+                # which moves (pixel, splat) pairs across the compositing thresholds (measured on the tiny scene: 43 of 6000 Gaussians'
+                # d xyz up to 1.1e-3 of the tensor's scale away from the autograd path's; with torch's activations the image is that
+                # path's bit for bit and every gradient within 5e-6: DESIGN 3.10)
+                ops.field16_forward(hp, md, P, xyz, time, order, scal, rot, flow, coef, self.pts, self.sc_d, self.rot_d, self.feat, self.a0,
+                                    None, None, None, None, s)
+                torch.exp(self.sc_d, out=self.sc)
+                torch.nn.functional.normalize(self.rot_d, out=self.rot)
+                torch.sigmoid(opac, out=self.op)
+                lines_kept = False
             else:
                 lines_kept = ops.field_forward(hp, md, P, xyz, time, order, scal, rot, flow, coef, self.pts, self.sc_d, self.rot_d, self.feat, self.a0,
                                   opac, self.sc, self.rot, self.op, s)
@@ -702,9 +743,14 @@ class FusedStep(_Step):
                 launch_early_cam()
                 early_cam = None
             if sl is None:
-                N.check(lib.mom_deform_backward_split(C.byref(md), P, self.feat.data_ptr(), self.a0.data_ptr(), d_pts.data_ptr(),
-                                                      d_sc.data_ptr(), d_rot.data_ptr(), self.dfeat.data_ptr(),
-                                                      self.dh_scratch.data_ptr(), s, side), "deform_bwd")
+                if self.F == 32:
+                    N.check(lib.mom_deform_backward_split_n(C.byref(md), P, 32, self.feat.data_ptr(), self.a0.data_ptr(), d_pts.data_ptr(),
+                                                            d_sc.data_ptr(), d_rot.data_ptr(), self.dfeat.data_ptr(),
+                                                            self.dh_scratch.data_ptr(), s, side), "deform_bwd")
+                else:
+                    N.check(lib.mom_deform_backward_split(C.byref(md), P, self.feat.data_ptr(), self.a0.data_ptr(), d_pts.data_ptr(),
+                                                          d_sc.data_ptr(), d_rot.data_ptr(), self.dfeat.data_ptr(),
+                                                          self.dh_scratch.data_ptr(), s, side), "deform_bwd")
                 if porders is not None:
                     self._hex_scratch_for(hp, P, dev)
                 if porders is not None and lines_kept:      # the forward's time lines are still in the field scratch
@@ -775,6 +821,21 @@ class FusedStep(_Step):
                 self.ssim_sum[:1].copy_(self._tr_sums[2:3])
             l1 = self._tr_sums[0] / n
         return self._loss(l1, reg, lam, n, B)
+
+
+class FusedStep16(FusedStep):
+    """The fine-stage iteration of a model with two HexPlane levels of 16-channel planes, F = 32 features into the shipped network
+    (dnerf/eulerian_150_16): FusedStep's launch sequence on the one-launch field of csrc/deform_field16.hip, the MLP backward on 32
+    features and the 16-channel HexPlane backward (the F == 32 branches of forward_backward).  One GPU only.  A class of its own
+    because FusedStep(...) on such a model is a MomError and stays one."""
+
+    WIDTHS = (32,)
+
+
+def fine_step(gaussians, opt, hyper, background):
+    """The fused fine-stage step of a model -- FusedStep for 64 features, FusedStep16 for 32 (step_features) -- or MomError."""
+    F = step_features(gaussians._deformation.deformation_net)
+    return (FusedStep16 if F == 32 else FusedStep)(gaussians, opt, hyper, background)
 
 
 class FusedCoarseStep(_Step):

@@ -493,6 +493,10 @@ def attach(trainer, rank, world, seed=6666, mode="camera", shard_adam=None):
         # a batch of cameras per rank is not a fused multi-GPU path (fused_step.py): such a trainer is what it was before the fused
         # step took batches -- no fused step at all, every iteration on the autograd path with its own drain / replay protocol
         fused = trainer.fused = None
+    if fused is not None and getattr(fused, "F", 64) == 32:
+        # the fused step on two levels of 16-channel planes is single-GPU (FusedStep16: forward_backward refuses a DistContext): such a
+        # trainer runs on the autograd path with sync_param_grads
+        fused = trainer.fused = None
     if shard_adam and (fused is None or mode != "camera"):
         raise ValueError("shard_adam needs the fused step and the camera-batch shard")
     trainer.dist = DistContext(rank, world, seed, mode, shard_adam=shard_adam)

@@ -89,8 +89,9 @@ class Deformation(nn.Module):
 
     def _mlp_fusable(self):
         """The fused MLP op (ops.deform_mlp) applies: the _fusable() model, or the same network on 32 features from exactly two
-        levels of 16 channels (dnerf/eulerian_150_16; csrc/deform_mlp32.hip).  Wider than _fusable() on purpose: the fused step,
-        the fused autograd path and the render pool key on _fusable() and keep declining 16-channel fields."""
+        levels of 16 channels (dnerf/eulerian_150_16; csrc/deform_mlp32.hip).  Wider than _fusable() on purpose: the fused
+        autograd path keys on _fusable() and keeps declining 16-channel fields (the fused step and no-grad render() take them
+        through _field16_fusable(): fused_step.step_features)."""
         if self._fusable():
             return True
         a = self.args

@@ -31,10 +31,12 @@ class Trainer:
         # instead of render()+autograd -- for any opt.batch_size: the cameras of a batch run one after the other inside one fused step
         # (train_4DGS.py:172-229).  Multi-GPU x batch is not supported by the fused step: parallel.attach() on a trainer with
         # batch_size > 1 drops the fused step again, so that trainer is on the autograd path throughout, as it always was.
+        # The fine step is fused_step.fine_step()'s choice by step_features(): FusedStep for the shipped 32 x 2 field, FusedStep16 for two
+        # levels of 16-channel planes (dnerf/eulerian_150_16) on one GPU -- parallel.attach() drops the fused step of such a trainer too.
         self.fused = None
         if fused and stage in ("fine", "coarse"):
-            from .fused_step import FusedCoarseStep, FusedStep
-            self.fused = (FusedStep if stage == "fine" else FusedCoarseStep)(gaussians, opt, hyper, self.background)
+            from .fused_step import FusedCoarseStep, fine_step
+            self.fused = (fine_step if stage == "fine" else FusedCoarseStep)(gaussians, opt, hyper, self.background)
         # every fused step since the last verified one: (serial, iteration, cameras); and the overflow-word read-backs in flight:
         # (serial of the last step they cover, ring slot, event)
         self._log = deque()
