@@ -228,6 +228,10 @@ def _sig(lib):
     lib.mom_select_scratch_bytes.argtypes = [i32]
     lib.mom_select_plan.argtypes = [i32, vp, vp, vp, vp, vp, vp]
     lib.mom_select_apply.argtypes = [i32, vp, C.POINTER(MomRowSelect), i32, vp]
+    lib.mom_densify_scratch_bytes.restype = sz
+    lib.mom_densify_scratch_bytes.argtypes = [i32]
+    lib.mom_densify_plan.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mom_densify_apply.argtypes = [i32, vp, vp, vp, vp, vp, C.POINTER(MomDensifyTensor), i32, sz, vp]
     lib.mom_ssim_forward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.mom_ssim_forward_slab.argtypes = [i32, i32, i32, sz, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.mom_ssim_backward_slab.argtypes = [i32, i32, i32, sz, vp, vp, vp, vp, C.c_float, vp, vp, vp]
@@ -253,6 +257,17 @@ class MomRowSelect(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_uint)]
 
 
+DENSIFY_MAX_TENSORS = 32            # MOM_DENSIFY_MAX_TENSORS
+DENSIFY_MAX_ROW_BYTES = 1 << 20     # MOM_DENSIFY_MAX_ROW_BYTES
+# MOM_DENSIFY_* roles of one tensor of a densify round
+DENSIFY_COPY, DENSIFY_MOMENT, DENSIFY_XYZ, DENSIFY_SCALING, DENSIFY_ROTATION, DENSIFY_ZERO = range(6)
+
+
+class MomDensifyTensor(C.Structure):
+    # mom_densify_apply takes sizeof of this mirror beside the array and refuses another size
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_uint), ("role", C.c_int)]
+
+
 # every symbol include/mom4d.h declares (tests/test_abi.py checks this list against the header)
 EXPORTS = [
     "mom_version", "mom_abi_version", "mom_abi_sizeof", "mom_raster_geom_bytes", "mom_raster_image_bytes", "mom_raster_binning_bytes", "mom_raster_layout",
@@ -274,6 +289,7 @@ EXPORTS = [
     "mom_raster_backward_acc", "mom_raster_backward_geometry_acc",
     "mom_deform_forward_n", "mom_deform_forward_activated_n", "mom_deform_backward_n", "mom_deform_backward_split_n",
     "mom_deform_field16_supported", "mom_deform_field16_scratch_bytes", "mom_deform_field16_forward",
+    "mom_densify_scratch_bytes", "mom_densify_plan", "mom_densify_apply",
 ]
 
 

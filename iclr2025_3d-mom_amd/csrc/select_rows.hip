@@ -6,29 +6,11 @@
 // nonzero() and host synchronisation.  Here the mask is scanned ONCE into a plan (dst_index[i] = position of row i among the
 // kept rows, or -1) and one kernel applies the plan to every tensor.
 #include "mom_common.h"
+#include "scan_dev.h"
 
 namespace {
 
 constexpr int kItems = 2048;       // rows per workgroup in the scan (256 threads x 8)
-
-__device__ __forceinline__ int block_exclusive_scan_256(int v, int* s_wave, int& total)
-{
-    // exclusive prefix of one int per thread over 256 threads; total = sum over the workgroup
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) s_wave[wv] = incl;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wv; w++) base += s_wave[w];
-    total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    __syncthreads();
-    return base + incl - v;
-}
 
 __global__ void __launch_bounds__(256) select_count_kernel(int n, const uint8_t* __restrict__ keep, int* __restrict__ block_counts)
 {

@@ -407,6 +407,110 @@ def select_rows(mask, tensors):
     return outs
 
 
+# --------------------------------------------------------------------------- one-pass densify round
+_DENSIFY_SINGLE = (("xyz", N.DENSIFY_XYZ, 3), ("scaling", N.DENSIFY_SCALING, 3), ("rotation", N.DENSIFY_ROTATION, 4))
+_DENSIFY_LISTS = (("copy", N.DENSIFY_COPY), ("moment", N.DENSIFY_MOMENT), ("zero", N.DENSIFY_ZERO))
+_densify_counts_host = None        # three pinned ints, reused: the plan's counts land here
+
+
+def densify_round(clone_mask, split_mask, tensors_by_role, z=None):
+    """Clone, split and the removal of the split parents (scene/gaussian_model.py:461-581: densify_and_clone, densify_and_split,
+    cat_tensors_to_optimizer, densification_postfix, prune_points) for every tensor of a model in one pass: the two masks are
+    scanned once, ONE host synchronisation reads the three counts (the outputs have to be allocated), and one kernel reads every
+    source row once and writes the round's final layout -- the rows that are not split in order, the clones in order, child 0 of
+    every split parent, child 1 of every split parent.
+
+    tensors_by_role: {"xyz": [P,3], "scaling": [P,3], "rotation": [P,4]} (float32; needed when anything is split: the children
+    are made of them) and the lists "copy" (every output row is its source row), "moment" (Adam moments: clone and child rows
+    are zero) and "zero" (statistics: zero at the new length).  The masks are disjoint 1-D bool tensors.  `z`: the [2S,3]
+    standard normals of the children; None draws them from torch's generator of the device, after the counts are known and only
+    if S > 0 -- the draw of the reference's torch.normal(zeros(2S,3), std).
+    Returns a dict with the same keys holding the new tensors, plus "counts" = (K, C, S) and "z" (None if S == 0)."""
+    global _densify_counts_host
+    _need_cuda(clone_mask, "densify_round")
+    _need_cuda(split_mask, "densify_round")
+    P = clone_mask.shape[0]
+    for m in (clone_mask, split_mask):
+        if m.dim() != 1 or m.dtype != torch.bool or m.shape[0] != P or m.device != clone_mask.device:
+            raise N.MomError("densify_round: the masks must be 1-D bool tensors of one length on one device")
+    dev = clone_mask.device
+    unknown = set(tensors_by_role) - {k for k, _, _ in _DENSIFY_SINGLE} - {k for k, _ in _DENSIFY_LISTS}
+    if unknown:
+        raise N.MomError(f"densify_round: unknown roles {sorted(unknown)}")
+    items = []                                                       # (key, position or None, role, source)
+    for key, role, width in _DENSIFY_SINGLE:
+        t_ = tensors_by_role.get(key)
+        if t_ is not None:
+            if t_.dtype != torch.float32 or tuple(t_.shape) != (P, width):
+                raise N.MomError(f"densify_round: {key} must be a float32 [{P},{width}] tensor, got {t_.dtype} {tuple(t_.shape)}")
+            items.append((key, None, role, t_))
+    for key, role in _DENSIFY_LISTS:
+        items += [(key, j, role, t_) for j, t_ in enumerate(tensors_by_role.get(key, ()))]
+    if len(items) > N.DENSIFY_MAX_TENSORS:
+        raise N.MomError(f"densify_round: {len(items)} tensors, one launch takes {N.DENSIFY_MAX_TENSORS}")
+    srcs = []
+    for key, j, role, t_ in items:
+        _need_cuda(t_, "densify_round")
+        t_ = t_.detach()
+        if t_.dim() < 1 or t_.shape[0] != P or t_.device != dev:
+            raise N.MomError(f"densify_round: every tensor needs one row per mask element on the masks' device ({key})")
+        if not t_.is_contiguous():
+            raise N.MomError(f"densify_round: {key} is not contiguous")
+        rb = (t_.numel() // P) * t_.element_size() if P else 0
+        if rb > N.DENSIFY_MAX_ROW_BYTES:
+            raise N.MomError(f"densify_round: rows of {rb} bytes ({key}); the limit is {N.DENSIFY_MAX_ROW_BYTES}")
+        srcs.append((t_, rb))
+    if z is not None:
+        _need_cuda(z, "densify_round")
+        if z.dtype != torch.float32 or z.dim() != 2 or z.shape[1] != 3 or not z.is_contiguous() or z.device != dev:
+            raise N.MomError("densify_round: z must be a contiguous float32 [2S,3] tensor on the masks' device")
+
+    lib, s = N.lib(), N.current_stream()
+    K = C_ = S = 0
+    if P:
+        if _densify_counts_host is None:
+            _densify_counts_host = torch.empty(3, dtype=torch.int32).pin_memory()
+        counts_host = _densify_counts_host
+        index = torch.empty((3, P), dtype=torch.int32, device=dev)
+        counts_dev = torch.empty(3, dtype=torch.int32, device=dev)
+        scratch = torch.empty(lib.mom_densify_scratch_bytes(P), dtype=torch.uint8, device=dev)
+        cm, sm = clone_mask.contiguous().view(torch.uint8), split_mask.contiguous().view(torch.uint8)
+        N.check(lib.mom_densify_plan(P, cm.data_ptr(), sm.data_ptr(), index[0].data_ptr(), index[1].data_ptr(),
+                                     index[2].data_ptr(), counts_dev.data_ptr(), counts_host.data_ptr(), scratch.data_ptr(), s),
+                "mom_densify_plan")
+        torch.cuda.current_stream().synchronize()      # the one sync of the round: sizes of the outputs
+        K, C_, S = (int(v) for v in counts_host)
+    if S:
+        if not all(k in tensors_by_role and tensors_by_role[k] is not None for k, _, _ in _DENSIFY_SINGLE):
+            raise N.MomError("densify_round: rows are split, and the children need xyz, scaling and rotation")
+        if z is None:
+            z = torch.randn((2 * S, 3), dtype=torch.float32, device=dev)
+        elif z.shape[0] != 2 * S:
+            raise N.MomError(f"densify_round: {S} rows are split, z has {z.shape[0]} rows instead of {2 * S}")
+    else:
+        z = None
+    nout = K + C_ + 2 * S
+    outs = [torch.empty((nout,) + tuple(t_.shape[1:]), dtype=t_.dtype, device=dev) for t_, _ in srcs]
+    if P:
+        arr = (N.MomDensifyTensor * max(len(items), 1))()
+        for i, ((_, _, role, _), (t_, rb), o) in enumerate(zip(items, srcs, outs)):
+            arr[i].src, arr[i].dst, arr[i].row_bytes, arr[i].role = t_.data_ptr(), o.data_ptr(), rb, role
+        counts = (C.c_int * 3)(K, C_, S)
+        N.check(lib.mom_densify_apply(P, index[0].data_ptr(), index[1].data_ptr(), index[2].data_ptr(), counts,
+                                      None if z is None else z.data_ptr(), arr, len(items), C.sizeof(N.MomDensifyTensor), s),
+                "mom_densify_apply")
+    result = {"counts": (K, C_, S), "z": z}
+    for key, _ in _DENSIFY_LISTS:
+        if key in tensors_by_role:
+            result[key] = []
+    for (key, j, _, _), o in zip(items, outs):
+        if j is None:
+            result[key] = o
+        else:
+            result[key].append(o)
+    return result
+
+
 # --------------------------------------------------------------------------- densification statistics
 def densify_stats(radii, viewspace_grad, max_radii2D, xyz_gradient_accum, denom, skip_flag=None, stream=None):
     """In place, for the Gaussians with radii > 0: running maximum radius, accumulated |dL/d mean2D| and its count
@@ -1046,6 +1150,7 @@ class _HipBackend:
     ssim = staticmethod(ssim)
     densify_stats = staticmethod(densify_stats)
     select_rows = staticmethod(select_rows)
+    densify_round = staticmethod(densify_round)
     plane_regulation = staticmethod(plane_regulation)
     Adam = FusedAdam
 

@@ -20,6 +20,9 @@ _PER_POINT = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")
 
 class GaussianModel:
     EMPTY_CACHE_AFTER_PRUNE = False
+    # densify() as one plan and one launch (ops.densify_round, csrc/densify_round.hip) where the backend has it; False: the
+    # op-by-op round below (densify_and_clone, densify_and_split, prune_points) on every backend.  DESIGN.md section 3.11.
+    FUSED_DENSIFY = True
 
     def setup_functions(self):
         def build_covariance_from_scaling_rotation(scaling, scaling_modifier, rotation):
@@ -379,8 +382,51 @@ class GaussianModel:
                 iteration=None, stage=None):
         grads = self.xyz_gradient_accum / self.denom
         grads[grads.isnan()] = 0.0
+        fused = getattr(ops.BACKEND, "densify_round", None) if self.FUSED_DENSIFY else None
+        # (max_grad <= 0: a fresh clone, whose padded gradient is 0, would pass the split's threshold -- only the op-by-op round
+        # has that case)
+        if fused is not None and max_grad > 0 and self._xyz.is_cuda:
+            self._densify_fused(fused, grads, max_grad, extent)
+            return
         self.densify_and_clone(grads, max_grad, extent, density_threshold, displacement_scale, model_path, iteration, stage)
         self.densify_and_split(grads, max_grad, extent)
+
+    def _densify_fused(self, fused, grads, grad_threshold, scene_extent):
+        """densify_and_clone + densify_and_split + the prune of the split parents as one backend call.  The two masks are the
+        expressions of those two functions on the rows there are before the round (the clones the op-by-op round has appended by
+        the time it builds the split mask have a padded gradient of 0 and are never split), so every row falls into the class it
+        falls into there; the backend moves every tensor and both moments of every per-point group into the final layout."""
+        dev, n0 = self._xyz.device, self.get_xyz.shape[0]
+        clone = (torch.norm(grads, dim=-1) >= grad_threshold) & \
+                (torch.max(self.get_scaling, dim=1).values <= self.percent_dense * scene_extent)
+        padded = torch.zeros((n0,), device=dev)
+        padded[:grads.shape[0]] = grads.squeeze()
+        split = (padded >= grad_threshold) & (torch.max(self.get_scaling, dim=1).values > self.percent_dense * scene_extent)
+        roles = {"copy": [], "moment": [], "zero": [self.xyz_gradient_accum, self._deformation_accum, self.denom, self.max_radii2D]}
+        order = []                                   # where _rebuild finds each group's outputs, in the order it asks for them
+        for g in self._single_groups():
+            old = g["params"][0]
+            st = self.optimizer.state.get(old, None)
+            if g["name"] in ("xyz", "scaling", "rotation"):
+                roles[g["name"]] = old.detach()
+                order.append((g["name"], None))
+            else:
+                order.append(("copy", len(roles["copy"])))
+                roles["copy"].append(old.detach())
+            if st is not None:
+                order += [("moment", len(roles["moment"])), ("moment", len(roles["moment"]) + 1)]
+                roles["moment"] += [st["exp_avg"], st["exp_avg_sq"]]
+        n_params = len(roles["copy"])
+        roles["copy"] += [self._deformation_table, self._scene_flow]
+        out = fused(clone, split, roles)
+        picked = iter(out[k] if j is None else out[k][j] for k, j in order)
+
+        def take(n, t):
+            return next(picked)
+        self._adopt(self._rebuild(take, take))
+        self._deformation_table, self._scene_flow = out["copy"][n_params:]
+        # all statistics restart after every densification (:505-508)
+        self.xyz_gradient_accum, self._deformation_accum, self.denom, self.max_radii2D = out["zero"]
 
     def grow(self, *a, **k):
         """Not part of the claimed surface: the reference's grow() (scene/gaussian_model.py:647-680) cannot run

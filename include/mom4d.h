@@ -405,6 +405,45 @@ int mom_select_plan(int n, const uint8_t* keep, int* dst_index, int* count_dev, 
                     mom_stream_t stream);
 int mom_select_apply(int n, const int* dst_index, const MomRowSelect* tensors, int count, mom_stream_t stream);
 
+/* ---- One-pass densify round (scene/gaussian_model.py:461-482 cat_tensors_to_optimizer, 484-509 densification_postfix,
+ * 511-539 densify_and_split with its prune_points, 541-581 densify_and_clone / prune: clone, split and the removal of the split
+ * parents, for every per-Gaussian tensor and both of its Adam moments) ----
+ * With P rows, C rows to clone and S rows to split (the two masks are disjoint; K = P - S), the round leaves K + C + 2S rows:
+ * the rows that are not split in order, then the clones in order, then child 0 of every split parent in order, then child 1.
+ * plan:  kept_index[i] = position of row i among the rows that are not split, or -1; clone_rank[i] / split_rank[i] = rank of row
+ *        i among the clones / the split parents, or -1 (device, [P] each); counts_dev (device) and, if non-null, counts_host
+ *        (pinned host memory, copied on the stream) = {K, C, S}.  P == 0: MOM_OK, zero counts, counts_dev may be null.
+ * apply: ONE launch for all `count` tensors.  `counts` is the plan's {K, C, S} ON THE HOST (the caller has waited for them: the
+ *        outputs had to be allocated), dst holds K + C + 2S rows of row_bytes bytes, z is [2S,3] standard normals (null if S == 0).
+ *        Per role:
+ *          MOM_DENSIFY_COPY      every output row is its source row (16-byte or 4-byte words when size and alignment allow)
+ *          MOM_DENSIFY_MOMENT    kept rows copy; clone and child rows are zero (an Adam moment: :461-482)
+ *          MOM_DENSIFY_XYZ       [P,3] floats; kept and clone rows copy; child b of the j-th split parent i is
+ *                                R(rotation_i) (z[b*S+j] * exp(scaling_i)) + xyz_i   (:517-524; R: utils/general_utils.py:84-105)
+ *          MOM_DENSIFY_SCALING   [P,3] floats; kept and clone rows copy; child rows are log(exp(scaling_i) / (0.8*2))   (:525)
+ *          MOM_DENSIFY_ROTATION  [P,4] floats; a copy, and the quaternions the xyz children read
+ *          MOM_DENSIFY_ZERO      zero at the new length (the statistics, :505-508); src is not read
+ *        The children are evaluated in torch's operation order, every element-wise operation rounded on its own.
+ *        A tensor with row_bytes == 0 is skipped.  tensor_size = sizeof(MomDensifyTensor) of the caller's header.
+ * MOM_EINVAL, before anything is launched: P < 0; a null index or counts pointer with P > 0; counts that are not a plan's
+ * (K != P - S, C or S outside [0, P]); count outside [0, MOM_DENSIFY_MAX_TENSORS]; another tensor_size; an unknown role;
+ * row_bytes > MOM_DENSIFY_MAX_ROW_BYTES; a tensor with rows and a null dst, or a null src unless its role is ZERO; an XYZ, SCALING
+ * or ROTATION tensor of another row size, misaligned or given twice; S > 0 without all three of them, or without z. */
+#define MOM_DENSIFY_MAX_TENSORS 32
+#define MOM_DENSIFY_MAX_ROW_BYTES (1u << 20)
+enum { MOM_DENSIFY_COPY = 0, MOM_DENSIFY_MOMENT, MOM_DENSIFY_XYZ, MOM_DENSIFY_SCALING, MOM_DENSIFY_ROTATION, MOM_DENSIFY_ZERO };
+typedef struct MomDensifyTensor {
+    const void* src;
+    void* dst;
+    unsigned row_bytes;
+    int role;              /* MOM_DENSIFY_* */
+} MomDensifyTensor;
+size_t mom_densify_scratch_bytes(int P);
+int mom_densify_plan(int P, const uint8_t* clone_mask, const uint8_t* split_mask, int* kept_index, int* clone_rank,
+                     int* split_rank, int* counts_dev, int* counts_host, void* scratch, mom_stream_t stream);
+int mom_densify_apply(int P, const int* kept_index, const int* clone_rank, const int* split_rank, const int* counts,
+                      const float* z, const MomDensifyTensor* tensors, int count, size_t tensor_size, mom_stream_t stream);
+
 /* ---- Densification statistics of one iteration (train_4DGS.py:266; scene/gaussian_model.py:713-715
  * add_densification_stats), in place, for the Gaussians with radii[i] > 0:
  *   max_radii2D[i] = max(max_radii2D[i], radii[i]);  xyz_gradient_accum[i] += |viewspace_grad[i, :2]|;  denom[i] += 1.
