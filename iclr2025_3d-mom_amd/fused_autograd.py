@@ -12,6 +12,14 @@ Every call owns its buffers (they come from torch's caching allocator), so sever
 backward -- the reference's batch loop -- and images may be kept.  Binning capacity follows the rasterizer module's sync mode
 (diff_gaussian_rasterization._C.set_sync_mode): "exact" waits for the frame's instance count like the reference's cudaMemcpy;
 "async" sizes from earlier frames and reports an overflow through the module's sticky flag.
+
+Two model shapes run as the node (node_width, NODE_WIDTHS): the shipped field, two HexPlane levels of 32 channels = 64 features, and
+two levels of 16 channels = 32 features (dnerf/eulerian_150_16).  The 16 x 2 node is the F == 32 branch of
+fused_step.FusedStep.forward_backward cut in two, with that branch's one-launch field written as the two launches whose bits it
+gives (16-channel HexPlane forward, MLP forward on 32 features: DESIGN 3.12) for their RAW outputs, torch's own
+exp / normalize / sigmoid on them (the image is then the op-by-op path's bit for bit, DESIGN 3.9 / 3.10), the shared rasterizer;
+backward: rasterizer, the MLP backward on 32 features, the 16-channel HexPlane backward.  feat / dfeat rows are as wide as the
+model's feature row, and so the buffer sets of the two shapes never mix (the width is part of the free list's key).
 """
 import ctypes as C
 
@@ -20,9 +28,14 @@ import torch
 from . import _native as N
 from . import ops
 from .diff_gaussian_rasterization import _C as RC
+from .fused_step import step_features
 
 
 DIRECT_GRADS = True      # False: always return the parameter gradients through the autograd graph
+
+# The feature widths (fused_step.step_features) gradient-mode render() runs as one node; every other model goes op by op.  32 is here
+# by the routing rule of DESIGN 3.6, measured in DESIGN 3.12 (tools/autograd16_rate.py); (64,) keeps 16 x 2 models op by op.
+NODE_WIDTHS = (64, 32)
 
 
 class grads_through_graph:
@@ -43,7 +56,9 @@ class grads_through_graph:
 # Internal buffers of a render() call (what no caller ever sees: the field's outputs, the rasterizer's geometry and image state, the
 # backward's intermediate gradients and scratch) are handed from one call to the next through a free list per (P, W, H, stream)
 # instead of going back to torch's allocator and being asked for again: twenty torch.empty calls and as many frees per iteration,
-# 40 us of the host time that paces this path.  A call takes a set in its forward and gives it back at the end of its backward; a
+# 40 us of the host time that paces this path.  (The key also holds the stage and the feature width F: a 32 x 2 and a 16 x 2 model of
+# one size in one process must not hand each other sets -- a [P,32] feat given to the 64-feature field kernel is a write past its
+# end.)  A call takes a set in its forward and gives it back at the end of its backward; a
 # call that is never back-propagated simply keeps its set (the garbage collector frees it), and several cameras rendered before one
 # backward each hold a set of their own.  The tensors a caller CAN hold -- image, depth, radii, every gradient -- are never pooled.
 _POOL = {}
@@ -65,20 +80,35 @@ def _pool_give(key, bufs):
 
 
 class _State:
-    __slots__ = ("pool_key", "bufs", "a", "keep", "P", "W", "H", "cam_time", "order", "porders", "feat", "a0", "pts", "sc_d", "rot_d", "sc", "rot", "op",
+    __slots__ = ("pool_key", "bufs", "a", "keep", "P", "W", "H", "F", "cam_time", "order", "porders", "feat", "a0", "pts", "sc_d", "rot_d", "sc", "rot", "op",
                  "color", "depth", "radii", "geom", "img", "binning", "cap", "xyz", "scal", "rotq", "opac", "flow", "coef", "planes",
                  "mlp", "field", "f_dc", "f_rest", "ready", "side")
 
 
-def field_params(pc):
-    """(planes, MLP tensors) of the deformation field, cached on the model until a parameter object is replaced (walking the
-    nn.Module tree costs 70 us per call)."""
-    dn = pc._deformation.deformation_net
+def _field_cache(dn):
+    """(first plane, first MLP tensor, planes, MLP tensors, step_features) of a deformation net, cached on it until a parameter
+    object is replaced (walking the nn.Module tree costs 70 us per call, and _field16_fusable() behind step_features walks every
+    plane: neither is paid per frame on a path the host paces)."""
     c = getattr(dn, "_fa_params", None)
     if c is None or c[0] is not dn.grid.grids[0][0] or c[1] is not dn.feature_out[0].weight:
         planes, mlp = [p for lv in dn.grid.grids for p in lv], dn._fused_params()
-        c = dn._fa_params = (planes[0], mlp[0], planes, mlp)
+        c = dn._fa_params = (planes[0], mlp[0], planes, mlp, step_features(dn))
+    return c
+
+
+def field_params(pc):
+    """(planes, MLP tensors) of the deformation field (_field_cache)."""
+    c = _field_cache(pc._deformation.deformation_net)
     return c[2], c[3]
+
+
+def node_width(dn):
+    """Width of the HexPlane feature row at which gradient-mode render() runs deformation net dn as ONE node, or 0 if it goes op by
+    op: fused_step.step_features(dn) -- 64 for the shipped field (Deformation._fusable), 32 for two levels of 16 channels
+    (Deformation._field16_fusable) where 32 is in NODE_WIDTHS.  The module's answer is cached with its parameter lists; NODE_WIDTHS
+    is read at every call."""
+    F = _field_cache(dn)[4]
+    return F if F == 64 or F in NODE_WIDTHS else 0
 
 
 def _forward_desc(pc, field, planes, mlp):
@@ -103,14 +133,23 @@ def _forward(pc, cam, bg, delta_scale, scaling_modifier, debug, coarse):
     st.xyz, st.f_dc, st.f_rest, st.scal, st.rotq, st.opac = ops.gaussian_params(pc, "fused render()")
     st.planes, st.mlp, st.field, st.ready, st.side = (), (), None, None, None
     e = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
-    st.pool_key = (P, W, H, dev, s, coarse)
+    F = 0
+    if not coarse:
+        fc = _field_cache(pc._deformation.deformation_net)
+        F = fc[4]
+        if F not in (64, 32):
+            raise N.MomError("fused render(): the deformation field is neither the shipped one (two HexPlane levels of 32 channels) nor two "
+                             "levels of 16 channels inside the field kernel's limits (fused_autograd.node_width)")
+    st.F = F
+    st.pool_key = (P, W, H, dev, s, coarse, F)
     b = st.bufs = _pool_take(st.pool_key)
     if b is None:
         b = st.bufs = {"geom": torch.empty(lib.mom_raster_geom_bytes(P), dtype=torch.uint8, device=dev),
                        "img": torch.empty(lib.mom_raster_image_bytes(W, H), dtype=torch.uint8, device=dev),
                        "nr_dev": torch.empty(1, dtype=torch.int32, device=dev)}
         if not coarse:
-            b.update(feat=e(P, 64), a0=e(P, 64), pts=e(P, 3), sc_d=e(P, 3), rot_d=e(P, 4), sc=e(P, 3), rot=e(P, 4), op=e(P, 1))
+            # (feat rows are F floats; a0 = relu(h0) is the network's width whatever feeds it)
+            b.update(feat=e(P, F), a0=e(P, 64), pts=e(P, 3), sc_d=e(P, 3), rot_d=e(P, 4), sc=e(P, 3), rot=e(P, 4), op=e(P, 1))
     st.color, st.depth = e(3, H, W), e(1, H, W)
     st.radii = torch.empty(P, dtype=torch.int32, device=dev)
     st.geom, st.img = b["geom"], b["img"]
@@ -119,7 +158,7 @@ def _forward(pc, cam, bg, delta_scale, scaling_modifier, debug, coarse):
         means, sc, rot, op = st.xyz, st.scal, st.rotq, st.opac
     else:
         field = st.field = pc._deformation.deformation_net.grid
-        st.planes, st.mlp = field_params(pc)
+        st.planes, st.mlp = fc[2], fc[3]
         flow = st.flow = pc._scene_flow if pc._scene_flow.is_contiguous() else pc._scene_flow.contiguous()
         st.cam_time = float(cam.time)
         st.coef = float(delta_scale * cam.frame_num)
@@ -131,8 +170,25 @@ def _forward(pc, cam, bg, delta_scale, scaling_modifier, debug, coarse):
         means, sc, rot, op = st.pts, st.sc, st.rot, st.op
         hp, keep, md = _forward_desc(pc, field, st.planes, st.mlp)
         st.keep += (keep,)
-        ops.field_forward(hp, md, P, st.xyz, st.cam_time, st.order, st.scal, st.rotq, flow, st.coef, st.pts, st.sc_d, st.rot_d,
-                          st.feat, st.a0, st.opac, st.sc, st.rot, st.op, s)
+        if F == 32:
+            # two levels of 16 channels: the 16-channel HexPlane forward and the MLP forward on 32 features, raw outputs only; the
+            # activated copies are torch's exp / normalize / sigmoid, as in FusedStep16 and FusedRender and for the same reason --
+            # the kernels' expf / quaternion norm differ from torch's in last bits, and the image would no longer be the op-by-op
+            # path's.  The two launches and not the one-launch field of csrc/deform_field16.hip, whose bits and
+            # time they are (96 against 97 us at 200 k points): that kernel reports under the hexplane_fwd profile slot
+            # alone, and gradient-mode render() of such a model is held to launching the MLP forward under its own slot
+            # (tests/test_mlp32_gpu.py); DESIGN 3.12
+            N.check(lib.mom_hexplane_forward(C.byref(hp), P, st.xyz.data_ptr(), None, st.cam_time,
+                                             None if st.order is None else st.order.data_ptr(), st.feat.data_ptr(), s), "hexplane_fwd")
+            N.check(lib.mom_deform_forward_n(C.byref(md), P, 32, st.feat.data_ptr(), st.xyz.data_ptr(), st.scal.data_ptr(),
+                                             st.rotq.data_ptr(), flow.data_ptr(), st.coef, st.pts.data_ptr(), st.sc_d.data_ptr(),
+                                             st.rot_d.data_ptr(), st.a0.data_ptr(), s), "deform_fwd")
+            torch.exp(st.sc_d, out=st.sc)
+            torch.nn.functional.normalize(st.rot_d, out=st.rot)
+            torch.sigmoid(st.opac, out=st.op)
+        else:
+            ops.field_forward(hp, md, P, st.xyz, st.cam_time, st.order, st.scal, st.rotq, flow, st.coef, st.pts, st.sc_d, st.rot_d,
+                              st.feat, st.a0, st.opac, st.sc, st.rot, st.op, s)
     st.a = ops.raster_args(cam, view, proj, campos, bg, P, pc.active_sh_degree, means, st.f_dc, st.f_rest, op, sc, rot, coarse,
                            scaling_modifier, debug, RC._state["keep_all_tiles"])   # set_keep_all_tiles(): the reference's lists
     _raster_forward(lib, st.a, st, b["nr_dev"], P, W, H, dev, s)
@@ -251,7 +307,7 @@ def _backward(st, dcolor, ddepth, direct=True):
         st.bufs = None
         return g2d, (gxyz, gdc, grest, gsc, grot, gop)
     if "dfeat" not in b:              # the deformation backward's intermediate gradient and scratch
-        b.update(dfeat=e(P, 64), scratch=torch.empty(lib.mom_deform_backward_scratch_bytes(P), dtype=torch.uint8, device=dev))
+        b.update(dfeat=e(P, st.F), scratch=torch.empty(lib.mom_deform_backward_scratch_bytes(P), dtype=torch.uint8, device=dev))
     overlap = ops.API_OVERLAP and direct
     ready = side = None
     if overlap:
@@ -262,7 +318,16 @@ def _backward(st, dcolor, ddepth, direct=True):
     gplanes, gmlp, hp, md, in_place = _field_grads(st, f, direct)
     dfeat, scratch = b["dfeat"], b["scratch"]
     # pts = xyz + dx(...): d xyz starts as d pts (already in gxyz); scale / rotation residuals likewise
-    if overlap:
+    if st.F == 32:
+        # the MLP backward on 32 features (csrc/deform_mlp32.hip), with or without the second stream as below
+        if overlap:
+            N.check(lib.mom_deform_backward_split_n(C.byref(md), P, 32, st.feat.data_ptr(), st.a0.data_ptr(), gxyz.data_ptr(),
+                                                    gsc.data_ptr(), grot.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), s, side),
+                    "deform_bwd")
+        else:
+            N.check(lib.mom_deform_backward_n(C.byref(md), P, 32, st.feat.data_ptr(), st.a0.data_ptr(), gxyz.data_ptr(), gsc.data_ptr(),
+                                              grot.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), s), "deform_bwd")
+    elif overlap:
         # with a second stream the MLP backward leaves an eighth of the chip free (for that Adam launch) and its partial-sum
         # reduction goes there too (csrc/deform_bwd_b3.hip); joined below
         N.check(lib.mom_deform_backward_split(C.byref(md), P, st.feat.data_ptr(), st.a0.data_ptr(), gxyz.data_ptr(), gsc.data_ptr(),

@@ -33,8 +33,10 @@ def _fused_path_applies(cam, pc, pipe, stage, override_color, cam_type, forward_
     """Whether this frame can take a fused launch sequence (fused_render.py without gradients, fused_autograd.py with them): fine
     stage with the shipped deformation configuration or coarse stage, SH colours and covariances computed by the rasterizer, an
     ordinary camera, everything on the GPU.  (Grad mode and pipe.per_op_autograd are for the caller to check.)
-    forward_only: the question of the no-grad branch, which also takes the same network on two levels of 16-channel planes
-    (Deformation._field16_fusable; fused_render.py has a field kernel for it, the gradient paths have none)."""
+    forward_only: the question of the no-grad branch, which asks the module's predicates: the shipped field, or the same network
+    on two levels of 16-channel planes (Deformation._field16_fusable).  The gradient branch asks fused_autograd.node_width(): the
+    same two shapes, the 16 x 2 one while 32 is in fused_autograd.NODE_WIDTHS; a field that predicate refuses (a plane beyond 1024
+    texels, 16 x 4, net_width 128 ...) keeps the op-by-op path."""
     if stage not in ("fine", "coarse") or override_color is not None or cam_type == "PanopticSports":
         return False
     if pipe.compute_cov3D_python or pipe.convert_SHs_python or not hasattr(cam, "device_tensors"):
@@ -46,7 +48,10 @@ def _fused_path_applies(cam, pc, pipe, stage, override_color, cam_type, forward_
     dn = getattr(pc._deformation, "deformation_net", None)
     if dn is None or not hasattr(dn, "_fusable"):
         return False
-    return dn._fusable() or (forward_only and dn._field16_fusable())
+    if forward_only:
+        return dn._fusable() or dn._field16_fusable()
+    from .. import fused_autograd
+    return fused_autograd.node_width(dn) != 0
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, stage="fine",

@@ -89,9 +89,10 @@ class Deformation(nn.Module):
 
     def _mlp_fusable(self):
         """The fused MLP op (ops.deform_mlp) applies: the _fusable() model, or the same network on 32 features from exactly two
-        levels of 16 channels (dnerf/eulerian_150_16; csrc/deform_mlp32.hip).  Wider than _fusable() on purpose: the fused
-        autograd path keys on _fusable() and keeps declining 16-channel fields (the fused step and no-grad render() take them
-        through _field16_fusable(): fused_step.step_features)."""
+        levels of 16 channels (dnerf/eulerian_150_16; csrc/deform_mlp32.hip).  Wider than _fusable() on purpose: it is
+        what the op-by-op path asks, whatever the planes' resolutions.  The fused step, no-grad render() and the one-node autograd
+        path take 16-channel fields through _field16_fusable(), which adds the field kernel's resolution limit
+        (fused_step.step_features, fused_autograd.node_width)."""
         if self._fusable():
             return True
         a = self.args
@@ -108,7 +109,8 @@ class Deformation(nn.Module):
         """The one-launch field forward for 16-channel planes (ops.field16_forward, csrc/deform_field16.hip) applies: the
         _mlp_fusable() network on a field that is not the shipped 32 x 2 one -- that is 32 features from exactly two levels of 16
         channels -- with every plane inside the kernel's resolution limit.  gaussian_renderer.render() asks for this or _fusable()
-        in its no-grad branch only; a field beyond the limit keeps rendering op by op."""
+        in its no-grad branch and, through fused_autograd.node_width, in its gradient branch; a field beyond the limit keeps rendering
+        op by op."""
         return (self._mlp_fusable() and not self._fusable()
                 and all(max(p.shape[2], p.shape[3]) <= self.FIELD16_MAX_RES for lv in self.grid.grids for p in lv))
 
