@@ -1,0 +1,273 @@
+"""The 3D motion optimisation module's fit: the [3,P] Eulerian scene flow from multi-view 2D flows.
+
+The reference's MotionOptimization.optimize_motion (train_motion.py:65-207) projects a point cloud into 14 x 5 views, samples each
+view's estimated 2D flow at the projected points and runs SGD on one [3,P] tensor so that the flowed points' projections move by
+those 2D flows.  Its output, MOM/scene_flow.pth, is the prior every deformation field of this package adds to its positions.  Here
+the preparation (valid sets, unflowed pixels: float64 numpy, cast as the reference casts) stays on the host and the whole SGD
+loop -- every epoch, every view -- is one HIP launch (ops.sceneflow_fit, csrc/sceneflow_fit.hip).
+
+    prepare_views      valid sets and unflowed pixels of a list of world-to-camera poses  -> ViewSet
+    fit_scene_flow     the fit itself, targets given per view at that view's valid points
+    optimize_motion    the reference's function: pose composition, griddata sampling, fit, our_flow
+    refit_scene_flow   a stage-1 directory's MOM/train_data.pth -> MOM/scene_flow.pth
+
+The rest of stage 1 (depth, the multi-view renders, the 2D flow estimator, the video GAN) is not part of this package.
+
+    python -m iclr2025_3d-mom_amd.motion --input_dir DIR [--train_iteration N]
+"""
+import os
+from dataclasses import dataclass
+from typing import List
+
+import numpy as np
+import torch
+
+from . import ops
+
+YZ_REVERSE = np.array([[1, 0, 0], [0, -1, 0], [0, 0, -1]], dtype=np.float64)     # train_motion.py:71
+
+
+@dataclass
+class ViewSet:
+    """What the fit needs of V views of P points.  R, T: float32 world-to-camera (train_motion.py:164-165 casts them);
+    valid[j]: the indices of view j's valid set, ascending (:173-177); pix0[j]: [2, n_j] float32, the unflowed pixels (:180,183)."""
+    P: int
+    H: int
+    W: int
+    R: np.ndarray
+    T: np.ndarray
+    valid: List[np.ndarray]
+    pix0: List[np.ndarray]
+
+    @property
+    def V(self):
+        return len(self.valid)
+
+
+def _pose(p):
+    """(R [3,3], T [3,1]) of a pose given as an (R, T) pair or as a 3x4 / 4x4 matrix, dtypes kept."""
+    if isinstance(p, (tuple, list)) and len(p) == 2:
+        R, T = np.asarray(p[0]), np.asarray(p[1])
+    else:
+        p = np.asarray(p)
+        R, T = p[:3, :3], p[:3, 3:4]
+    if R.shape != (3, 3) or T.size != 3:
+        raise ValueError(f"a world-to-camera pose is (R [3,3], T [3]) or a 3x4 / 4x4 matrix, got {R.shape} and {T.shape}")
+    return R, T.reshape(3, 1)
+
+
+def prepare_views(points, K, w2c_list, H, W):
+    """Valid sets and unflowed pixels exactly as train_motion.py:161-183 forms them: numpy in the dtypes given (the reference has
+    float32 points and K and float64 poses, so float64 throughout), `z > 0, 0 <= u <= W-1, 0 <= v <= H-1`, pixels cast to
+    float32 at the end.  A view without a single valid point raises ValueError: the reference skips such a view in one of its two
+    loops only, its lists go out of step and it cannot run either."""
+    points = np.asarray(points)
+    if points.ndim != 2 or points.shape[0] != 3:
+        raise ValueError(f"points must be [3, P], got {points.shape}")
+    K = np.asarray(K)
+    Rs, Ts, valid, pix0 = [], [], [], []
+    for j, pose in enumerate(w2c_list):
+        R, T = _pose(pose)
+        cam = R.dot(points) + T
+        pix = np.matmul(K, cam)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            idx = np.where(np.logical_and.reduce((pix[2] > 0, pix[0] / pix[2] >= 0, pix[0] / pix[2] <= W - 1,
+                                                  pix[1] / pix[2] >= 0, pix[1] / pix[2] <= H - 1)))[0]
+        if len(idx) == 0:
+            raise ValueError(f"view {j} sees none of the {points.shape[1]} points")
+        Rs.append(np.asarray(R, np.float32))
+        Ts.append(np.asarray(T, np.float32).reshape(3))
+        valid.append(idx)
+        pix0.append((pix[:2, idx] / pix[-1:, idx]).astype(np.float32))
+    if not valid:
+        raise ValueError("no views")
+    return ViewSet(P=points.shape[1], H=int(H), W=int(W), R=np.stack(Rs), T=np.stack(Ts), valid=valid, pix0=pix0)
+
+
+def learning_rates(epochs, lr=0.5, gamma=0.97):
+    """lr of every epoch as SGD + ExponentialLR hold it (train_motion.py:128-130,203): one multiplication per epoch, in Python
+    floats; the optimiser rounds it to float32 when it is used."""
+    out, cur = [], float(lr)
+    for _ in range(epochs):
+        out.append(cur)
+        cur = cur * gamma
+    return np.asarray(out, dtype=np.float32)
+
+
+def view_weights(views, divisor):
+    """w_j = (1 / divisor) / (2 n_j) in float32, in the order autograd forms it: the division of the summed loss by idx + 1,
+    then the mean over the view's 2 n_j entries."""
+    inv = np.float32(1.0) / np.float32(divisor)
+    return np.asarray([inv / np.float32(2 * len(v)) for v in views.valid], dtype=np.float32)
+
+
+def pack_views(views, gt):
+    """records [V,P,4] float32 = {pix0, gt} and valid [ceil(V/32),P] int32 bit words, on the host."""
+    V, P = views.V, views.P
+    if len(gt) != V:
+        raise ValueError(f"{len(gt)} targets for {V} views")
+    rec = np.zeros((V, P, 4), np.float32)
+    bits = np.zeros(((V + 31) // 32, P), np.uint32)
+    for j in range(V):
+        g = gt[j].detach().cpu().numpy() if torch.is_tensor(gt[j]) else np.asarray(gt[j])
+        idx = views.valid[j]
+        if g.shape != (2, len(idx)):
+            raise ValueError(f"the target of view {j} must be [2, {len(idx)}] (one column per valid point), got {g.shape}")
+        rec[j, idx, 0:2] = views.pix0[j].T
+        rec[j, idx, 2:4] = g.T.astype(np.float32)
+        bits[j // 32, idx] |= np.uint32(1 << (j % 32))
+    return rec, bits.view(np.int32)
+
+
+def fit_scene_flow(points, K, views, gt, epochs=200, lr=0.5, gamma=0.97, divisor=None, device=None):
+    """The fit (train_motion.py:125-207).  points [3,P]; K 3x3; views: a ViewSet of the same points; gt: per view a [2, n_j]
+    array or tensor, the 2D flow at that view's valid points (the reference's GT_list); divisor: the reference's idx + 1 (:189),
+    one more than the slot index of the last view that has a flow -- the number of views when none was skipped, the default.
+    Returns (flow [3,P], loss [E], flow2d_last [V,P,2]) on the device: the scene flow, every epoch's loss, and the last epoch's
+    2D flow of every point in every view (0 where the point is not in the view's valid set).  Everything is enqueued on the current
+    stream; nothing is read back."""
+    dev = torch.device("cuda" if device is None else device)
+    pts = np.ascontiguousarray(np.asarray(points.detach().cpu() if torch.is_tensor(points) else points), dtype=np.float32)
+    if pts.shape != (3, views.P):
+        raise ValueError(f"points must be [3, {views.P}] like the views', got {pts.shape}")
+    if epochs < 0:
+        raise ValueError("epochs must not be negative")
+    rec, bits = pack_views(views, gt)
+    w = view_weights(views, views.V if divisor is None else divisor)
+    K_host = np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, dtype=np.float32)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    V, P = views.V, views.P
+    flow = torch.zeros((3, P), dtype=torch.float32, device=dev)
+    loss = torch.zeros(epochs, dtype=torch.float32, device=dev)
+    flow2d = torch.zeros((V, P, 2), dtype=torch.float32, device=dev)
+    ops.sceneflow_fit(up(pts), K_host, up(views.R), up(views.T), up(w), up(rec), up(bits), up(learning_rates(epochs, lr, gamma)),
+                      flow, loss, flow2d)
+    return flow, loss, flow2d
+
+
+def _griddata():
+    try:
+        from scipy.interpolate import griddata
+    except ImportError as e:
+        raise ImportError("optimize_motion samples the 2D flow images with scipy.interpolate.griddata (train_motion.py:22,120,198): "
+                          "scipy is needed for it and for refit_scene_flow; fit_scene_flow takes already sampled targets") from e
+    return griddata
+
+
+def _pixel_grid(H, W):
+    x, y = np.meshgrid(np.arange(W, dtype=np.float32), np.arange(H, dtype=np.float32), indexing="xy")    # train_motion.py:87-88
+    return np.stack((x, y), axis=-1).reshape(-1, 2)
+
+
+def sample_flow_image(flow_image, pix0, H, W):
+    """A [1,2,H,W] flow image at the pixels pix0 [2,n] (train_motion.py:117-121): linear griddata over the pixel grid, 0 outside."""
+    g = torch.as_tensor(flow_image).permute(2, 3, 1, 0).squeeze().reshape(H * W, 2).cpu().clone().numpy()
+    return _griddata()(_pixel_grid(H, W), g, np.asarray(pix0).transpose(1, 0), method="linear", fill_value=0).T
+
+
+def _fit_slots(train_data, slots, K, H, W, train_iteration, device=None):
+    """slots: per view slot its (R, T) world-to-camera pose, or None for a slot without a flow (the reference's non_frame_idx).
+    Frame k of train_data carries the k-th present slot's T2C_flow (train_motion.py:81-85)."""
+    present = [i for i, s in enumerate(slots) if s is not None]
+    if not present:
+        raise ValueError("no view has a 2D flow to fit")
+    points = train_data["pcd_points"]
+    views = prepare_views(points, K, [slots[i] for i in present], H, W)
+    gt = []
+    for k, _ in enumerate(present):
+        # float64 pixels, as the reference hands them to griddata (:115,120)
+        R, T = _pose(slots[present[k]])
+        pix = np.matmul(np.asarray(K), R.dot(np.asarray(points)) + T)
+        idx = views.valid[k]
+        gt.append(sample_flow_image(train_data["frames"][k]["T2C_flow"][0], pix[:2, idx] / pix[-1:, idx], H, W))
+    flow, loss, flow2d = fit_scene_flow(points, K, views, gt, epochs=train_iteration, divisor=present[-1] + 1, device=device)
+    return views, present, gt, flow, loss, flow2d
+
+
+def optimize_motion(train_data, render_poses, internal_poses, K, H, W, non_frame_idx=(), train_iteration=200, device=None):
+    """MotionOptimization.optimize_motion (train_motion.py:65-207) without its unused arguments: view slot idx = i * len(internal)
+    + j has the pose internal[j] o render[i] (:91-97); slots in non_frame_idx have no flow; the k-th remaining slot takes
+    train_data['frames'][k]['T2C_flow'][0].  After the fit each fitted slot's last-epoch 2D flow is resampled onto the pixel
+    grid and appended to train_data['frames'][idx]['our_flow'] -- indexed by the SLOT, as the reference does (:200).
+    Returns (train_data, scene_flow [3,P] on the device)."""
+    render_poses, internal_poses = np.asarray(render_poses), np.asarray(internal_poses)
+    slots = []
+    for i in range(len(render_poses)):
+        for j in range(len(internal_poses)):
+            idx = i * len(internal_poses) + j
+            if idx in non_frame_idx:
+                slots.append(None)
+                continue
+            Rw2i, Tw2i = render_poses[i, :3, :3], render_poses[i, :3, 3:4]
+            Ri2j, Ti2j = internal_poses[j, :3, :3], internal_poses[j, :3, 3:4]
+            slots.append((np.matmul(Ri2j, Rw2i), np.matmul(Ri2j, Tw2i) + Ti2j))
+    views, present, _, flow, _, flow2d = _fit_slots(train_data, slots, K, H, W, train_iteration, device)
+    if train_iteration > 0:
+        griddata, grid = _griddata(), _pixel_grid(H, W)
+        flow2d = flow2d.cpu().numpy()
+        points = np.asarray(train_data["pcd_points"])
+        for k, idx in enumerate(present):
+            R, T = _pose(slots[idx])
+            pix = np.matmul(np.asarray(K), R.dot(points) + T)
+            v = views.valid[k]
+            final = griddata((pix[:2, v] / pix[-1:, v]).transpose(1, 0), flow2d[k, v], grid, method="linear",
+                             fill_value=0).reshape(H, W, 2)
+            train_data["frames"][idx]["our_flow"].append(torch.tensor(np.transpose(final, (2, 0, 1))).unsqueeze(0))
+    return train_data, flow
+
+
+def pose_from_transform_matrix(transform_matrix):
+    """The world-to-camera (R, T) a frame's transform_matrix was made of: the inverse of train_motion.py:156-159, where
+    Rj2w = (yz_reverse R)^T and Tj2w = -Rj2w (yz_reverse T)."""
+    m = np.asarray(transform_matrix, dtype=np.float64)
+    Rj2w, Tj2w = m[:3, :3], m[:3, 3:4]
+    return np.matmul(YZ_REVERSE, Rj2w.T), -np.matmul(YZ_REVERSE, np.matmul(Rj2w.T, Tj2w))
+
+
+def transform_matrix_from_pose(R, T):
+    """train_motion.py:156-159."""
+    R, T = np.asarray(R, np.float64), np.asarray(T, np.float64).reshape(3, 1)
+    Rj2w = np.matmul(YZ_REVERSE, R).T
+    Tj2w = -np.matmul(Rj2w, np.matmul(YZ_REVERSE, T))
+    return np.concatenate((np.concatenate((Rj2w, Tj2w), axis=1), np.array([[0, 0, 0, 1.0]])), axis=0)
+
+
+def stage1_intrinsics(H, W):
+    """K of a stage-1 output (train_motion.py:47-62): the fixed focal length, the principal point at the image centre."""
+    from .scene.dataset_readers import FOCAL
+    return np.array([[FOCAL * (W / H), 0., W / 2], [0., FOCAL, H / 2], [0., 0., 1.]]).astype(np.float32)
+
+
+def refit_scene_flow(input_dir, train_iteration=200, device=None):
+    """Fits the scene flow of a stage-1 directory again from what MOM/train_data.pth holds -- the point cloud, every frame's pose
+    (its transform_matrix) and 2D flow (T2C_flow) -- and writes MOM/scene_flow.pth.  A frame with an empty T2C_flow list is a view
+    without a flow.  Returns the [3,P] flow (a CPU tensor, what is written)."""
+    from .scene.dataset_readers import load_train_data
+    mom = os.path.join(input_dir, "MOM")
+    data = load_train_data(os.path.join(mom, "train_data.pth"))
+    H, W = int(data["H"]), int(data["W"])
+    frames = data["frames"]
+    slots = [pose_from_transform_matrix(fr["transform_matrix"]) if len(fr.get("T2C_flow", ())) else None for fr in frames]
+    if all(s is None for s in slots):
+        raise ValueError(f"{mom}/train_data.pth: no frame carries a T2C_flow image (every list is empty), so there is nothing to "
+                         "fit the scene flow to")
+    # _fit_slots reads the k-th present slot's flow from frame k: hand it the frames that have one, in order
+    with_flow = dict(data, frames=[fr for fr, s in zip(frames, slots) if s is not None])
+    _, _, _, flow, _, _ = _fit_slots(with_flow, slots, stage1_intrinsics(H, W), H, W, train_iteration, device)
+    flow = flow.cpu()
+    torch.save(flow, os.path.join(mom, "scene_flow.pth"))
+    return flow
+
+
+def main(argv=None):
+    from argparse import ArgumentParser
+    ap = ArgumentParser(description="Fit MOM/scene_flow.pth of a stage-1 directory to the 2D flows in its MOM/train_data.pth")
+    ap.add_argument("--input_dir", required=True)
+    ap.add_argument("--train_iteration", type=int, default=200)
+    a = ap.parse_args(argv)
+    flow = refit_scene_flow(a.input_dir, a.train_iteration)
+    print(f"scene_flow.pth: {tuple(flow.shape)}, largest magnitude {float(flow.abs().max()):.6g}")
+
+
+if __name__ == "__main__":
+    main()

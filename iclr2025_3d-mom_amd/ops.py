@@ -511,6 +511,61 @@ def densify_round(clone_mask, split_mask, tensors_by_role, z=None):
     return result
 
 
+# --------------------------------------------------------------------------- scene-flow fit
+def sceneflow_fit(points, K, R, T, w, records, valid, lr, flow, loss=None, flow2d_last=None):
+    """The motion optimisation module's SGD loop (train_motion.py:125-207), every epoch and every view in one launch
+    (csrc/sceneflow_fit.hip; include/mom4d.h has the arithmetic).  Enqueued on the current stream; nothing is read back.
+
+    points [3,P], R [V,3,3], T [V,3], w [V], records [V,P,4] = {pix0, gt}, lr [E]: contiguous float32 on one device;
+    valid [ceil(V/32),P] int32 bit words; K: the 3x3 intrinsics as HOST numbers (a CPU tensor, an array or nested lists);
+    flow [3,P] is updated in place; loss [E] and flow2d_last [V,P,2] are optional outputs.  Returns flow."""
+    _need_cuda(points, "sceneflow_fit")
+    dev = points.device
+    if points.dim() != 2 or points.shape[0] != 3:
+        raise N.MomError(f"sceneflow_fit: points must be [3,P], got {tuple(points.shape)}")
+    P = points.shape[1]
+    if R.dim() != 3 or tuple(R.shape[1:]) != (3, 3) or R.shape[0] < 1:
+        raise N.MomError(f"sceneflow_fit: R must be [V,3,3] with V >= 1, got {tuple(R.shape)}")
+    V = R.shape[0]
+    if lr.dim() != 1:
+        raise N.MomError(f"sceneflow_fit: lr must be [E], got {tuple(lr.shape)}")
+    E = lr.shape[0]
+    words = (V + 31) // 32
+    want = [("points", points, (3, P), torch.float32), ("R", R, (V, 3, 3), torch.float32), ("T", T, (V, 3), torch.float32),
+            ("w", w, (V,), torch.float32), ("records", records, (V, P, 4), torch.float32), ("valid", valid, (words, P), torch.int32),
+            ("lr", lr, (E,), torch.float32), ("flow", flow, (3, P), torch.float32)]
+    if loss is not None:
+        want.append(("loss", loss, (E,), torch.float32))
+    if flow2d_last is not None:
+        want.append(("flow2d_last", flow2d_last, (V, P, 2), torch.float32))
+    for name, t_, shape, dtype in want:
+        _need_cuda(t_, "sceneflow_fit")
+        if tuple(t_.shape) != shape or t_.dtype != dtype or t_.device != dev or not t_.is_contiguous():
+            raise N.MomError(f"sceneflow_fit: {name} must be a contiguous {dtype} {list(shape)} tensor on {dev}, "
+                             f"got {t_.dtype} {list(t_.shape)} on {t_.device}")
+    if flow.requires_grad or (loss is not None and loss.requires_grad):
+        raise N.MomError("sceneflow_fit: flow is updated in place and takes no gradient (the kernel is the optimiser)")
+    if torch.is_tensor(K):
+        if K.is_cuda:
+            raise N.MomError("sceneflow_fit: K is read on the host; pass a CPU tensor or an array (a device tensor would be a synchronisation)")
+        K = K.detach().numpy()
+    K = np.asarray(K, dtype=np.float32)
+    if K.shape != (3, 3):
+        raise N.MomError(f"sceneflow_fit: K must be 3x3, got {K.shape}")
+    if K[0, 1] != 0 or K[1, 0] != 0 or K[2, 0] != 0 or K[2, 1] != 0 or K[2, 2] != 1:
+        raise N.MomError("sceneflow_fit: K must be [[fx,0,cx],[0,fy,cy],[0,0,1]]")
+    lib = N.lib()
+    k9 = (C.c_float * 9)(*[float(x) for x in K.reshape(-1)])
+    scratch, nbytes = None, 0
+    if loss is not None and P:
+        nbytes = lib.mom_sceneflow_fit_scratch_bytes(P, V, E)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    N.check(lib.mom_sceneflow_fit(P, V, E, N.ptr(points), k9, N.ptr(R), N.ptr(T), N.ptr(w), N.ptr(records), N.ptr(valid), N.ptr(lr),
+                                  N.ptr(flow), N.ptr(loss), N.ptr(flow2d_last), N.ptr(scratch), nbytes, N.current_stream()),
+            "mom_sceneflow_fit")
+    return flow
+
+
 # --------------------------------------------------------------------------- densification statistics
 def densify_stats(radii, viewspace_grad, max_radii2D, xyz_gradient_accum, denom, skip_flag=None, stream=None):
     """In place, for the Gaussians with radii > 0: running maximum radius, accumulated |dL/d mean2D| and its count

@@ -21,6 +21,7 @@
  *   l1_loss / ssim                   utils/loss_utils.py:23-24,52-92
  *   compute_regulation               scene/gaussian_model.py:730-769
  *   boolean-mask row compaction      scene/gaussian_model.py:424-459
+ *   the scene-flow fit (SGD loop)    train_motion.py:125-207
  */
 #ifndef MOM4D_H_INCLUDED
 #define MOM4D_H_INCLUDED
@@ -587,6 +588,31 @@ int mom_deform_field16_forward(const MomHexPlane* hp, const MomDeformMLP* w, int
                                float flow_coef, float* pts, float* scales, float* rots, float* feat_save, float* a0_save,
                                const float* opacity_raw, float* scales_act, float* rots_act, float* opacity_act, void* scratch,
                                mom_stream_t stream);
+
+/* ---- the scene-flow fit of the motion optimisation module (train_motion.py:125-207 MotionOptimization.optimize_motion) ----
+ * SGD on the [3,P] Eulerian scene flow against V views' 2D flows, all E epochs in one launch: a thread owns a point and keeps its
+ * flow in registers (csrc/sceneflow_fit.hip).  Per epoch e (train_motion.py:134-203), with q = p + f:
+ *     c = R_j q + T_j, h = K c, (u, v) = (h_x, h_y) / h_z                      train_motion.py:169-172,181
+ *     d = ((u, v) - pix0) - gt                                                 :184,187 (utils/loss_utils.py l1_loss)
+ *     loss[e] = sum over j and the view's valid points of w_j (|d_x| + |d_y|)  :187-189; w_j = (1 / divisor) / (2 n_j)
+ *     f -= lr[e] * d loss[e] / d f, sign(0) = 0                                :190-193, once per epoch; lr[e] = 0.5 * 0.97^e, :128-130,203
+ *   points  [3,P]; K: HOST memory, the row-major 3x3 [[fx,0,cx],[0,fy,cy],[0,0,1]] of train_motion.py:58-62 (anything else: MOM_EINVAL)
+ *   R [V,3,3], T [V,3] world to camera (:147-153 composes them); w [V]
+ *   records [V,P,4] = {pix0.x, pix0.y, gt.x, gt.y} (16-byte aligned): the unflowed pixel of :180,183 and the estimated flow sampled
+ *           there (:120); entries of invalid (view, point) pairs are read and ignored
+ *   valid   [ceil(V/32),P] words: bit j % 32 of valid[j / 32][p] = point p is in view j's valid set (:173-177)
+ *   lr [E]; flow [3,P] in and out (the reference starts from zeros, helpmotion.py:27)
+ *   loss [E] or null; flow2d_last [V,P,2] or null: the last epoch's (u, v) - pix0, taken before the last update (:196-200), 0 where
+ *           invalid; not written when E == 0
+ *   scratch: mom_sceneflow_fit_scratch_bytes(P, V, E) bytes when loss is given (per-wave partial sums, added in a fixed order by a
+ *           second launch on the same stream: no atomics, the same bits on every run); otherwise not read and may be null
+ * Stream-ordered, no allocation, no copy, no synchronisation.  P == 0 does nothing.  V <= 0, E < 0, P < 0, a null required pointer,
+ * a misaligned records / flow2d_last or a scratch_bytes below the sizing function's value: MOM_EINVAL before anything is launched.
+ * Nothing guards h_z <= 0 once the flow has moved a valid point behind a camera: inf / nan there, as in the reference. */
+size_t mom_sceneflow_fit_scratch_bytes(int P, int V, int E);
+int mom_sceneflow_fit(int P, int V, int E, const float* points, const float* K, const float* R, const float* T, const float* w,
+                      const float* records, const uint32_t* valid, const float* lr, float* flow, float* loss, float* flow2d_last,
+                      void* scratch, size_t scratch_bytes, mom_stream_t stream);
 
 /* ---- rendered image -> 8-bit interleaved RGB (render_4DGS.py:64 torchvision.utils.save_image: x * 255 + 0.5, clamp, truncate;
  * CHW -> HWC) in one pass, so that a frame can leave the device as the bytes a PNG encoder takes.  img [C,H,W] floats, out [H,W,C]
