@@ -1,20 +1,20 @@
 // Deformation field in one launch for 16-channel HexPlane fields (dnerf/eulerian_150_16: two levels of 16 channels, net_width 64,
 // defor_depth 0), forward, one timestamp for all points, gfx950.
 //
-// The result of mom_hexplane_forward (channels 16, two levels; hexplane16.hip) followed by mom_deform_forward_activated_n
+// The result of mom_hexplane_forward (channels 16, two levels; hexplane.hip at C = 16) followed by mom_deform_forward_activated_n
 // (in_features 32; deform_mlp32.hip), bit for bit, without feat[P,32] in between: a wave gathers the 32 features of its tile of 32
 // Gaussians into LDS, reads them back as the trunk layer's B operand and runs deform32_fwd_kernel's MLP on them.  fp32 throughout
 // (v_mfma_f32_32x32x2_f32, the k-ascending chains of deform_mlp_dev.h / deform_mlp32_dev.h): no bf16 split and no per-frame time
 // lines here -- both reassociate sums, and a no-grad render() of such a model has to give the image of the op-by-op route.
 //
-// Gather (the lane mapping of hexplane16.hip): sixteen lanes own one (point, level), lane = channel; the wave's four groups take
+// Gather (the lane mapping of hexplane.hip at C = 16): sixteen lanes own one (point, level), lane = channel; the wave's four groups take
 // the points 4 i + q of the tile, i = 0..7, first at level 0, then at level 1.  What a (point, level) needs of its position is
 // separable by axis -- cell index and fraction along x, y, z at that level's resolution -- and is computed ONCE, by lane
 // (point, level) of the wave, into a 16-byte LDS record {x0 | y0 << 10 | z0 << 20, bx, by, bz}; the time axis is the same for every
 // point.  The sixteen lanes of a group read the record as one broadcast and form the six planes' offsets and weights from it with
-// the expressions of hexplane16.hip's make_rec_fwd (ATen's weights from b = ix - x0 and 1 - b; a corner outside the plane gets
+// the expressions of hexplane.hip's make_rec_fwd (ATen's weights from b = ix - x0 and 1 - b; a corner outside the plane gets
 // weight exactly 0 and the address of its neighbour), so every sample, and the product over the planes in the reference's order,
-// is that kernel's.  hexplane16.hip keeps 32-byte records per (point, PLANE), 6 KB per wave and level: sixteen waves of those do
+// is that kernel's.  hexplane.hip keeps 32-byte records per (point, PLANE), 6 KB per wave and level: sixteen waves of those do
 // not fit beside the weights.
 //
 // LDS, 1024 threads = sixteen waves around one copy of the weights (deform_mlp_dev.h's map, 70 720 B):
@@ -58,7 +58,7 @@ __device__ __forceinline__ void axis_cell(float c, int size, int& i0, float& b)
     b = ix - (float)i0;
 }
 
-// one plane's bilinear sample at this lane's channel (hexplane16_fwd4_kernel's, term by term): `pl` already points at the channel,
+// one plane's bilinear sample at this lane's channel (hexplane_fwd4_kernel<16>'s, term by term): `pl` already points at the channel,
 // o00 is the byte offset of texel (y0, x0), sx / sy the byte steps to x0 + 1 / y0 + 1 (0 when that neighbour is outside)
 __device__ __forceinline__ float sample16(const float* __restrict__ pl, unsigned o00, unsigned sx, unsigned sy, float ax, float bx,
                                           float ay, float by)

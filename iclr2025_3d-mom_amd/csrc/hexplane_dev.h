@@ -1,4 +1,4 @@
-// Device helpers of the HexPlane kernels shared by hexplane.hip, hexplane16.hip and deform_field.hip: normalize_aabb and ATen's
+// Device helpers of the HexPlane kernels shared by hexplane.hip, deform_field.hip and deform_field16.hip: normalize_aabb and ATen's
 // grid_sampler_2d coordinate arithmetic (align_corners=True, padding_mode='border'), the kernel argument block and its host-side fill.
 #pragma once
 #include "mom_common.h"

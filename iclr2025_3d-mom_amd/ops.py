@@ -70,7 +70,7 @@ def _hexplane_desc(planes_by_level, aabb, grads_by_level=None, aabb_host=None):
 
 class HexPlaneFunction(torch.autograd.Function):
     """features[P, L*C] = HexPlaneField(xyz, t) (reference scene/hexplane.py:160-183), level-major; C = the planes' channel
-    count, 32 or 16 (csrc/hexplane.hip, csrc/hexplane16.hip; any other count is a MomError from the library)."""
+    count, 32 or 16 (csrc/hexplane.hip, one template instantiated for both; any other count is a MomError from the library)."""
 
     @staticmethod
     def forward(ctx, xyz, time, aabb, n_levels, order, aabb_host, plane_orders, *planes):

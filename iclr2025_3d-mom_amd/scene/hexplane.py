@@ -1,6 +1,6 @@
 """HexPlaneField with the reference's constructor, parameter names and numerics
 (reference scene/hexplane.py:109-183), whose forward/backward run as two fused HIP kernels
-(csrc/hexplane.hip for 32-channel planes, csrc/hexplane16.hip for 16-channel ones) instead of 12 grid_sample
+(csrc/hexplane.hip, instantiated for 32-channel and for 16-channel planes) instead of 12 grid_sample
 launches per direction.
 
 Planes keep the reference's logical shape [1, C, H, W] (regularisers, state_dict and the optimizer see

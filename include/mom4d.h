@@ -314,7 +314,7 @@ typedef struct MomHexPlane {
 } MomHexPlane;
 /* Planes are channel-last, [H][W][channels] floats.  feat [P, levels*channels] row-major, level-major within a row.  times:
  * optional per-point timestamps [P]; null -> `time` for all points (render() uses one timestamp per camera).  channels must be
- * 32 or 16 (MOM_EINVAL otherwise): 32 lanes own one (point, level) at 32 channels, 16 lanes at 16 (csrc/hexplane16.hip). */
+ * 32 or 16 (MOM_EINVAL otherwise): 32 lanes own one (point, level) at 32 channels, 16 lanes at 16 (one template over the channel count, csrc/hexplane.hip). */
 int mom_hexplane_forward(const MomHexPlane* hp, int P, const float* xyz, const float* times, float time,
                          const uint32_t* order, float* feat, mom_stream_t stream);
 /* dfeat [P, levels*channels]; plane gradients accumulate into hp->grads; dxyz [P,3] (may be null) is ACCUMULATED into.

@@ -346,13 +346,13 @@ def events(order, c, chunk, walk=None):
 
 # ---------------------------------------------------------------------------------------- walk lengths (the launchers' formulas)
 def per_half32(P):
-    """hexplane_backward (csrc/hexplane.hip): 512 workgroups x 8 half-waves, ranges rounded up to the 32-position chunk."""
+    """hexplane_backward_launch<32> (csrc/hexplane.hip): 512 workgroups x 8 half-waves, ranges rounded up to the 32-position chunk."""
     per = -(-P // (512 * 8))
     return -(-per // 32) * 32
 
 
 def per_group16(P):
-    """mom_launch_hexplane16_backward (csrc/hexplane16.hip): 512 workgroups x 16 groups, ranges rounded up to the 16-position chunk."""
+    """hexplane_backward_launch<16> (csrc/hexplane.hip): 512 workgroups x 16 groups, ranges rounded up to the 16-position chunk."""
     per = -(-P // (512 * 16))
     return -(-per // 16) * 16
 

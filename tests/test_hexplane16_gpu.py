@@ -1,6 +1,6 @@
 """HexPlane fields with 16-channel planes (kplanes_config output_coordinate_dim = 16: the reference's dnerf eulerian_150_16,
-dynerf and hypernerf configurations; resolution [64, 64, 64, 150], multires [1, 2] or [1, 2, 4]) on the GPU: the kernels of
-csrc/hexplane16.hip against oracle.torch_ref.hexplane_features (the reference's grid_sample sequence, channel-agnostic), and a
+dynerf and hypernerf configurations; resolution [64, 64, 64, 150], multires [1, 2] or [1, 2, 4]) on the GPU: the 16-channel
+instantiations of csrc/hexplane.hip against oracle.torch_ref.hexplane_features (the reference's grid_sample sequence, channel-agnostic), and a
 model of that shape through the op-by-op module, render() and one training iteration against the CPU oracle.
 
 Tolerances are those of tests/test_ops_gpu.py::test_hexplane_forward_backward_parity (forward rtol 2e-5 / atol 5e-6; gradients
@@ -99,38 +99,7 @@ def test_forward_backward_parity_16_channels(res, multires, t):
     _grads_close(fg, p3, ref, "per-point t")
 
 
-@pytest.mark.parametrize("P", [1, 63, 20000])
-def test_two_pass_backward_equals_generic_backward_on_shared_cells(P):
-    """8 x 8 x 8 cells and up to 20 000 points: many points per texel, several workgroups, a ragged last chunk and last group."""
-    t = 0.3
-    f = _field((8, 8, 8, 5), (1, 2))
-    pts = _points(P)
-    w = torch.randn(P, f.feat_dim, generator=torch.Generator().manual_seed(3))
-    ref = _oracle(f, pts, t, w)
-    fg = f.cuda()
-    levels = [list(g) for g in fg.grids]
-    host = fg.aabb_host()
-
-    def run(two_pass):
-        fg.zero_grad()
-        p = pts.cuda().requires_grad_(True)
-        order = ops.morton_order(p)
-        po = ops.hexplane_orders(p, levels, fg.aabb, aabb_host=host) if two_pass else None
-        feat = ops.hexplane_features(p, t, fg.aabb, levels, order=order, aabb_host=host, plane_orders=po)
-        (feat * w.cuda()).sum().backward()
-        torch.cuda.synchronize()
-        return p.grad.cpu().numpy(), [[q.grad.cpu().numpy().copy() for q in g] for g in fg.grids]
-
-    two, gen = run(True), run(False)
-    for got, what in ((two, "two-pass"), (gen, "generic")):
-        _close(got[0], ref[1], what + " dxyz")
-        for l in range(2):
-            for i in range(6):
-                _close(got[1][l][i], ref[2][l][i], f"{what} plane {l} {i}")
-    _close(two[0], gen[0], "two-pass vs generic dxyz")
-    for l in range(2):
-        for i in range(6):
-            _close(two[1][l][i], gen[1][l][i], f"two-pass vs generic plane {l} {i}")
+# (the two-pass backward against the generic one, both channel counts: tests/test_hexplane_widths_gpu.py)
 
 
 class HP:

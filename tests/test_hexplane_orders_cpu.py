@@ -138,7 +138,7 @@ def test_fresh_orders_have_runs_that_cross_a_chunk_boundary_and_stale_ones_have_
 
 def test_walk_lengths_of_the_multi_chunk_cases():
     """hexplane_backward:               per_half  = ceil(P / (512 * 8))  rounded up to 32  (MOM_HEX_SBLOCKS = 512 workgroups, 8 half-waves)
-    mom_launch_hexplane16_backward:  per_group = ceil(P / (512 * 16)) rounded up to 16  (kScatterBlocks = 512, 16 groups)
+    the same launcher at 16 channels:  per_group = ceil(P / (512 * 16)) rounded up to 16  (the same 512 workgroups, 16 groups)
 
          P        per_half  chunks   per_group  chunks
       131 072        32       1         16        1

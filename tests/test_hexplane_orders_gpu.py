@@ -2,8 +2,8 @@
 
 HexPlaneField rebuilds its Morton order and its six plane orders every REORDER_EVERY calls only (and may sort them while Adam
 writes the positions): 63 of 64 training steps walk an order that was sorted for other positions.  The contract is "an order is
-a permutation whatever the keys were, and only speed depends on it".  The scatter kernels (hexplane_bwd5_scatter_kernel<false / true>
-in csrc/hexplane.hip, hexplane16_scatter_kernel in csrc/hexplane16.hip) recompute every cell from the current positions and keep
+a permutation whatever the keys were, and only speed depends on it".  The scatter kernels (hexplane_bwd5_scatter_kernel<32, false / true>
+and hexplane_bwd5_scatter_kernel<16, false> in csrc/hexplane.hip) recompute every cell from the current positions and keep
 four texel rows and two line rows pending along the walk; a fresh sorted order shows them long runs of one cell and neighbouring
 cells next, any other order shows them a cell change at every position, the same parity slot evicted again and again, border
 positions between two positions of one interior cell, a ride row that stays while the cell changes.  And above 131 072 points every

@@ -1,4 +1,4 @@
-"""The 16-channel HexPlane forward and two-pass backward (csrc/hexplane16.hip) beside the 32-channel kernels (csrc/hexplane.hip)
+"""The 16-channel HexPlane forward and two-pass backward beside the 32-channel kernels (two instantiations of the templates of csrc/hexplane.hip)
 on the same points and resolutions: 200 000 points, resolution [64, 64, 64, 150], multires [1, 2], Morton order, plane orders given.
 
 Times are the event pairs of csrc/profile.hip around mom_hexplane_forward / mom_hexplane_backward (slots hexplane_fwd and
