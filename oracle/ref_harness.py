@@ -472,6 +472,168 @@ def g12_stage1_reader():
     np.savez_compressed(os.path.join(OUT, "g12_stage1_reader.npz"), **out)
 
 
+def _ref_settings(overlay=None):
+    """The reference's own ModelHiddenParams defaults (arguments/__init__.py) with the `ModelHiddenParams` / `OptimizationParams`
+    dicts of one of its settings files merged over them by its own merge_hparams -- what train_4DGS.py:432-443 does, with the
+    file read by runpy instead of mmcv (`_base_` followed the way mmcv does: the base's dicts updated by the file's).
+    Returns (hidden-parameter group, batch_size)."""
+    import runpy
+    from argparse import ArgumentParser
+    import arguments as RA
+    from utils.params_utils import merge_hparams
+    parser = ArgumentParser()
+    RA.ModelParams(parser), RA.PipelineParams(parser)
+    op_group, hp_group = RA.OptimizationParams(parser), RA.ModelHiddenParams(parser)
+    args = parser.parse_args([])
+
+    def read(path):
+        cfg = {k: v for k, v in runpy.run_path(path).items() if not k.startswith("__")}
+        base = cfg.pop("_base_", None)
+        if base is None:
+            return cfg
+        merged = read(os.path.join(os.path.dirname(path), base))
+        for k, v in cfg.items():
+            merged[k] = {**merged.get(k, {}), **v} if isinstance(v, dict) else v
+        return merged
+
+    if overlay is not None:
+        args = merge_hparams(args, read(os.path.join(REF, overlay)))
+    return hp_group.extract(args), int(op_group.extract(args).batch_size)
+
+
+G16_SHAPES = {"dynerf": ("arguments/dynerf/default.py", [6, 5, 8, 5]),
+              "hypernerf": ("arguments/hypernerf/default.py", [6, 5, 8, 5]),
+              "bare": (None, [5, 4, 6, 3])}
+# one change each on top of arguments/dnerf/eulerian_150_16.py (the dnerf overlay, 16-channel planes, net_width 64)
+G16_SWITCHES = {"static_mlp": dict(static_mlp=True, no_do=False, no_dshs=False),
+                "apply_rotation": dict(apply_rotation=True),
+                "grid_pe": dict(grid_pe=2),
+                "defor_depth": dict(defor_depth=3),
+                "opacity_only": dict(no_dx=True, no_ds=True, no_dr=True, no_do=False)}
+G16_FILES = {"dynerf": ["dynerf"], "hypernerf": ["hypernerf"], "bare": ["bare"],
+             "switches_a": ["static_mlp", "apply_rotation", "opacity_only"], "switches_b": ["grid_pe", "defor_depth"]}
+G16_CASES = ((0, 0, 0.0), (7, 1, 0.4))
+G16_OUTPUTS = ("pts", "scales", "rots", "opacity", "shs")
+G16_INPUTS = ("xyz", "scaling", "rotation", "opacity", "shs")
+
+
+def g16_model_shapes():
+    """The model shapes the reference ships besides the dnerf one, and five switches of Deformation.forward_dynamic, through the
+    reference's own deform_network: settings from its own defaults and settings files (only kplanes_config["resolution"] made
+    small), parameters from oracle/param_fill.py (not stored), 129 points.  Per case: the settings as JSON, the five outputs for
+    both (frame_num, delta_scale, t) triples and, for the second, the gradients of a weighted sum of all five outputs with respect
+    to the five inputs and every parameter (zero-length where the reference leaves None)."""
+    import copy
+    import json
+    from scene.deformation import deform_network
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import param_fill
+    n = 129
+    g = torch.Generator().manual_seed(11)
+    inputs = {"xyz": points(n, 5), "scaling": torch.randn(n, 3, generator=g), "rotation": torch.randn(n, 4, generator=g),
+              "opacity": torch.randn(n, 1, generator=g), "shs": torch.randn(n, 16, 3, generator=g)}
+    flow = torch.randn(n, 3, generator=g) * 1e-2
+    # loss weights for all five outputs, drawn as g2's and scaled by 2^-10: the gradients of a sum over 129 points then stay below
+    # 0.15, where the absolute tolerance they are compared at (1e-7) is 1e-6 of their scale or more -- above the last-bit noise
+    # between two float32 BLAS libraries (measured: up to 1.3e-6 of a tensor's scale on a cancelling sum)
+    ws = [torch.randn(n, 3, generator=g), torch.randn(n, 3, generator=g), torch.randn(n, 4, generator=g),
+          torch.randn(n, 1, generator=g), torch.randn(n, 16, 3, generator=g)]
+    ws = [w * 2.0 ** -10 for w in ws]
+    shared = {k: v.numpy() for k, v in inputs.items()}
+    shared["scene_flow"] = flow.numpy()
+    shared.update({f"w{i}": w.numpy() for i, w in enumerate(ws)})
+
+    def settings(name):
+        if name in G16_SHAPES:
+            hp, batch = _ref_settings(G16_SHAPES[name][0])
+            res = G16_SHAPES[name][1]
+        else:
+            hp, batch = _ref_settings("arguments/dnerf/eulerian_150_16.py")
+            for k, v in G16_SWITCHES[name].items():
+                assert hasattr(hp, k)
+                setattr(hp, k, v)
+            res = [6, 5, 8, 5]
+        own = list(hp.kplanes_config["resolution"])
+        hp.kplanes_config = dict(copy.deepcopy(hp.kplanes_config), resolution=list(res))
+        return hp, batch, own
+
+    def one(name):
+        hp, batch, own = settings(name)
+        net = deform_network(hp)
+        net.deformation_net.set_aabb([1.0, 1.2, 1.4], [-1.0, -1.2, -1.4])
+        param_fill.fill(net)
+        mods = dict(net.named_modules())
+        # the settings as data (the tests build their models from them), and the plane resolution they had before it was made small
+        out = {"settings": np.array(json.dumps(dict(vars(hp), batch_size=batch), sort_keys=True)), "resolution": np.array(own)}
+        seen = {}
+        hooks = [m.register_forward_hook(lambda mod, i, o, k=k: seen.__setitem__(k, o.detach()))
+                 for k, m in net.named_modules() if isinstance(m, torch.nn.ReLU)
+                 or k.rsplit(".", 1)[-1] in ("pos_deform", "scales_deform", "rotations_deform", "opacity_deform", "shs_deform", "static_mlp")]
+        live = {"pos_deform": ("xyz", not hp.no_dx), "scales_deform": ("scaling", not hp.no_ds),
+                "rotations_deform": ("rotation", not hp.no_dr), "opacity_deform": ("opacity", not hp.no_do),
+                "shs_deform": ("shs", not hp.no_dshs)}
+        for frame_num, delta_scale, t in G16_CASES:
+            ins = {k: v.clone().requires_grad_(True) for k, v in inputs.items()}
+            net.zero_grad()
+            seen.clear()
+            outs = net(ins["xyz"], ins["scaling"], ins["rotation"], ins["opacity"], ins["shs"], torch.full((n, 1), t), flow,
+                       torch.tensor(frame_num), delta_scale)
+            tag = f"f{frame_num}_d{delta_scale}"
+            for k, o in zip(G16_OUTPUTS, outs):
+                out[f"{k}_{tag}"] = o.detach().numpy().copy()
+            # ---- the fixture is not vacuous: every ReLU layer between 20 % and 80 % active, every live head's residual at least
+            # 1e-2 of the input it is added to (root mean squares over the fixture's points)
+            rms = lambda x: float(x.double().pow(2).mean().sqrt())
+            relus = {k: o for k, o in seen.items() if isinstance(mods[k], torch.nn.ReLU)}        # (a switched-off head never runs)
+            for k, o in relus.items():
+                frac = float((o > 0).float().mean())
+                assert 0.2 <= frac <= 0.8, (name, tag, k, frac)
+            assert len(relus) == max(hp.defor_depth - 1, 0) + 2 * (sum(on for _, on in live.values()) + bool(hp.static_mlp)), (name, sorted(relus))
+            for h, (inp, on) in live.items():
+                key = "deformation_net." + h
+                assert (key in seen) == on, (name, h, "ran" if key in seen else "did not run")
+                if on:
+                    # ... and not by its bias alone: what the head computes varies over the points by that much too
+                    r = seen[key].reshape(n, -1)
+                    assert rms(r) >= 1e-2 * rms(inputs[inp]), (name, tag, h, rms(r), rms(inputs[inp]))
+                    assert rms(r - r.mean(0)) >= 1e-2 * rms(inputs[inp]), (name, tag, h, "variation", rms(r - r.mean(0)), rms(inputs[inp]))
+            if hp.static_mlp:
+                m = seen["deformation_net.static_mlp"]
+                assert float(m.std()) >= 1e-2 and rms(m - 1.0) >= 1e-2, (name, "the mask is a constant", float(m.std()))
+            if (frame_num, delta_scale, t) != G16_CASES[1]:
+                continue
+            sum((o * w).sum() for o, w in zip(outs, ws)).backward()
+            for k in G16_INPUTS:
+                assert ins[k].grad is not None and float(ins[k].grad.abs().max()) > 0, (name, k)
+                out[f"d{k}_{tag}"] = ins[k].grad.numpy().copy()
+            for k, p in net.named_parameters():
+                assert p.grad is None or float(p.grad.abs().max()) > 0, (name, k)
+                out[f"grad_{tag}__{k}"] = np.zeros(0, np.float32) if p.grad is None else p.grad.numpy().copy()
+            groups = {}
+            for k, p in net.named_parameters():
+                if p.requires_grad:                                 # (the box, grid.aabb, is a frozen parameter)
+                    groups.setdefault(k.split(".")[0] if k.startswith("timenet") else k.split(".")[1], set()).add(p.grad is None)
+            assert all(len(v) == 1 for v in groups.values()), (name, groups)
+            dead = sorted(k for k, v in groups.items() if v == {True})
+            want_dead = sorted(["timenet"] + [h for h, (_, on) in live.items() if not on])
+            assert dead == want_dead, (name, dead, want_dead)
+        for h in hooks:
+            h.remove()
+        return out
+
+    for fname, cases in G16_FILES.items():
+        out = dict(shared, cases=np.array(cases))
+        for c in cases:
+            out.update({f"{c}__{k}": v for k, v in one(c).items()})
+        path = os.path.join(OUT, f"g16_{fname}.npz")
+        np.savez_compressed(path, **out)
+        size = os.path.getsize(path)
+        print(f"g16_{fname}.npz: {size} bytes")
+        assert size <= 795542, (fname, size)                       # no larger than the largest fixture before it (g1_hexplane.npz)
+    total = sum(os.path.getsize(os.path.join(OUT, f"g16_{f}.npz")) for f in G16_FILES)
+    assert total < 3_000_000, total
+
+
 if __name__ == "__main__":
     # python oracle/ref_harness.py            -> every fixture
     # python oracle/ref_harness.py g9 g3      -> only the named ones (g7 needs g1's field, so it pulls g1 in)
@@ -491,4 +653,5 @@ if __name__ == "__main__":
     if want("g9t"): g9_trajectories()
     if want("g11"): g11_checkpoint_formats()
     if want("g12"): g12_stage1_reader()
+    if want("g16"): g16_model_shapes()
     print("golden fixtures written to", OUT, sorted(os.listdir(OUT)))
