@@ -235,6 +235,7 @@ def _sig(lib):
     lib.mom_sceneflow_fit_scratch_bytes.restype = sz
     lib.mom_sceneflow_fit_scratch_bytes.argtypes = [i32, i32, i32]
     lib.mom_sceneflow_fit.argtypes = [i32, i32, i32, vp, C.POINTER(C.c_float), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.mom_flow_sample.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.mom_ssim_forward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.mom_ssim_forward_slab.argtypes = [i32, i32, i32, sz, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.mom_ssim_backward_slab.argtypes = [i32, i32, i32, sz, vp, vp, vp, vp, C.c_float, vp, vp, vp]
@@ -293,7 +294,7 @@ EXPORTS = [
     "mom_deform_forward_n", "mom_deform_forward_activated_n", "mom_deform_backward_n", "mom_deform_backward_split_n",
     "mom_deform_field16_supported", "mom_deform_field16_scratch_bytes", "mom_deform_field16_forward",
     "mom_densify_scratch_bytes", "mom_densify_plan", "mom_densify_apply",
-    "mom_sceneflow_fit_scratch_bytes", "mom_sceneflow_fit",
+    "mom_sceneflow_fit_scratch_bytes", "mom_sceneflow_fit", "mom_flow_sample",
 ]
 
 

@@ -4,20 +4,25 @@ The reference's MotionOptimization.optimize_motion (train_motion.py:65-207) proj
 view's estimated 2D flow at the projected points and runs SGD on one [3,P] tensor so that the flowed points' projections move by
 those 2D flows.  Its output, MOM/scene_flow.pth, is the prior every deformation field of this package adds to its positions.  Here
 the preparation (valid sets, unflowed pixels: float64 numpy, cast as the reference casts) stays on the host and the whole SGD
-loop -- every epoch, every view -- is one HIP launch (ops.sceneflow_fit, csrc/sceneflow_fit.hip).
+loop -- every epoch, every view -- is one HIP launch (ops.sceneflow_fit, csrc/sceneflow_fit.hip).  The sampling is the
+reference's scipy.interpolate.griddata, one call per view on the host (sampler="griddata", the default), or one HIP launch for all
+views (sampler="device": ops.flow_sample, csrc/flow_sample.hip) that needs the pixel grid's triangulation once per image size.
 
     prepare_views      valid sets and unflowed pixels of a list of world-to-camera poses  -> ViewSet
-    fit_scene_flow     the fit itself, targets given per view at that view's valid points
+    grid_diagonals     which diagonal griddata's triangulation of an H x W pixel grid puts into every cell (cached)
+    sample_flow_images the fit's records from the views' flow images, on the device
+    fit_scene_flow     the fit itself, targets given per view at that view's valid points or as device records
     optimize_motion    the reference's function: pose composition, griddata sampling, fit, our_flow
     refit_scene_flow   a stage-1 directory's MOM/train_data.pth -> MOM/scene_flow.pth
 
 The rest of stage 1 (depth, the multi-view renders, the 2D flow estimator, the video GAN) is not part of this package.
 
-    python -m iclr2025_3d-mom_amd.motion --input_dir DIR [--train_iteration N]
+    python -m iclr2025_3d-mom_amd.motion --input_dir DIR [--train_iteration N] [--sampler device]
 """
+import functools
 import os
 from dataclasses import dataclass
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 import torch
@@ -30,7 +35,8 @@ YZ_REVERSE = np.array([[1, 0, 0], [0, -1, 0], [0, 0, -1]], dtype=np.float64)    
 @dataclass
 class ViewSet:
     """What the fit needs of V views of P points.  R, T: float32 world-to-camera (train_motion.py:164-165 casts them);
-    valid[j]: the indices of view j's valid set, ascending (:173-177); pix0[j]: [2, n_j] float32, the unflowed pixels (:180,183)."""
+    valid[j]: the indices of view j's valid set, ascending (:173-177); pix0[j]: [2, n_j] float32, the unflowed pixels (:180,183);
+    pix64[j]: the same pixels before that cast, as the reference hands them to griddata (:115,120) -- prepare_views fills it."""
     P: int
     H: int
     W: int
@@ -38,6 +44,7 @@ class ViewSet:
     T: np.ndarray
     valid: List[np.ndarray]
     pix0: List[np.ndarray]
+    pix64: Optional[List[np.ndarray]] = None
 
     @property
     def V(self):
@@ -65,7 +72,7 @@ def prepare_views(points, K, w2c_list, H, W):
     if points.ndim != 2 or points.shape[0] != 3:
         raise ValueError(f"points must be [3, P], got {points.shape}")
     K = np.asarray(K)
-    Rs, Ts, valid, pix0 = [], [], [], []
+    Rs, Ts, valid, pix0, pix64 = [], [], [], [], []
     for j, pose in enumerate(w2c_list):
         R, T = _pose(pose)
         cam = R.dot(points) + T
@@ -78,10 +85,11 @@ def prepare_views(points, K, w2c_list, H, W):
         Rs.append(np.asarray(R, np.float32))
         Ts.append(np.asarray(T, np.float32).reshape(3))
         valid.append(idx)
-        pix0.append((pix[:2, idx] / pix[-1:, idx]).astype(np.float32))
+        pix64.append(pix[:2, idx] / pix[-1:, idx])
+        pix0.append(pix64[-1].astype(np.float32))
     if not valid:
         raise ValueError("no views")
-    return ViewSet(P=points.shape[1], H=int(H), W=int(W), R=np.stack(Rs), T=np.stack(Ts), valid=valid, pix0=pix0)
+    return ViewSet(P=points.shape[1], H=int(H), W=int(W), R=np.stack(Rs), T=np.stack(Ts), valid=valid, pix0=pix0, pix64=pix64)
 
 
 def learning_rates(epochs, lr=0.5, gamma=0.97):
@@ -101,13 +109,27 @@ def view_weights(views, divisor):
     return np.asarray([inv / np.float32(2 * len(v)) for v in views.valid], dtype=np.float32)
 
 
+def valid_words(views):
+    """valid [ceil(V/32),P] int32 bit words: bit j % 32 of word [j // 32, p] = point p is in view j's valid set."""
+    bits = np.zeros(((views.V + 31) // 32, views.P), np.uint32)
+    for j, idx in enumerate(views.valid):
+        bits[j // 32, idx] |= np.uint32(1 << (j % 32))
+    return bits.view(np.int32)
+
+
+def _upload(a, dev):
+    """An array or CPU tensor on `dev`.  To a GPU it goes through pinned memory and an asynchronous copy on the current stream, so
+    that preparing a fit only enqueues (a copy from pageable memory makes the host wait for the stream)."""
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" and not t.is_cuda else t.to(dev)
+
+
 def pack_views(views, gt):
     """records [V,P,4] float32 = {pix0, gt} and valid [ceil(V/32),P] int32 bit words, on the host."""
     V, P = views.V, views.P
     if len(gt) != V:
         raise ValueError(f"{len(gt)} targets for {V} views")
     rec = np.zeros((V, P, 4), np.float32)
-    bits = np.zeros(((V + 31) // 32, P), np.uint32)
     for j in range(V):
         g = gt[j].detach().cpu().numpy() if torch.is_tensor(gt[j]) else np.asarray(gt[j])
         idx = views.valid[j]
@@ -115,14 +137,15 @@ def pack_views(views, gt):
             raise ValueError(f"the target of view {j} must be [2, {len(idx)}] (one column per valid point), got {g.shape}")
         rec[j, idx, 0:2] = views.pix0[j].T
         rec[j, idx, 2:4] = g.T.astype(np.float32)
-        bits[j // 32, idx] |= np.uint32(1 << (j % 32))
-    return rec, bits.view(np.int32)
+    return rec, valid_words(views)
 
 
-def fit_scene_flow(points, K, views, gt, epochs=200, lr=0.5, gamma=0.97, divisor=None, device=None):
+def fit_scene_flow(points, K, views, gt, epochs=200, lr=0.5, gamma=0.97, divisor=None, device=None, records=None):
     """The fit (train_motion.py:125-207).  points [3,P]; K 3x3; views: a ViewSet of the same points; gt: per view a [2, n_j]
     array or tensor, the 2D flow at that view's valid points (the reference's GT_list); divisor: the reference's idx + 1 (:189),
     one more than the slot index of the last view that has a flow -- the number of views when none was skipped, the default.
+    records: in place of gt (then None), what sample_flow_images returned -- (records [V,P,4], valid words) already on the device:
+    nothing is packed or uploaded for them; the view weights still come from the host's valid counts.
     Returns (flow [3,P], loss [E], flow2d_last [V,P,2]) on the device: the scene flow, every epoch's loss, and the last epoch's
     2D flow of every point in every view (0 where the point is not in the view's valid set).  Everything is enqueued on the current
     stream; nothing is read back."""
@@ -132,15 +155,20 @@ def fit_scene_flow(points, K, views, gt, epochs=200, lr=0.5, gamma=0.97, divisor
         raise ValueError(f"points must be [3, {views.P}] like the views', got {pts.shape}")
     if epochs < 0:
         raise ValueError("epochs must not be negative")
-    rec, bits = pack_views(views, gt)
+    up = lambda a: _upload(a, dev)
+    if records is not None:
+        if gt is not None:
+            raise ValueError("give the targets as gt (per view, on the host) or as records (on the device), not both")
+        rec, bits = records
+    else:
+        rec, bits = (up(a) for a in pack_views(views, gt))
     w = view_weights(views, views.V if divisor is None else divisor)
     K_host = np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, dtype=np.float32)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     V, P = views.V, views.P
     flow = torch.zeros((3, P), dtype=torch.float32, device=dev)
     loss = torch.zeros(epochs, dtype=torch.float32, device=dev)
     flow2d = torch.zeros((V, P, 2), dtype=torch.float32, device=dev)
-    ops.sceneflow_fit(up(pts), K_host, up(views.R), up(views.T), up(w), up(rec), up(bits), up(learning_rates(epochs, lr, gamma)),
+    ops.sceneflow_fit(up(pts), K_host, up(views.R), up(views.T), up(w), rec, bits, up(learning_rates(epochs, lr, gamma)),
                       flow, loss, flow2d)
     return flow, loss, flow2d
 
@@ -165,14 +193,101 @@ def sample_flow_image(flow_image, pix0, H, W):
     return _griddata()(_pixel_grid(H, W), g, np.asarray(pix0).transpose(1, 0), method="linear", fill_value=0).T
 
 
-def _fit_slots(train_data, slots, K, H, W, train_iteration, device=None):
+@functools.lru_cache(maxsize=None)
+def grid_diagonals(H, W):
+    """bool [H-1, W-1], True where the anti-diagonal (x+1, y)-(x, y+1) splits cell (x, y) of griddata's triangulation of the H x W
+    pixel grid and False where the main diagonal (x, y)-(x+1, y+1) does: scipy.spatial.Delaunay over exactly the points griddata is
+    given, read simplex by simplex.  The choice is Qhull's and irregular, but it depends on (H, W) alone, so the result is kept per
+    (H, W) for the life of the process (read-only).  Raises RuntimeError unless the triangulation is two triangles per cell with
+    one diagonal in every cell -- a Qhull that answers differently must not pass silently."""
+    H, W = int(H), int(W)
+    if H < 2 or W < 2:
+        raise ValueError(f"a pixel grid needs at least one cell (H, W >= 2), got H {H}, W {W}")
+    try:
+        from scipy.spatial import Delaunay
+    except ImportError as e:
+        raise ImportError("grid_diagonals reads the cell diagonals out of scipy.spatial.Delaunay: scipy is needed for it; "
+                          "sample_flow_images also takes an explicit mask") from e
+    s = np.asarray(Delaunay(_pixel_grid(H, W)).simplices, dtype=np.int64)
+    cells = (H - 1) * (W - 1)
+    if s.shape != (2 * cells, 3):
+        raise RuntimeError(f"the triangulation of the {H} x {W} pixel grid has {s.shape[0]} triangles, not two per cell ({2 * cells})")
+    xs, ys = s % W, s // W
+    x0, y0 = xs.min(1), ys.min(1)
+    if (xs.max(1) - x0 != 1).any() or (ys.max(1) - y0 != 1).any():
+        raise RuntimeError(f"the triangulation of the {H} x {W} pixel grid has a triangle that is not half of one cell")
+    # corner k = dx + 2 dy of the cell; a triangle is the cell without one corner: without 0 or 3 it lies on the anti-diagonal
+    missing = 15 - (1 << ((xs - x0[:, None]) + 2 * (ys - y0[:, None]))).sum(1)
+    cell = y0 * (W - 1) + x0
+    count = np.bincount(cell, minlength=cells)
+    halves = np.bincount(cell, weights=missing, minlength=cells).astype(np.int64)
+    if not np.isin(missing, (1, 2, 4, 8)).all() or (count != 2).any() or not np.isin(halves, (1 + 8, 2 + 4)).all():
+        raise RuntimeError(f"the triangulation of the {H} x {W} pixel grid does not split every cell by exactly one diagonal")
+    mask = (halves == 1 + 8).reshape(H - 1, W - 1)
+    mask.setflags(write=False)
+    return mask
+
+
+def pack_diagonals(mask):
+    """The mask of grid_diagonals as ops.flow_sample's bit words: int32 [ceil(cells / 32)], bit c % 32 of word c // 32 for the
+    cell c = y (W-1) + x."""
+    b = np.packbits(np.asarray(mask, dtype=bool).reshape(-1), bitorder="little")
+    words = np.zeros((b.size + 3) // 4 * 4, np.uint8)
+    words[:b.size] = b
+    return words.view("<u4").astype(np.uint32).view(np.int32)
+
+
+def sample_flow_images(views, flow_images, diagonals=None, device=None):
+    """The fit's records on the device: (records [V,P,4] float32 = {pix0, gt}, valid [ceil(V/32),P] int32 bit words), gt being
+    view j's flow image sampled at its valid points as sample_flow_image does, to float64 rounding, for all views in one launch
+    (ops.flow_sample).  views: a ViewSet of prepare_views (it carries the float64 pixels); flow_images: per view a [1,2,H,W]
+    tensor or array, or one [V,2,H,W] tensor; they are read as float32, which the stage-1 flow images are.
+    diagonals: the bool [H-1, W-1] mask of the cells the anti-diagonal splits; None means grid_diagonals(H, W), which needs scipy.
+    A caller without scipy can pass a mask of its own (all False, say) and still run, knowing that in every cell whose diagonal is
+    not griddata's the result then leaves the reference by up to the cell's mixed second difference f00 - f10 - f01 + f11 (times
+    min(fx, fy, 1-fx, 1-fy) <= 1/2) -- on a noisy flow image that is the scale of the image itself.
+    Uploads the dense float64 pixels ([V,P,2], 16 bytes per pair) and the bit words; nothing is read back."""
+    dev = torch.device("cuda" if device is None else device)
+    V, P, H, W = views.V, views.P, views.H, views.W
+    if views.pix64 is None:
+        raise ValueError("the ViewSet carries no float64 pixels (pix64): build it with prepare_views")
+    if torch.is_tensor(flow_images) and flow_images.dim() == 4:
+        images = flow_images
+    else:
+        images = torch.cat([torch.as_tensor(f).reshape(1, 2, H, W) for f in flow_images])
+    if tuple(images.shape) != (V, 2, H, W):
+        raise ValueError(f"{V} views of {H} x {W} pixels need flow images [{V}, 2, {H}, {W}], got {tuple(images.shape)}")
+    mask = grid_diagonals(H, W) if diagonals is None else np.asarray(diagonals)
+    if mask.shape != (H - 1, W - 1):
+        raise ValueError(f"diagonals must be [{H - 1}, {W - 1}], one entry per cell, got {mask.shape}")
+    pix = np.zeros((V, P, 2), np.float64)
+    for j, idx in enumerate(views.valid):
+        pix[j, idx] = views.pix64[j].T
+    up = lambda a: _upload(a, dev)
+    bits = up(valid_words(views))
+    return ops.flow_sample(up(images.detach().to(torch.float32).contiguous()), up(pix), bits, up(pack_diagonals(mask))), bits
+
+
+SAMPLERS = ("griddata", "device")
+
+
+def _fit_slots(train_data, slots, K, H, W, train_iteration, device=None, sampler="griddata"):
     """slots: per view slot its (R, T) world-to-camera pose, or None for a slot without a flow (the reference's non_frame_idx).
-    Frame k of train_data carries the k-th present slot's T2C_flow (train_motion.py:81-85)."""
+    Frame k of train_data carries the k-th present slot's T2C_flow (train_motion.py:81-85).  sampler: "griddata" samples every
+    view's image on the host as the reference does, "device" samples all of them in one launch (sample_flow_images; the returned
+    gt is then None)."""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
     present = [i for i, s in enumerate(slots) if s is not None]
     if not present:
         raise ValueError("no view has a 2D flow to fit")
     points = train_data["pcd_points"]
     views = prepare_views(points, K, [slots[i] for i in present], H, W)
+    if sampler == "device":
+        images = [train_data["frames"][k]["T2C_flow"][0] for k in range(len(present))]
+        flow, loss, flow2d = fit_scene_flow(points, K, views, None, epochs=train_iteration, divisor=present[-1] + 1, device=device,
+                                            records=sample_flow_images(views, images, device=device))
+        return views, present, None, flow, loss, flow2d
     gt = []
     for k, _ in enumerate(present):
         # float64 pixels, as the reference hands them to griddata (:115,120)
@@ -184,11 +299,13 @@ def _fit_slots(train_data, slots, K, H, W, train_iteration, device=None):
     return views, present, gt, flow, loss, flow2d
 
 
-def optimize_motion(train_data, render_poses, internal_poses, K, H, W, non_frame_idx=(), train_iteration=200, device=None):
+def optimize_motion(train_data, render_poses, internal_poses, K, H, W, non_frame_idx=(), train_iteration=200, device=None,
+                    sampler="griddata"):
     """MotionOptimization.optimize_motion (train_motion.py:65-207) without its unused arguments: view slot idx = i * len(internal)
     + j has the pose internal[j] o render[i] (:91-97); slots in non_frame_idx have no flow; the k-th remaining slot takes
     train_data['frames'][k]['T2C_flow'][0].  After the fit each fitted slot's last-epoch 2D flow is resampled onto the pixel
-    grid and appended to train_data['frames'][idx]['our_flow'] -- indexed by the SLOT, as the reference does (:200).
+    grid and appended to train_data['frames'][idx]['our_flow'] -- indexed by the SLOT, as the reference does (:200); that
+    resampling triangulates each view's scattered pixels and stays scipy's griddata whatever `sampler` (_fit_slots) is.
     Returns (train_data, scene_flow [3,P] on the device)."""
     render_poses, internal_poses = np.asarray(render_poses), np.asarray(internal_poses)
     slots = []
@@ -201,7 +318,7 @@ def optimize_motion(train_data, render_poses, internal_poses, K, H, W, non_frame
             Rw2i, Tw2i = render_poses[i, :3, :3], render_poses[i, :3, 3:4]
             Ri2j, Ti2j = internal_poses[j, :3, :3], internal_poses[j, :3, 3:4]
             slots.append((np.matmul(Ri2j, Rw2i), np.matmul(Ri2j, Tw2i) + Ti2j))
-    views, present, _, flow, _, flow2d = _fit_slots(train_data, slots, K, H, W, train_iteration, device)
+    views, present, _, flow, _, flow2d = _fit_slots(train_data, slots, K, H, W, train_iteration, device, sampler)
     if train_iteration > 0:
         griddata, grid = _griddata(), _pixel_grid(H, W)
         flow2d = flow2d.cpu().numpy()
@@ -238,11 +355,14 @@ def stage1_intrinsics(H, W):
     return np.array([[FOCAL * (W / H), 0., W / 2], [0., FOCAL, H / 2], [0., 0., 1.]]).astype(np.float32)
 
 
-def refit_scene_flow(input_dir, train_iteration=200, device=None):
+def refit_scene_flow(input_dir, train_iteration=200, device=None, sampler="griddata"):
     """Fits the scene flow of a stage-1 directory again from what MOM/train_data.pth holds -- the point cloud, every frame's pose
     (its transform_matrix) and 2D flow (T2C_flow) -- and writes MOM/scene_flow.pth.  A frame with an empty T2C_flow list is a view
-    without a flow.  Returns the [3,P] flow (a CPU tensor, what is written)."""
+    without a flow.  sampler: "griddata" (one scipy call per view on the host) or "device" (_fit_slots).  Returns the [3,P] flow
+    (a CPU tensor, what is written)."""
     from .scene.dataset_readers import load_train_data
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
     mom = os.path.join(input_dir, "MOM")
     data = load_train_data(os.path.join(mom, "train_data.pth"))
     H, W = int(data["H"]), int(data["W"])
@@ -253,7 +373,7 @@ def refit_scene_flow(input_dir, train_iteration=200, device=None):
                          "fit the scene flow to")
     # _fit_slots reads the k-th present slot's flow from frame k: hand it the frames that have one, in order
     with_flow = dict(data, frames=[fr for fr, s in zip(frames, slots) if s is not None])
-    _, _, _, flow, _, _ = _fit_slots(with_flow, slots, stage1_intrinsics(H, W), H, W, train_iteration, device)
+    _, _, _, flow, _, _ = _fit_slots(with_flow, slots, stage1_intrinsics(H, W), H, W, train_iteration, device, sampler)
     flow = flow.cpu()
     torch.save(flow, os.path.join(mom, "scene_flow.pth"))
     return flow
@@ -264,8 +384,10 @@ def main(argv=None):
     ap = ArgumentParser(description="Fit MOM/scene_flow.pth of a stage-1 directory to the 2D flows in its MOM/train_data.pth")
     ap.add_argument("--input_dir", required=True)
     ap.add_argument("--train_iteration", type=int, default=200)
+    ap.add_argument("--sampler", choices=SAMPLERS, default="griddata", help="where the 2D flow images are sampled: scipy's griddata "
+                    "per view on the host, or one HIP launch for all views")
     a = ap.parse_args(argv)
-    flow = refit_scene_flow(a.input_dir, a.train_iteration)
+    flow = refit_scene_flow(a.input_dir, a.train_iteration, sampler=a.sampler)
     print(f"scene_flow.pth: {tuple(flow.shape)}, largest magnitude {float(flow.abs().max()):.6g}")
 
 

@@ -566,6 +566,47 @@ def sceneflow_fit(points, K, R, T, w, records, valid, lr, flow, loss=None, flow2
     return flow
 
 
+def flow_sample(flow_images, pix, valid, diagonals, records=None):
+    """The fit's records from the views' 2D flow images: what scipy.interpolate.griddata(pixel grid, image, pixels, "linear") gives
+    at every view's valid points (train_motion.py:117-121), all V views in one launch (csrc/flow_sample.hip; include/mom4d.h has the
+    arithmetic).  Enqueued on the current stream; nothing is read back.
+
+    flow_images [V,2,H,W] (the frames' layout, repacked on the device) or [V,H,W,2] (taken as it is); a shape that could be either,
+    [V,2,n,2], is read as [V,2,H,W]: float32; pix [V,P,2] float64, the unflowed pixels; valid [ceil(V/32),P] int32 bit words;
+    diagonals [ceil((H-1)(W-1)/32)] int32 bit words (motion.pack_diagonals): all contiguous on one device.
+    records [V,P,4] float32 is written in full -- zeros for invalid pairs -- and returned (allocated when not given)."""
+    if flow_images.dim() != 4 or 2 not in (flow_images.shape[1], flow_images.shape[3]) or flow_images.shape[0] < 1:
+        raise N.MomError(f"flow_sample: flow_images must be [V,2,H,W] or [V,H,W,2] with V >= 1, got {tuple(flow_images.shape)}")
+    if flow_images.dtype != torch.float32 or not flow_images.is_contiguous():
+        raise N.MomError(f"flow_sample: flow_images must be a contiguous torch.float32 tensor, got {flow_images.dtype}, "
+                         f"strides {tuple(flow_images.stride())}")
+    channel_first = flow_images.shape[1] == 2
+    V, H, W = (flow_images.shape[0], *flow_images.shape[2:]) if channel_first else flow_images.shape[:3]
+    if H < 2 or W < 2:
+        raise N.MomError(f"flow_sample: an image needs at least one cell (H, W >= 2), got H {H}, W {W}")
+    if pix.dim() != 3:
+        raise N.MomError(f"flow_sample: pix must be [V,P,2], got {tuple(pix.shape)}")
+    P, dev = pix.shape[1], flow_images.device
+    want = [("pix", pix, (V, P, 2), torch.float64), ("valid", valid, ((V + 31) // 32, P), torch.int32),
+            ("diagonals", diagonals, (((H - 1) * (W - 1) + 31) // 32,), torch.int32)]
+    if records is not None:
+        want.append(("records", records, (V, P, 4), torch.float32))
+    for name, t_, shape, dtype in want:
+        if tuple(t_.shape) != shape or t_.dtype != dtype or t_.device != dev or not t_.is_contiguous():
+            raise N.MomError(f"flow_sample: {name} must be a contiguous {dtype} {list(shape)} tensor on {dev}, "
+                             f"got {t_.dtype} {list(t_.shape)} on {t_.device}")
+    _need_cuda(flow_images, "flow_sample")
+    if records is None:
+        records = torch.empty((V, P, 4), dtype=torch.float32, device=dev)
+    elif records.requires_grad:
+        raise N.MomError("flow_sample: records is written in place and takes no gradient")
+    if channel_first:
+        flow_images = flow_images.permute(0, 2, 3, 1).contiguous()
+    N.check(N.lib().mom_flow_sample(P, V, H, W, N.ptr(flow_images), N.ptr(pix), N.ptr(valid), N.ptr(diagonals), N.ptr(records),
+                                    N.current_stream()), "mom_flow_sample")
+    return records
+
+
 # --------------------------------------------------------------------------- densification statistics
 def densify_stats(radii, viewspace_grad, max_radii2D, xyz_gradient_accum, denom, skip_flag=None, stream=None):
     """In place, for the Gaussians with radii > 0: running maximum radius, accumulated |dL/d mean2D| and its count

@@ -614,6 +614,29 @@ int mom_sceneflow_fit(int P, int V, int E, const float* points, const float* K, 
                       const float* records, const uint32_t* valid, const float* lr, float* flow, float* loss, float* flow2d_last,
                       void* scratch, size_t scratch_bytes, mom_stream_t stream);
 
+/* ---- the fit's records: every view's 2D flow image sampled at the view's projected points (train_motion.py:117-121) ----
+ * What scipy.interpolate.griddata(pixel grid, image, pixels, method="linear") computes there, for all V views in one launch
+ * (csrc/flow_sample.hip): linear interpolation inside one of the two triangles of the pixel's cell.  Which diagonal splits a cell is
+ * the triangulation's choice and depends on (H, W) alone; the caller passes it as one bit per cell.  Per valid (view, point),
+ * everything in float64 without contraction, each channel f of the image:
+ *     x0 = clamp((int)floor(u), 0, W-2); y0 = clamp((int)floor(v), 0, H-2); fx = u - x0; fy = v - y0
+ *     f00 = f(x0,y0)  f10 = f(x0+1,y0)  f01 = f(x0,y0+1)  f11 = f(x0+1,y0+1)                  (float -> double)
+ *     anti-diagonal cell: fx + fy <= 1 ? f00 + fx (f10 - f00) + fy (f01 - f00) : f11 + (1-fx) (f01 - f11) + (1-fy) (f10 - f11)
+ *     main-diagonal cell: fx >= fy     ? f00 + fx (f10 - f00) + fy (f11 - f10) : f00 + fx (f11 - f01) + fy (f01 - f00)
+ *     gt = (float)result
+ *   flow    [V,H,W,2] float32, channel-last (8-byte aligned)
+ *   pix     [V,P,2] float64 (16-byte aligned): the unflowed pixel (u, v) as the reference hands it to griddata (:115,120)
+ *   valid   [ceil(V/32),P] words, the layout mom_sceneflow_fit reads
+ *   diag    [ceil((H-1)(W-1)/32)] words: bit c % 32 of diag[c / 32], c = y (W-1) + x; set: the anti-diagonal (x+1,y)-(x,y+1) splits cell
+ *           (x, y); clear: the main diagonal (x,y)-(x+1,y+1)
+ *   records [V,P,4] float32 (16-byte aligned) = {(float)u, (float)v, gt.x, gt.y}, what mom_sceneflow_fit reads.  EVERY record is
+ *           written: an invalid pair's is four zeros, chosen by selection on its bit; its cell indices are clamped like any other's
+ *           (in float64, before the conversion), so whatever pix holds there -- NaN, 1e300 -- reaches no address.
+ * Stream-ordered, no allocation, no copy, no synchronisation.  P == 0 does nothing.  P < 0, V <= 0, V > 65535 (the view is a grid
+ * axis), H < 2, W < 2, a null pointer or a misaligned flow / pix / records: MOM_EINVAL before anything is launched. */
+int mom_flow_sample(int P, int V, int H, int W, const float* flow, const double* pix, const uint32_t* valid, const uint32_t* diag,
+                    float* records, mom_stream_t stream);
+
 /* ---- rendered image -> 8-bit interleaved RGB (render_4DGS.py:64 torchvision.utils.save_image: x * 255 + 0.5, clamp, truncate;
  * CHW -> HWC) in one pass, so that a frame can leave the device as the bytes a PNG encoder takes.  img [C,H,W] floats, out [H,W,C]
  * bytes; C <= 4. */
