@@ -347,7 +347,10 @@ def deform_mlp(feat, xyz, scaling, rotation, scene_flow, flow_coef, params):
 class L1LossFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, gt):
+        if img.numel() != gt.numel():      # (the kernel walks both with one index: a shorter gt would be read past its end)
+            raise N.MomError(f"l1_loss: image {tuple(img.shape)} and target {tuple(gt.shape)} differ in their number of elements")
         _need_cuda(img, "l1_loss")
+        _need_cuda(gt, "l1_loss")
         a = img.detach().contiguous().float()
         b = gt.detach().contiguous().float()
         dimg = torch.empty_like(a)
@@ -800,18 +803,23 @@ class PlaneRegFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, w_smooth, w_l1, *planes):
-        _need_cuda(planes[0], "plane_regulation")
         # the descriptor array holds pointers, shapes and weights only: rebuilt when one of them moves (the loop hands in the same
-        # twelve planes every iteration; twelve plane_storage() views and sixty field stores were 40 us of host time per call)
+        # twelve planes every iteration; twelve plane_storage() views and sixty field stores were 40 us of host time per call).
+        # The planes' layout and device are checked where it is built: a key that matches names planes that passed
         key = (tuple((p.data_ptr(), p.shape, p.stride()) for p in planes), tuple(w_smooth), tuple(w_l1))
         c = PlaneRegFunction._fwd_cache
         if c is None or c[0] != key:
             arr = (N.MomRegPlane * len(planes))()
             for i, p in enumerate(planes):
                 st = plane_storage(p)
+                if st is None or p.dtype != torch.float32:
+                    raise N.MomError(f"plane_regulation: plane {i} (shape {tuple(p.shape)}, strides {p.stride()}, {p.dtype}) is not a "
+                                     "channel-last float32 [1,C,H,W] tensor (ops.make_plane)")
                 arr[i].plane, arr[i].grad = st.data_ptr(), None
                 arr[i].H, arr[i].W = st.shape[0], _reg_row_units(st)
                 arr[i].w_smooth, arr[i].w_l1, arr[i].grad_scale = float(w_smooth[i]), float(w_l1[i]), 0.0
+            for p in planes:
+                _need_cuda(p, "plane_regulation")
             c = PlaneRegFunction._fwd_cache = (key, arr)
         arr = c[1]
         dev = planes[0].device
@@ -850,7 +858,8 @@ class PlaneRegFunction(torch.autograd.Function):
         direct = PlaneRegFunction.DIRECT_GRADS and direct_grads_ok(planes, ctx.needs_input_grad[2:])
         held = [p.grad if direct else None for p in planes]
         in_place = in_place_flags(held, planes)
-        key = (tuple(p.data_ptr() for p in planes), tuple(w_smooth), tuple(w_l1),
+        # (the shapes belong to the key: the descriptor holds H and W, and two planes of one size may follow each other at one address)
+        key = (tuple((p.data_ptr(), p.shape) for p in planes), tuple(w_smooth), tuple(w_l1),
                tuple(h.data_ptr() if ip else 0 for h, ip in zip(held, in_place)))
         c = PlaneRegFunction._cache
         busy = c is not None and (any(h is not None and h.data_ptr() == v.data_ptr() for h, v in zip(held, c[2]))
@@ -949,14 +958,15 @@ _IN_PLACE_MEMO = {}
 def in_place_flags(held, planes):
     """[h is a gradient tensor the kernels can add into in place: same layout as its plane, dense] for every plane.  The answer
     depends on the two tensors' storage, shape and strides only, and the loop hands in the SAME buffers iteration after iteration
-    (the gradient buffers are cached), so it is remembered per (gradient pointer, plane pointer): twelve pairs of pointer reads
-    instead of twelve shape-and-stride walks, twice per iteration of the API path."""
+    (the gradient buffers are cached), so it is remembered: twelve dictionary reads instead of twelve shape-and-stride walks, twice
+    per iteration of the API path.  The key holds BOTH tensors' shape and strides beside the pointers: two views of one buffer
+    share a pointer and differ in layout."""
     out = []
     for h, p in zip(held, planes):
         if h is None:
             out.append(False)
             continue
-        k = (h.data_ptr(), p.data_ptr(), h.shape, h.stride())
+        k = (h.data_ptr(), p.data_ptr(), h.shape, h.stride(), p.shape, p.stride())
         v = _IN_PLACE_MEMO.get(k)
         if v is None:
             if len(_IN_PLACE_MEMO) > 4096:
@@ -1069,7 +1079,7 @@ class FusedAdam(torch.optim.Optimizer):
                 "step_buf": buf, "arrs": arrs, "params": params, "offs": [0 if ranges is None else ranges[id(p)][0] for _, p in live],
                 "views": views, "rows": {cfg: np.asarray(r, dtype=np.int64) for cfg, r in rows.items()}, "groups": groups,
                 "gidx": np.asarray(gidx, dtype=np.int64), "offs4": np.asarray([0 if ranges is None else 4 * ranges[id(p)][0] for _, p in live], dtype=np.uint64),
-                "last_grad": [0] * len(params), "betas": [(b1, b2) for _, b1, b2, _, _ in entries]}
+                "last_grad": [(0, None)] * len(params), "betas": [(b1, b2) for _, b1, b2, _, _ in entries]}
 
     def _plan_key(self, live):
         return tuple((p.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(),
@@ -1099,11 +1109,14 @@ class FusedAdam(torch.optim.Optimizer):
         last, ptrs = plan["last_grad"], []
         for j, p in enumerate(plan["params"]):
             g = p.grad
-            gp = g.data_ptr()
-            if gp != last[j]:           # (the same buffer as last step -- the gradient buffers are cached -- was checked then)
-                if g.stride() != p.stride() and not _same_layout(g, p):
+            gp, gs = g.data_ptr(), g.stride()
+            seen = last[j]
+            # (the same buffer WITH the same strides as last step -- the gradient buffers are cached -- was checked then; the pointer
+            # alone says nothing: a contiguous view of the buffer a channel-last gradient lived in has its address)
+            if gp != seen[0] or gs != seen[1]:
+                if gs != p.stride() and not _same_layout(g, p):
                     raise N.MomError("FusedAdam: param/grad must be dense with identical strides")
-                last[j] = gp
+                last[j] = (gp, gs)
             ptrs.append(gp)
         plan["step_buf"] += 1
         # the step counters are host tensors the state surgery and rewind() may have touched: read them all in one go, and form

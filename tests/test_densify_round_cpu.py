@@ -255,7 +255,7 @@ def test_densify_keeps_the_op_by_op_round_for_a_threshold_of_zero(monkeypatch):
     with cpu_backend.installed():
         gm = g8_model()
         monkeypatch.setattr(GaussianModel, "FUSED_DENSIFY", True)
-        monkeypatch.setattr(ops, "BACKEND", Backend)
+        ops.set_backend(Backend)          # (installed() puts the caller's backend back; monkeypatch's undo, after it, would leave the CPU one)
         gm.densify_and_clone, gm.densify_and_split = _Spy(), _Spy()
         gm.densify(0.0, 0.005, 5.0, None, 5, 5)
         assert fused.calls == 0 and gm.densify_and_clone.calls == 1 and gm.densify_and_split.calls == 1
