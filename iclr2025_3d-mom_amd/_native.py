@@ -243,6 +243,13 @@ def _sig(lib):
     lib.mom_activations_forward.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp]
     lib.mom_activations_backward.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mom_image_to_rgb8.argtypes = [i32, i32, i32, vp, vp, vp]
+    lib.mom_png_bound.restype = sz
+    lib.mom_png_bound.argtypes = [i32, i32, i32]
+    lib.mom_png_scratch_bytes.restype = sz
+    lib.mom_png_scratch_bytes.argtypes = [i32, i32, i32]
+    lib.mom_png_encode.argtypes = [i32, i32, i32, vp, vp, sz, vp, vp, vp]
+    lib.mom_png_encode_host.argtypes = [i32, i32, i32, vp, vp, sz, vp]
+    lib.mom_png_tables.argtypes = [i32, vp, vp, vp, i32, vp]
     lib.mom_profile_enable.argtypes = [i32, i32]
     lib.mom_profile_read.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_longlong), i32]
     lib.mom_profile_name.restype = C.c_char_p
@@ -295,6 +302,7 @@ EXPORTS = [
     "mom_deform_field16_supported", "mom_deform_field16_scratch_bytes", "mom_deform_field16_forward",
     "mom_densify_scratch_bytes", "mom_densify_plan", "mom_densify_apply",
     "mom_sceneflow_fit_scratch_bytes", "mom_sceneflow_fit", "mom_flow_sample",
+    "mom_png_bound", "mom_png_scratch_bytes", "mom_png_encode", "mom_png_encode_host", "mom_png_tables",
 ]
 
 

@@ -610,6 +610,43 @@ def flow_sample(flow_images, pix, valid, diagonals, records=None):
     return records
 
 
+# --------------------------------------------------------------------------- PNG: the IDAT's zlib stream on the device
+def png_bound(C_, H, W):
+    """Bytes that always hold the stream of an [H,W,C_] image (mom_png_bound; 0: unsupported shape)."""
+    return int(N.lib().mom_png_bound(C_, H, W))
+
+
+def png_scratch(C_, H, W, device):
+    """The uint8 device scratch png_encode needs for an [H,W,C_] image; reusable by later calls on the same stream."""
+    if torch.device(device).type != "cuda":
+        raise N.MomError(f"png_scratch: libmom4d has no CPU path (got device {device})")
+    n = int(N.lib().mom_png_scratch_bytes(C_, H, W))
+    if n == 0:
+        raise N.MomError(f"png_scratch: unsupported image shape C {C_}, H {H}, W {W}")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def png_encode(rgb8, out, out_size, scratch):
+    """rgb8 [H,W,C] uint8 (what mom_image_to_rgb8 writes; C 1, 3 or 4) -> out [>= png_bound] uint8: the complete zlib stream of the
+    image's PNG scanlines, its length in out_size [1] int32 (csrc/png_encode.hip).  utils.image_io.png_from_zlib_stream frames
+    out[:out_size] as a file.  Enqueued on the current stream; nothing is read back, bytes of out behind the stream are untouched."""
+    _need_cuda(rgb8, "png_encode")
+    if rgb8.dim() != 3 or rgb8.dtype != torch.uint8 or not rgb8.is_contiguous():
+        raise N.MomError(f"png_encode: rgb8 must be a contiguous uint8 [H,W,C] tensor, got {rgb8.dtype} {list(rgb8.shape)}")
+    H, W, C_ = rgb8.shape
+    bound = png_bound(C_, H, W)
+    if bound == 0:
+        raise N.MomError(f"png_encode: unsupported image shape C {C_}, H {H}, W {W}")
+    for name, t_, dtype, n in (("out", out, torch.uint8, bound), ("out_size", out_size, torch.int32, 1),
+                               ("scratch", scratch, torch.uint8, N.lib().mom_png_scratch_bytes(C_, H, W))):
+        if t_.dtype != dtype or t_.device != rgb8.device or not t_.is_contiguous() or t_.numel() < n:
+            raise N.MomError(f"png_encode: {name} must be a contiguous {dtype} tensor of at least {n} elements on {rgb8.device}, "
+                             f"got {t_.dtype} {list(t_.shape)} on {t_.device}")
+    N.check(N.lib().mom_png_encode(C_, H, W, rgb8.data_ptr(), out.data_ptr(), out.numel(), out_size.data_ptr(), scratch.data_ptr(),
+                                   N.current_stream()), "mom_png_encode")
+    return out
+
+
 # --------------------------------------------------------------------------- densification statistics
 def densify_stats(radii, viewspace_grad, max_radii2D, xyz_gradient_accum, denom, skip_flag=None, stream=None):
     """In place, for the Gaussians with radii > 0: running maximum radius, accumulated |dL/d mean2D| and its count

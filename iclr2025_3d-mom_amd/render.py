@@ -5,7 +5,9 @@ like torchvision.utils.save_image -- and, when imageio is installed, <model_path
 32 pixels.  How it gets there differs: the reference encodes each PNG inside the render loop, on the thread that also launches
 the kernels, so its printed FPS is the PNG encoder's (render_4DGS.py:60-71).  Here the loop only enqueues GPU work -- render,
 one quantisation kernel (mom_image_to_rgb8), an async copy into a ring of pinned host buffers -- and a pool of threads encodes
-finished frames behind it (PIL releases the GIL inside zlib).  `scripted=True` keeps the reference's blocking order for
+finished frames behind it (PIL releases the GIL inside zlib).  With MOM_PNG_ENCODER=device (or AsyncPNGWriter(encoder="device"))
+the frame is deflated on the GPU as well (mom_png_encode, csrc/png_encode.hip): what crosses to the host is a finished zlib
+stream, and the threads only frame it in PNG chunks and write it.  `scripted=True` keeps the reference's blocking order for
 comparison.  Frames whose binning buffer overflowed in async mode are rendered again at the end (FusedRender.overflowed)."""
 import contextlib
 import os
@@ -19,7 +21,7 @@ import torch
 from . import _native as N
 from . import gaussian_renderer as GR
 from .gaussian_renderer import render
-from .utils.image_io import save_image, save_uint8
+from .utils.image_io import save_image, save_uint8, save_zlib_stream
 
 
 # zlib level of the asynchronous writer's PNGs.  PNG is lossless at every level: the decoded pixels are the same bytes, only the
@@ -27,14 +29,38 @@ from .utils.image_io import save_image, save_uint8
 # render loop waits for (a frame takes 0.26 ms to render and ~35 ms of one host core to compress at level 6, torchvision's / PIL's
 # default, which the blocking order `scripted=True` keeps).
 PNG_COMPRESS_LEVEL = int(os.environ.get("MOM_PNG_LEVEL", "1"))
+PNG_ENCODERS = ("host", "device")      # MOM_PNG_ENCODER / AsyncPNGWriter(encoder=): who deflates the asynchronous writer's frames
+
+
+def png_encoder(encoder=None):
+    """"host" or "device": the argument, or MOM_PNG_ENCODER when it is None (unset or empty: "host"); anything else is a ValueError."""
+    if encoder is None:
+        encoder = os.environ.get("MOM_PNG_ENCODER") or "host"
+    if encoder not in PNG_ENCODERS:
+        raise ValueError(f"the PNG encoder must be one of {PNG_ENCODERS}, got {encoder!r}")
+    return encoder
 
 
 class AsyncPNGWriter:
     """submit(image [3,H,W] on the GPU, path): quantise on the device, copy to a pinned slot behind the frame's kernels, encode on
-    a worker thread.  At most `slots` frames are in flight; submit() blocks only when all slots are busy."""
+    a worker thread.  At most `slots` frames are in flight; submit() blocks only when all slots are busy.
 
-    def __init__(self, H, W, C=3, slots=48, workers=None, compress_level=None):
+    encoder: "host" (the default; None reads MOM_PNG_ENCODER) -- the raw bytes cross to the host and a worker deflates them with
+    zlib at `compress_level`, filter type 0; "device" -- mom_png_encode makes the IDAT's zlib stream behind the quantisation kernel
+    (row filters, constant Huffman tables, run-length matches), the slot's pinned buffer receives the stream and its length in one
+    copy, and the worker only adds the chunk framing and the CRC.  Both files decode to the same bytes.  A frame the device encoder
+    does not take (a channel count other than 1, 3, 4; a tensor that is not on the GPU) goes the host way."""
+
+    def __init__(self, H, W, C=3, slots=48, workers=None, compress_level=None, encoder=None):
         self.H, self.W, self.C = H, W, C
+        self.encoder = encoder = png_encoder(encoder)
+        self.zcap = 0                       # device encoder: the stream's capacity, a multiple of 16; its length word follows
+        if encoder == "device":
+            bound = int(N.lib().mom_png_bound(C, H, W))
+            if bound:
+                self.zcap = (bound + 15) & ~15
+                self.zhost = [torch.empty(self.zcap + 4, dtype=torch.uint8).pin_memory() for _ in range(slots)]
+                self.zdev = [None] * slots      # (stream and length word, scratch) per slot
         self.level = PNG_COMPRESS_LEVEL if compress_level is None else int(compress_level)
         self.host = [torch.empty((H, W, C), dtype=torch.uint8).pin_memory() for _ in range(slots)]
         self.dev = [None] * slots
@@ -52,10 +78,34 @@ class AsyncPNGWriter:
         img = image if (image.is_contiguous() and image.dtype == torch.float32) else image.contiguous().float()
         N.check(N.lib().mom_image_to_rgb8(self.C, self.H, self.W, img.data_ptr(), self.dev[slot].data_ptr(), N.current_stream()),
                 "mom_image_to_rgb8")
+        if self.zcap and image.is_cuda:
+            if self.zdev[slot] is None or self.zdev[slot][0].device != image.device:
+                self.zdev[slot] = (torch.empty(self.zcap + 4, dtype=torch.uint8, device=image.device),
+                                   torch.empty(N.lib().mom_png_scratch_bytes(self.C, self.H, self.W), dtype=torch.uint8,
+                                               device=image.device))
+            z, scratch = self.zdev[slot]
+            N.check(N.lib().mom_png_encode(self.C, self.H, self.W, self.dev[slot].data_ptr(), z.data_ptr(), self.zcap,
+                                           z.data_ptr() + self.zcap, scratch.data_ptr(), N.current_stream()), "mom_png_encode")
+            self.zhost[slot].copy_(z, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self.futures.append(self.pool.submit(self._frame, slot, ev, path))
+            return
         self.host[slot].copy_(self.dev[slot], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         self.futures.append(self.pool.submit(self._encode, slot, ev, path))
+
+    def _frame(self, slot, ev, path):
+        try:
+            ev.synchronize()
+            z = self.zhost[slot].numpy()
+            size = int(z[self.zcap:].view(np.uint32)[0])
+            if not 8 <= size <= self.zcap:
+                raise N.MomError(f"mom_png_encode reported a stream of {size} bytes for {path} (capacity {self.zcap})")
+            save_zlib_stream(memoryview(z)[:size], path, self.H, self.W, self.C)
+        finally:
+            self.free.put(slot)
 
     def _encode(self, slot, ev, path):
         try:

@@ -642,6 +642,33 @@ int mom_flow_sample(int P, int V, int H, int W, const float* flow, const double*
  * bytes; C <= 4. */
 int mom_image_to_rgb8(int C, int H, int W, const float* img, uint8_t* out, mom_stream_t stream);
 
+/* ---- those bytes -> the zlib stream of a PNG's IDAT, on the device (csrc/png_encode.hip, csrc/png_dev.h), so that the host only
+ * frames it in chunks and writes it (render.AsyncPNGWriter(encoder="device"); the reference encodes on the host inside its timed
+ * loop, render_4DGS.py:60-71).  Lossless: the stream inflates to the PNG scanlines -- a filter byte (1 Sub, 2 Up or 4 Paeth, the one
+ * with the smallest sum of absolute signed residuals) and the filtered row -- of exactly the bytes given.
+ *   Stream: 78 01; per segment of 4 rows one deflate block (BFINAL = 0), the smaller of a Huffman-coded block -- deflate's fixed
+ *   code or one of a few constant dynamic-block tables (the cheapest for the segment), literals and run-length matches at distance 1
+ *   and C, lengths 3..258 -- closed by an empty stored block so that it ends on a byte, and ceil(n / 65535) stored blocks; a final
+ *   empty fixed block 03 00; the Adler-32 of the scanlines, big-endian.
+ *   the bound        the capacity that always suffices: 2 + every segment as stored blocks + 2 + 4.  0 for an unsupported shape:
+ *                    C not 1, 3 or 4, H < 1, W < 1, or a bound of 2^31 and above
+ *   the scratch size bytes of device scratch for mom_png_encode (0 for an unsupported shape)
+ *   the encoder      rgb8 [H,W,C], out [capacity], out_size [1], scratch: device pointers.  Four launches on `stream`; no allocation, no
+ *                    copy, no synchronisation.  out[*out_size ..] is not written.
+ *   the host form    the same stream, byte for byte, computed on the host from host pointers: a test seam (the device coder's
+ *                    per-chunk code is host code too), not a fallback -- nothing in the package calls it in place of the kernels
+ *   the tables       index -1: returns the number of tables.  Otherwise fills table `index`: litlen [288] and dist [32] code lengths
+ *                    (0 = no code), header = the block header the encoder emits (BFINAL = 0, BTYPE, a dynamic block's code lengths),
+ *                    least-significant bit first, *header_bits its length; returns the number of tables
+ * An unsupported shape, a null pointer, a capacity below the bound, a table index out of range or a header_capacity too small:
+ * MOM_EINVAL before anything is launched. */
+size_t mom_png_bound(int C, int H, int W);
+size_t mom_png_scratch_bytes(int C, int H, int W);
+int mom_png_encode(int C, int H, int W, const uint8_t* rgb8, uint8_t* out, size_t capacity, uint32_t* out_size, void* scratch,
+                   mom_stream_t stream);
+int mom_png_encode_host(int C, int H, int W, const uint8_t* rgb8, uint8_t* out, size_t capacity, uint32_t* out_size);
+int mom_png_tables(int index, uint8_t* litlen, uint8_t* dist, uint8_t* header, int header_capacity, int* header_bits);
+
 const char* mom_version(void);
 
 /* Per-kernel HIP-event timing (bench.py's live roofline figure).  Slots: see mom_profile_name(0..15).
