@@ -236,6 +236,12 @@ def _sig(lib):
     lib.mom_sceneflow_fit_scratch_bytes.argtypes = [i32, i32, i32]
     lib.mom_sceneflow_fit.argtypes = [i32, i32, i32, vp, C.POINTER(C.c_float), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.mom_flow_sample.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.mom_tri_resample_scratch_bytes.restype = sz
+    lib.mom_tri_resample_scratch_bytes.argtypes = [i32, i32, i32]
+    lib.mom_tri_resample.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_double, vp, vp, sz, vp]
+    lib.mom_pcd_compose_scratch_bytes.restype = sz
+    lib.mom_pcd_compose_scratch_bytes.argtypes = [i32, i32, i32]
+    lib.mom_pcd_compose.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.mom_ssim_forward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.mom_ssim_forward_slab.argtypes = [i32, i32, i32, sz, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.mom_ssim_backward_slab.argtypes = [i32, i32, i32, sz, vp, vp, vp, vp, C.c_float, vp, vp, vp]
@@ -266,6 +272,10 @@ SELECT_MAX_TENSORS = 32  # MOM_SELECT_MAX_TENSORS
 
 class MomRowSelect(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_uint)]
+
+
+TRI_LANE_BOX = 64        # MOM_TRI_LANE_BOX: the largest bounding box, in pixels, a lane of mom_tri_resample's cover pass walks itself
+TRI_BOX_GROW = 2.0 ** -20   # MOM_TRI_BOX_GROW
 
 
 DENSIFY_MAX_TENSORS = 32            # MOM_DENSIFY_MAX_TENSORS
@@ -303,6 +313,7 @@ EXPORTS = [
     "mom_densify_scratch_bytes", "mom_densify_plan", "mom_densify_apply",
     "mom_sceneflow_fit_scratch_bytes", "mom_sceneflow_fit", "mom_flow_sample",
     "mom_png_bound", "mom_png_scratch_bytes", "mom_png_encode", "mom_png_encode_host", "mom_png_tables",
+    "mom_tri_resample_scratch_bytes", "mom_tri_resample", "mom_pcd_compose_scratch_bytes", "mom_pcd_compose",
 ]
 
 

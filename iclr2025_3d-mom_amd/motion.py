@@ -8,19 +8,30 @@ loop -- every epoch, every view -- is one HIP launch (ops.sceneflow_fit, csrc/sc
 reference's scipy.interpolate.griddata, one call per view on the host (sampler="griddata", the default), or one HIP launch for all
 views (sampler="device": ops.flow_sample, csrc/flow_sample.hip) that needs the pixel grid's triangulation once per image size.
 
+The opposite direction -- values given at a view's projected points, wanted at every pixel centre -- is what the reference's
+render_PCD (train_motion.py:211-366: the multi-view renders of the point cloud stage 2 trains on) and the our_flow resampling at
+the end of optimize_motion (:196-200) do, again with one griddata per use, each triangulating the same scattered points anew.
+Here a view is triangulated once, on host threads (triangulate_views: scipy.spatial.Delaunay, Qhull's own choice where the
+triangulation is not unique), the triangulation is kept on the ViewSet for every use, and point location, interpolation, the
+border and mask morphology and the 8-bit cast run on the device (ops.tri_resample, ops.pcd_compose, csrc/tri_resample.hip).
+
     prepare_views      valid sets and unflowed pixels of a list of world-to-camera poses  -> ViewSet
     grid_diagonals     which diagonal griddata's triangulation of an H x W pixel grid puts into every cell (cached)
     sample_flow_images the fit's records from the views' flow images, on the device
     fit_scene_flow     the fit itself, targets given per view at that view's valid points or as device records
     optimize_motion    the reference's function: pose composition, griddata sampling, fit, our_flow
+    triangulate_views  one Delaunay triangulation per view of a ViewSet, in a thread pool, cached on the ViewSet
+    resample_to_grid   per-view values at the views' points -> [V,H,W,C] on the device
+    render_pcd         the reference's render_PCD: the multi-view images and masks of the point cloud
     refit_scene_flow   a stage-1 directory's MOM/train_data.pth -> MOM/scene_flow.pth
 
-The rest of stage 1 (depth, the multi-view renders, the 2D flow estimator, the video GAN) is not part of this package.
+The rest of stage 1 (the depth network, the pose generators, the 2D flow estimator, the video GAN) is not part of this package.
 
-    python -m iclr2025_3d-mom_amd.motion --input_dir DIR [--train_iteration N] [--sampler device]
+    python -m iclr2025_3d-mom_amd.motion --input_dir DIR [--train_iteration N] [--sampler device] [--resampler device]
 """
 import functools
 import os
+from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -36,7 +47,9 @@ YZ_REVERSE = np.array([[1, 0, 0], [0, -1, 0], [0, 0, -1]], dtype=np.float64)    
 class ViewSet:
     """What the fit needs of V views of P points.  R, T: float32 world-to-camera (train_motion.py:164-165 casts them);
     valid[j]: the indices of view j's valid set, ascending (:173-177); pix0[j]: [2, n_j] float32, the unflowed pixels (:180,183);
-    pix64[j]: the same pixels before that cast, as the reference hands them to griddata (:115,120) -- prepare_views fills it."""
+    pix64[j]: the same pixels before that cast, as the reference hands them to griddata (:115,120) -- prepare_views fills it.
+    simplices[j]: int32 [T_j, 3], view j's Delaunay triangulation (triangulate_views fills and keeps it); packed: what
+    upload_views put on a device, kept for the next use on that device."""
     P: int
     H: int
     W: int
@@ -45,6 +58,8 @@ class ViewSet:
     valid: List[np.ndarray]
     pix0: List[np.ndarray]
     pix64: Optional[List[np.ndarray]] = None
+    simplices: Optional[List[np.ndarray]] = None
+    packed: Optional[dict] = None
 
     @property
     def V(self):
@@ -63,6 +78,21 @@ def _pose(p):
     return R, T.reshape(3, 1)
 
 
+def _valid_pixels(points, K, R, T, H, W):
+    """(valid indices, float64 pixels [2, n]) of one view, by the reference's expressions (train_motion.py:105-115,285-297)."""
+    pix = np.matmul(K, R.dot(points) + T)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        idx = np.where(np.logical_and.reduce((pix[2] > 0, pix[0] / pix[2] >= 0, pix[0] / pix[2] <= W - 1,
+                                              pix[1] / pix[2] >= 0, pix[1] / pix[2] <= H - 1)))[0]
+    return idx, pix[:2, idx] / pix[-1:, idx]
+
+
+def _view_set(P, H, W, poses, valid, pix64):
+    return ViewSet(P=P, H=int(H), W=int(W), R=np.stack([np.asarray(R, np.float32) for R, _ in poses]),
+                   T=np.stack([np.asarray(T, np.float32).reshape(3) for _, T in poses]), valid=valid,
+                   pix0=[p.astype(np.float32) for p in pix64], pix64=pix64)
+
+
 def prepare_views(points, K, w2c_list, H, W):
     """Valid sets and unflowed pixels exactly as train_motion.py:161-183 forms them: numpy in the dtypes given (the reference has
     float32 points and K and float64 poses, so float64 throughout), `z > 0, 0 <= u <= W-1, 0 <= v <= H-1`, pixels cast to
@@ -72,24 +102,18 @@ def prepare_views(points, K, w2c_list, H, W):
     if points.ndim != 2 or points.shape[0] != 3:
         raise ValueError(f"points must be [3, P], got {points.shape}")
     K = np.asarray(K)
-    Rs, Ts, valid, pix0, pix64 = [], [], [], [], []
+    poses, valid, pix64 = [], [], []
     for j, pose in enumerate(w2c_list):
         R, T = _pose(pose)
-        cam = R.dot(points) + T
-        pix = np.matmul(K, cam)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            idx = np.where(np.logical_and.reduce((pix[2] > 0, pix[0] / pix[2] >= 0, pix[0] / pix[2] <= W - 1,
-                                                  pix[1] / pix[2] >= 0, pix[1] / pix[2] <= H - 1)))[0]
+        idx, pix = _valid_pixels(points, K, R, T, H, W)
         if len(idx) == 0:
             raise ValueError(f"view {j} sees none of the {points.shape[1]} points")
-        Rs.append(np.asarray(R, np.float32))
-        Ts.append(np.asarray(T, np.float32).reshape(3))
+        poses.append((R, T))
         valid.append(idx)
-        pix64.append(pix[:2, idx] / pix[-1:, idx])
-        pix0.append(pix64[-1].astype(np.float32))
+        pix64.append(pix)
     if not valid:
         raise ValueError("no views")
-    return ViewSet(P=points.shape[1], H=int(H), W=int(W), R=np.stack(Rs), T=np.stack(Ts), valid=valid, pix0=pix0, pix64=pix64)
+    return _view_set(points.shape[1], H, W, poses, valid, pix64)
 
 
 def learning_rates(epochs, lr=0.5, gamma=0.97):
@@ -269,6 +293,215 @@ def sample_flow_images(views, flow_images, diagonals=None, device=None):
 
 
 SAMPLERS = ("griddata", "device")
+RESAMPLERS = ("griddata", "device")
+MAX_WORKERS = 16
+
+
+def triangulate_views(views, workers=8):
+    """Per view of a ViewSet the simplices of scipy.spatial.Delaunay over pix64[j].T -- exactly the points, and the Qhull options,
+    griddata triangulates (train_motion.py:198,304,319) -- as int32 [T_j, 3], in a pool of `workers` threads (Qhull releases the
+    GIL; at most 16, never sized by the machine).  The list is kept on the ViewSet: every later consumer of the same views
+    (render_pcd, optimize_motion's our_flow, resample_to_grid) finds it there.  A view with fewer than 3 valid points, or one
+    Qhull rejects (collinear points, say), raises ValueError naming the view."""
+    if views.simplices is not None:
+        return views.simplices
+    if views.pix64 is None:
+        raise ValueError("the ViewSet carries no float64 pixels (pix64): build it with prepare_views")
+    try:
+        from scipy.spatial import Delaunay, QhullError
+    except ImportError as e:
+        raise ImportError("triangulate_views triangulates each view's pixels with scipy.spatial.Delaunay: scipy is needed for it; "
+                          "a ViewSet whose `simplices` are already filled in needs none") from e
+
+    def one(j):
+        pts = np.ascontiguousarray(views.pix64[j].T, dtype=np.float64)
+        if pts.shape[0] < 3:
+            raise ValueError(f"view {j} has {pts.shape[0]} valid points: a triangulation needs at least 3")
+        try:
+            return np.ascontiguousarray(Delaunay(pts).simplices, dtype=np.int32)
+        except QhullError as e:
+            raise ValueError(f"view {j}: Qhull cannot triangulate its {pts.shape[0]} points ({str(e).strip().splitlines()[0]})") from e
+
+    workers = max(1, min(int(workers), MAX_WORKERS, views.V))
+    if workers == 1:
+        tris = [one(j) for j in range(views.V)]
+    else:
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            tris = list(pool.map(one, range(views.V)))
+    views.simplices = tris
+    return tris
+
+
+def _offsets(counts):
+    off = np.zeros(len(counts) + 1, np.int64)
+    np.cumsum(counts, out=off[1:])
+    if off[-1] > np.iinfo(np.int32).max:
+        raise ValueError(f"{off[-1]} rows in all: more than an int32 offset holds")
+    return off.astype(np.int32)
+
+
+def upload_views(views, device=None, workers=8):
+    """What ops.tri_resample and ops.pcd_compose read of a ViewSet, on the device: pts [N,2] float64 (the views' pixels
+    concatenated), pt_off, tris [T,3] int32, tri_off, and `gather` [N] int64 = j P + valid[j], the rows of a dense [V,P,C] tensor in
+    that order.  Triangulates first when the ViewSet has no simplices yet; kept on the ViewSet per device."""
+    dev = torch.device("cuda" if device is None else device)
+    if views.packed is not None and views.packed["device"] == dev:
+        return views.packed
+    tris = triangulate_views(views, workers)
+    up = lambda a: _upload(a, dev)
+    views.packed = dict(device=dev,
+                        pts=up(np.concatenate([p.T for p in views.pix64]).astype(np.float64)),
+                        pt_off=up(_offsets([len(v) for v in views.valid])),
+                        tris=up(np.concatenate(tris).astype(np.int32).reshape(-1, 3)),
+                        tri_off=up(_offsets([len(t) for t in tris])),
+                        gather=up(np.concatenate([j * views.P + np.asarray(v, np.int64) for j, v in enumerate(views.valid)])))
+    return views.packed
+
+
+def upload_values(views, values, device=None):
+    """Per-view [n_j, C] arrays or tensors, one row per valid point -> one [N, C] float32 tensor on the device, in the views' order."""
+    dev = torch.device("cuda" if device is None else device)
+    if len(values) != views.V:
+        raise ValueError(f"{len(values)} value arrays for {views.V} views")
+    rows = [np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=np.float32) for v in values]
+    for j, r in enumerate(rows):
+        if r.ndim != 2 or r.shape[0] != len(views.valid[j]) or r.shape[1] != rows[0].shape[1]:
+            raise ValueError(f"the values of view {j} must be [{len(views.valid[j])}, C] (one row per valid point), got {r.shape}")
+    return _upload(np.concatenate(rows), dev)
+
+
+def resample_to_grid(views, values, fill=0.0, device=None, workers=8):
+    """Values given at every view's valid points, linearly interpolated at every pixel centre: what
+    griddata(pix64[j].T, values[j], pixel grid, method="linear", fill_value=fill) gives per view, for all views in one call of
+    ops.tri_resample.  values: per view an [n_j, C] array or tensor (read as float32), what upload_values made of such a list, or
+    one dense [V,P,C] device tensor such as fit_scene_flow's flow2d, whose valid rows are gathered on the device.  Returns
+    [V,H,W,C] float64 on the device; with the views uploaded (upload_views) and the values on the device it only enqueues."""
+    dev = torch.device("cuda" if device is None else device)
+    pk = upload_views(views, dev, workers)
+    if torch.is_tensor(values) and values.dim() == 3:
+        if values.shape[:2] != (views.V, views.P):
+            raise ValueError(f"dense values must be [{views.V}, {views.P}, C], got {tuple(values.shape)}")
+        vals = values.to(dev).reshape(views.V * views.P, -1).index_select(0, pk["gather"]).to(torch.float32).contiguous()
+    elif torch.is_tensor(values) and values.is_cuda:
+        vals = values                                   # [N, C] on the device already, in the views' order (upload_values)
+    else:
+        vals = upload_values(views, values, dev)
+    return ops.tri_resample(pk["pts"], pk["pt_off"], pk["tris"], pk["tri_off"], vals, views.H, views.W, fill=fill)
+
+
+def compose_slots(render_poses, internal_poses):
+    """View slot i * len(internal) + j -> (Rw2j, Tw2j) = internal[j] o render[i] (train_motion.py:91-97,271-277)."""
+    render_poses, internal_poses = np.asarray(render_poses), np.asarray(internal_poses)
+    slots = []
+    for i in range(len(render_poses)):
+        for j in range(len(internal_poses)):
+            Rw2i, Tw2i = render_poses[i, :3, :3], render_poses[i, :3, 3:4]
+            Ri2j, Ti2j = internal_poses[j, :3, :3], internal_poses[j, :3, 3:4]
+            slots.append((np.matmul(Ri2j, Rw2i), np.matmul(Ri2j, Tw2i) + Ti2j))
+    return slots
+
+
+def pcd_points(src_img, src_mask, depth, K, R0, T0):
+    """The point cloud render_PCD makes of the source image (train_motion.py:213-226): every pixel unprojected with inv(K) and its
+    depth and moved by the inverse of the first render pose, cast to float32; colours and (three equal) mask colours in [0, 1]."""
+    mask3 = np.repeat(np.array(src_mask)[..., np.newaxis], 3, axis=-1).astype(np.uint8)
+    H, W = depth.shape
+    x, y = np.meshgrid(np.arange(W, dtype=np.float32), np.arange(H, dtype=np.float32), indexing="xy")
+    cam = np.matmul(np.linalg.inv(K), np.stack((x * depth, y * depth, 1 * depth), axis=0).reshape(3, -1))
+    world = (np.linalg.inv(R0).dot(cam) - np.linalg.inv(R0).dot(T0)).astype(np.float32)
+    return world, np.array(src_img).reshape(-1, 3).astype(np.float32) / 255., mask3.reshape(-1, 3).astype(np.float32) / 255.
+
+
+def _hint_points(xs, ys, depth, K, R0, T0):
+    """A list of hint pixels in world space (train_motion.py:228-247), with the reference's swapped [h_y, h_x, 1] as written."""
+    out = []
+    for h_x, h_y in zip(xs, ys):
+        cam = np.linalg.inv(K).dot(np.array([[h_y], [h_x], [1]]) * depth[h_y, h_x])
+        out.append((np.linalg.inv(R0).dot(cam) - np.linalg.inv(R0).dot(T0)).astype(np.float32))
+    return out
+
+
+def _project_hints(hints, K, R, T):
+    """(:338-352): the first pixel coordinate goes to the `y` list and the second to the `x` list, as the reference has it."""
+    first, second = [], []
+    for h in hints:
+        pix = np.matmul(K, R.dot(h) + T)
+        pix /= pix[2]
+        first.append(pix[0])
+        second.append(pix[1])
+    return second, first
+
+
+def pcd_views(points, K, slots, H, W):
+    """(ViewSet of the slots that see a point, their slot indices, none_idx) (train_motion.py:285-297)."""
+    poses, valid, pix64, present, none_idx = [], [], [], [], []
+    for idx, (R, T) in enumerate(slots):
+        v, pix = _valid_pixels(points, K, R, T, H, W)
+        if len(v) == 0:
+            none_idx.append(idx)
+            continue
+        poses.append((R, T))
+        valid.append(v)
+        pix64.append(pix)
+        present.append(idx)
+    if not present:
+        raise ValueError("no view sees a point of the cloud")
+    return _view_set(points.shape[1], H, W, poses, valid, pix64), present, none_idx
+
+
+def pcd_values(views, colors, mask_colors):
+    """Per view the [n_j, 4] float32 rows (r, g, b, m) of its valid points; mask_colors [P] or [P,3] (three equal channels: one is kept)."""
+    colors, mask_colors = np.asarray(colors, np.float32), np.asarray(mask_colors, np.float32)
+    rgbm = np.concatenate([colors, (mask_colors if mask_colors.ndim == 1 else mask_colors[:, 0])[:, None]], axis=1)
+    return [rgbm[v] for v in views.valid]
+
+
+def render_pcd_device(views, values, device=None, workers=8):
+    """The device part of render_pcd: (image [V,H,W,3], mask [V,H,W]) uint8 on the device for a ViewSet of the point cloud and its
+    (r, g, b, m) values (pcd_values, or what upload_values made of them).  One tri_resample and one pcd_compose: eight launches for
+    all views; with the views and the values uploaded it only enqueues."""
+    dev = torch.device("cuda" if device is None else device)
+    pk = upload_views(views, dev, workers)
+    return ops.pcd_compose(resample_to_grid(views, values, fill=0.0, device=dev), pk["pts"], pk["pt_off"])
+
+
+def render_pcd(src_img, src_mask, depth, hints, render_poses, internal_poses, device=None, workers=8, K=None):
+    """MotionOptimization.render_PCD (train_motion.py:211-366): the renders of the source image's point cloud from
+    len(render_poses) x len(internal_poses) views, which stage 2 trains on.  src_img, src_mask: PIL images (or arrays) of one size;
+    depth [H,W]: the source depth (the reference's self.src_depth; the depth network is not part of this package); hints: four lists
+    (start x, start y, end x, end y); the poses are arguments as in optimize_motion; K: the intrinsics, by default the
+    reference's (stage1_intrinsics).  Everything that is not per-pixel work follows the reference on the host in its dtypes; each
+    view is triangulated once (triangulate_views, `workers` threads) and the resampling, the border, the mask morphology and the
+    8-bit cast run on the device for all views at once (render_pcd_device).  The reference's depth image (:307-308) is never used
+    and is not computed.  Returns (train_data, none_idx) in the reference's layout (:251-260,354-364): `image` and `mask` are PIL
+    images, T2C_flow and our_flow empty lists; a slot that sees no point is in none_idx and has no frame."""
+    from PIL import Image
+    depth = np.asarray(depth)
+    H, W = depth.shape
+    if K is None:
+        from .scene.dataset_readers import FOCAL
+        K, focal = stage1_intrinsics(H, W), (FOCAL * (W / H), FOCAL)
+    else:
+        K = np.asarray(K)
+        focal = (float(K[0, 0]), float(K[1, 1]))
+    render_poses = np.asarray(render_poses)
+    R0, T0 = render_poses[0, :3, :3], render_poses[0, :3, 3:4]
+    world, colors, mask_colors = pcd_points(src_img, src_mask, depth, K, R0, T0)
+    starts = _hint_points(hints[0], hints[1], depth, K, R0, T0)
+    ends = _hint_points(hints[2], hints[3], depth, K, R0, T0)
+    train_data = {"camera_angle_x": 2 * np.arctan(W / (2 * focal[0])), "camera_angle_y": 2 * np.arctan(H / (2 * focal[1])),
+                  "W": W, "H": H, "pcd_points": world.copy(), "pcd_colors": colors.copy(), "pcd_masks": mask_colors.copy(), "frames": []}
+    slots = compose_slots(render_poses, internal_poses)
+    views, present, none_idx = pcd_views(world, K, slots, H, W)
+    image, mask = (t.cpu().numpy() for t in render_pcd_device(views, pcd_values(views, colors, mask_colors), device, workers))
+    for k, idx in enumerate(present):
+        R, T = slots[idx]
+        sx, sy = _project_hints(starts, K, R, T)
+        ex, ey = _project_hints(ends, K, R, T)
+        train_data["frames"].append({"image": Image.fromarray(image[k]), "transform_matrix": transform_matrix_from_pose(R, T).tolist(),
+                                     "mask": Image.fromarray(mask[k]), "final_hint_start_x": sx, "final_hint_start_y": sy,
+                                     "final_hint_end_x": ex, "final_hint_end_y": ey, "T2C_flow": [], "our_flow": []})
+    return train_data, none_idx
 
 
 def _fit_slots(train_data, slots, K, H, W, train_iteration, device=None, sampler="griddata"):
@@ -300,26 +533,23 @@ def _fit_slots(train_data, slots, K, H, W, train_iteration, device=None, sampler
 
 
 def optimize_motion(train_data, render_poses, internal_poses, K, H, W, non_frame_idx=(), train_iteration=200, device=None,
-                    sampler="griddata"):
+                    sampler="griddata", resampler="griddata", workers=8):
     """MotionOptimization.optimize_motion (train_motion.py:65-207) without its unused arguments: view slot idx = i * len(internal)
     + j has the pose internal[j] o render[i] (:91-97); slots in non_frame_idx have no flow; the k-th remaining slot takes
     train_data['frames'][k]['T2C_flow'][0].  After the fit each fitted slot's last-epoch 2D flow is resampled onto the pixel
-    grid and appended to train_data['frames'][idx]['our_flow'] -- indexed by the SLOT, as the reference does (:200); that
-    resampling triangulates each view's scattered pixels and stays scipy's griddata whatever `sampler` (_fit_slots) is.
-    Returns (train_data, scene_flow [3,P] on the device)."""
-    render_poses, internal_poses = np.asarray(render_poses), np.asarray(internal_poses)
-    slots = []
-    for i in range(len(render_poses)):
-        for j in range(len(internal_poses)):
-            idx = i * len(internal_poses) + j
-            if idx in non_frame_idx:
-                slots.append(None)
-                continue
-            Rw2i, Tw2i = render_poses[i, :3, :3], render_poses[i, :3, 3:4]
-            Ri2j, Ti2j = internal_poses[j, :3, :3], internal_poses[j, :3, 3:4]
-            slots.append((np.matmul(Ri2j, Rw2i), np.matmul(Ri2j, Tw2i) + Ti2j))
+    grid and appended to train_data['frames'][idx]['our_flow'] -- indexed by the SLOT, as the reference does (:200) -- as a
+    [1,2,H,W] float64 CPU tensor.  resampler: "griddata" does that with one scipy griddata per view on the host, as the reference
+    does; "device" triangulates each view once on `workers` host threads (triangulate_views) and resamples all views in one call
+    (resample_to_grid) from the flow the fit left on the device.  Returns (train_data, scene_flow [3,P] on the device)."""
+    if resampler not in RESAMPLERS:
+        raise ValueError(f"resampler must be one of {RESAMPLERS}, got {resampler!r}")
+    slots = [None if idx in non_frame_idx else s for idx, s in enumerate(compose_slots(render_poses, internal_poses))]
     views, present, _, flow, _, flow2d = _fit_slots(train_data, slots, K, H, W, train_iteration, device, sampler)
-    if train_iteration > 0:
+    if train_iteration > 0 and resampler == "device":
+        final = resample_to_grid(views, flow2d, fill=0.0, device=flow2d.device, workers=workers).permute(0, 3, 1, 2).cpu()
+        for k, idx in enumerate(present):
+            train_data["frames"][idx]["our_flow"].append(final[k].contiguous().unsqueeze(0))
+    elif train_iteration > 0:
         griddata, grid = _griddata(), _pixel_grid(H, W)
         flow2d = flow2d.cpu().numpy()
         points = np.asarray(train_data["pcd_points"])
@@ -355,14 +585,17 @@ def stage1_intrinsics(H, W):
     return np.array([[FOCAL * (W / H), 0., W / 2], [0., FOCAL, H / 2], [0., 0., 1.]]).astype(np.float32)
 
 
-def refit_scene_flow(input_dir, train_iteration=200, device=None, sampler="griddata"):
+def refit_scene_flow(input_dir, train_iteration=200, device=None, sampler="griddata", resampler="griddata"):
     """Fits the scene flow of a stage-1 directory again from what MOM/train_data.pth holds -- the point cloud, every frame's pose
     (its transform_matrix) and 2D flow (T2C_flow) -- and writes MOM/scene_flow.pth.  A frame with an empty T2C_flow list is a view
-    without a flow.  sampler: "griddata" (one scipy call per view on the host) or "device" (_fit_slots).  Returns the [3,P] flow
-    (a CPU tensor, what is written)."""
+    without a flow.  sampler: "griddata" (one scipy call per view on the host) or "device" (_fit_slots).  resampler: checked like
+    optimize_motion's and otherwise without effect here -- the refit writes the scene flow alone, and our_flow, the one thing the
+    resampler makes, is not part of it.  Returns the [3,P] flow (a CPU tensor, what is written)."""
     from .scene.dataset_readers import load_train_data
     if sampler not in SAMPLERS:
         raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
+    if resampler not in RESAMPLERS:
+        raise ValueError(f"resampler must be one of {RESAMPLERS}, got {resampler!r}")
     mom = os.path.join(input_dir, "MOM")
     data = load_train_data(os.path.join(mom, "train_data.pth"))
     H, W = int(data["H"]), int(data["W"])
@@ -386,8 +619,11 @@ def main(argv=None):
     ap.add_argument("--train_iteration", type=int, default=200)
     ap.add_argument("--sampler", choices=SAMPLERS, default="griddata", help="where the 2D flow images are sampled: scipy's griddata "
                     "per view on the host, or one HIP launch for all views")
+    ap.add_argument("--resampler", choices=RESAMPLERS, default="griddata", help="where optimize_motion resamples our_flow onto the "
+                    "pixel grid: scipy's griddata per view on the host, or one triangulation per view and the device for the rest; "
+                    "scene_flow.pth does not depend on it")
     a = ap.parse_args(argv)
-    flow = refit_scene_flow(a.input_dir, a.train_iteration, sampler=a.sampler)
+    flow = refit_scene_flow(a.input_dir, a.train_iteration, sampler=a.sampler, resampler=a.resampler)
     print(f"scene_flow.pth: {tuple(flow.shape)}, largest magnitude {float(flow.abs().max()):.6g}")
 
 

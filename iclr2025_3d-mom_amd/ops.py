@@ -647,6 +647,82 @@ def png_encode(rgb8, out, out_size, scratch):
     return out
 
 
+# --------------------------------------------------------------------------- scattered values -> the pixel grid (stage 1)
+def _tri_views(name, pts, pt_off, H, W):
+    """Checks shared by tri_resample and pcd_compose; returns (V, N, device)."""
+    _need_cuda(pts, name)
+    dev = pts.device
+    if pts.dim() != 2 or pts.shape[1] != 2 or pts.dtype != torch.float64 or not pts.is_contiguous():
+        raise N.MomError(f"{name}: pts must be a contiguous torch.float64 [N,2] tensor, got {pts.dtype} {list(pts.shape)}")
+    if pt_off.dim() != 1 or pt_off.numel() < 2 or pt_off.dtype != torch.int32 or pt_off.device != dev or not pt_off.is_contiguous():
+        raise N.MomError(f"{name}: pt_off must be a contiguous torch.int32 [V+1] tensor on {dev} with V >= 1, "
+                         f"got {pt_off.dtype} {list(pt_off.shape)} on {pt_off.device}")
+    V = pt_off.numel() - 1
+    if N.lib().mom_tri_resample_scratch_bytes(V, H, W) == 0:
+        raise N.MomError(f"{name}: unsupported shape V {V}, H {H}, W {W}")
+    return V, pts.shape[0], dev
+
+
+def tri_resample(pts, pt_off, tris, tri_off, values, H, W, fill=0.0, out=None, scratch=None):
+    """Linear interpolation of values given at each view's projected points, at every pixel centre: what
+    scipy.interpolate.griddata(points, values, pixel grid, "linear", fill_value=fill) gives (train_motion.py:198,304,319), for all
+    V views in one call, from the views' triangulations (csrc/tri_resample.hip; include/mom4d.h has the arithmetic and the
+    lowest-index rule).  Enqueued on the current stream; nothing is read back.
+
+    pts [N,2] float64, the views' points concatenated; pt_off [V+1] int32; tris [T,3] int32, indices local to the view;
+    tri_off [V+1] int32 (both offset arrays non-decreasing from 0 to N / T: they are not read on the host); values [N,C] float32,
+    1 <= C <= 8: contiguous on one device.  Returns out [V,H,W,C] float64 (allocated when not given).  scratch: an int32 tensor
+    of at least V*H*W elements to reuse, or None."""
+    V, n, dev = _tri_views("tri_resample", pts, pt_off, H, W)
+    if values.dim() != 2 or not 1 <= values.shape[1] <= 8:
+        raise N.MomError(f"tri_resample: values must be [N,C] with 1 <= C <= 8, got {tuple(values.shape)}")
+    C_ = values.shape[1]
+    if tris.dim() != 2:
+        raise N.MomError(f"tri_resample: tris must be [T,3], got {tuple(tris.shape)}")
+    T = tris.shape[0]
+    want = [("tris", tris, (T, 3), torch.int32), ("tri_off", tri_off, (V + 1,), torch.int32),
+            ("values", values, (n, C_), torch.float32)]
+    if out is not None:
+        want.append(("out", out, (V, H, W, C_), torch.float64))
+    for name, t_, shape, dtype in want:
+        if tuple(t_.shape) != shape or t_.dtype != dtype or t_.device != dev or not t_.is_contiguous():
+            raise N.MomError(f"tri_resample: {name} must be a contiguous {dtype} {list(shape)} tensor on {dev}, "
+                             f"got {t_.dtype} {list(t_.shape)} on {t_.device}")
+    if out is None:
+        out = torch.empty((V, H, W, C_), dtype=torch.float64, device=dev)
+    if scratch is None:
+        scratch = torch.empty(V * H * W, dtype=torch.int32, device=dev)
+    elif scratch.dtype != torch.int32 or scratch.device != dev or not scratch.is_contiguous() or scratch.numel() < V * H * W:
+        raise N.MomError(f"tri_resample: scratch must be a contiguous torch.int32 tensor of at least {V * H * W} elements on {dev}")
+    N.check(N.lib().mom_tri_resample(V, H, W, C_, n, T, N.ptr(pts), pt_off.data_ptr(), N.ptr(tris), tri_off.data_ptr(),
+                                     N.ptr(values), float(fill), out.data_ptr(), scratch.data_ptr(), scratch.numel() * 4,
+                                     N.current_stream()), "mom_tri_resample")
+    return out
+
+
+def pcd_compose(resampled, pts, pt_off):
+    """The per-pixel remainder of the reference's render_PCD (train_motion.py:298-330,355,357) for V views: border, hit map, 9 x 9
+    dilation, 11 x 11 erosions, the 8-bit cast (csrc/tri_resample.hip; include/mom4d.h lists the steps).  resampled [V,H,W,4]
+    float64 = tri_resample of (r, g, b, mask) with fill 0; pts, pt_off as for tri_resample.  Returns (image [V,H,W,3],
+    mask [V,H,W]) uint8 on the device.  Enqueued on the current stream; nothing is read back."""
+    if resampled.dim() != 4 or resampled.shape[3] != 4 or resampled.dtype != torch.float64 or not resampled.is_contiguous():
+        raise N.MomError(f"pcd_compose: resampled must be a contiguous torch.float64 [V,H,W,4] tensor, got {resampled.dtype} "
+                         f"{list(resampled.shape)}")
+    _, H, W, _ = resampled.shape
+    V, n, dev = _tri_views("pcd_compose", pts, pt_off, H, W)
+    if resampled.shape[0] != V or resampled.device != dev:
+        raise N.MomError(f"pcd_compose: resampled has {resampled.shape[0]} views on {resampled.device}, pt_off {V} on {dev}")
+    nbytes = int(N.lib().mom_pcd_compose_scratch_bytes(V, H, W))
+    if nbytes == 0:
+        raise N.MomError(f"pcd_compose: unsupported shape V {V}, H {H}, W {W} (H, W >= 5)")
+    image = torch.empty((V, H, W, 3), dtype=torch.uint8, device=dev)
+    mask = torch.empty((V, H, W), dtype=torch.uint8, device=dev)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    N.check(N.lib().mom_pcd_compose(V, H, W, n, resampled.data_ptr(), N.ptr(pts), pt_off.data_ptr(), image.data_ptr(),
+                                    mask.data_ptr(), scratch.data_ptr(), nbytes, N.current_stream()), "mom_pcd_compose")
+    return image, mask
+
+
 # --------------------------------------------------------------------------- densification statistics
 def densify_stats(radii, viewspace_grad, max_radii2D, xyz_gradient_accum, denom, skip_flag=None, stream=None):
     """In place, for the Gaussians with radii > 0: running maximum radius, accumulated |dL/d mean2D| and its count

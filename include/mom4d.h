@@ -637,6 +637,58 @@ int mom_sceneflow_fit(int P, int V, int E, const float* points, const float* K, 
 int mom_flow_sample(int P, int V, int H, int W, const float* flow, const double* pix, const uint32_t* valid, const uint32_t* diag,
                     float* records, mom_stream_t stream);
 
+/* ---- values given at each view's projected points -> every pixel centre (train_motion.py:198,304,319) ----
+ * What scipy.interpolate.griddata(view's pixels, values, pixel grid, method="linear", fill_value=fill) computes, for all V views in
+ * one call (csrc/tri_resample.hip), given the views' triangulations (scipy.spatial.Delaunay's simplices: the host makes them once per
+ * view, motion.triangulate_views).  Pixel (X, Y) of view j takes the LOWEST-INDEX triangle of that view whose test passes, and `fill`
+ * if none does.  For a triangle with vertices p0, p1, p2 (rows tris[t][0..2] of the view's points), in float64 without contraction:
+ *     a = x0 - x2; b = x1 - x2; c = y0 - y2; d = y1 - y2; det = a d - b c; dx = X - x2; dy = Y - y2
+ *     c0 = (d dx - b dy) / det;  c1 = (a dy - c dx) / det;  c2 = (1 - c0) - c1
+ *     test: -eps <= ci <= 1 + eps for all three, eps = 100 * 2^-52 (the bounds scipy's LinearNDInterpolator uses)
+ *     out[k] = ((c0 v0[k]) + (c1 v1[k])) + (c2 v2[k])                                         (float -> double)
+ *   The test is evaluated at the pixel centres of the triangle's bounding box, grown by MOM_TRI_BOX_GROW = 2^-20 on every side and
+ *   clamped to the image: [ceil(min x - 2^-20), floor(max x + 2^-20)] x the same in y.  In exact arithmetic a centre outside the
+ *   ungrown box by more than eps (|a| + |b|) cannot pass, so nothing is missed while the vertices lie within 2^24 of the image.
+ *   A triangle with an index outside [0, n_j), a non-finite vertex, det == 0 or a non-finite det is skipped.
+ *   pts     [N,2] float64 (16-byte aligned): the views' points (u, v) concatenated, view j's are rows pt_off[j] .. pt_off[j+1]
+ *   pt_off  [V+1], tri_off [V+1] int32 DEVICE arrays.  Contract: non-decreasing, off[0] = 0, off[V] = N (T).  They are not read on the
+ *           host; whatever they hold, a range read from them is used only if it lies within [0, N] ([0, T]), so a broken array loses
+ *           triangles, never reaches an address outside the buffers and never makes a loop longer than 16 steps
+ *   tris    [T,3] int32, indices LOCAL to the view;  values [N,C] float32, 1 <= C <= 8;  out [V,H,W,C] float64, written in full
+ *   scratch mom_tri_resample_scratch_bytes(V, H, W) bytes, 4-byte aligned: owner [V,H,W] int32, the index of each pixel's triangle.
+ *           The owner word, not the order the atomics land in, decides the result: the same bits on every run
+ * Three launches on `stream` (init, cover, resolve); no allocation, no copy, no synchronisation.  A lane walks its triangle's box while
+ * that has at most MOM_TRI_LANE_BOX pixels; a larger one is taken by the whole wave.  A view without points or triangles is all `fill`.
+ * V <= 0, V > 65535, H < 1, W < 1, V H W >= 2^31, C outside 1..8, N < 0, T < 0, a null pointer that would be read or written, a
+ * misaligned pts / scratch or a scratch_bytes below the sizing function's value (0 for an unsupported shape): MOM_EINVAL before
+ * anything is launched. */
+#define MOM_TRI_LANE_BOX 64
+size_t mom_tri_resample_scratch_bytes(int V, int H, int W);
+int mom_tri_resample(int V, int H, int W, int C, int N, int T, const double* pts, const int* pt_off, const int* tris,
+                     const int* tri_off, const float* values, double fill, double* out, void* scratch, size_t scratch_bytes,
+                     mom_stream_t stream);
+
+/* ---- the per-pixel remainder of the multi-view point-cloud renders (MotionOptimization.render_PCD, train_motion.py:298-330,355,357)
+ * resampled [V,H,W,4] float64 = (r, g, b, m): mom_tri_resample's output for the points' colours and ONE mask channel (the reference's
+ * three are equal; where it sums three, (m + m) + m is formed).  Per view, everything in float64 without contraction, as written there:
+ *    1 border (:305,320)  I = resampled[clamp(y,1,H-2)][clamp(x,1,W-2)], what edgemask I + (1-edgemask) pad(I[1:-1,1:-1], edge) is
+ *    2 hit (:298,310-311) hit[rint(v)][rint(u)] = 1 for every point of the view (half to even; a point that rounds outside is skipped)
+ *    3 dil (:312)         the 9 x 9 maximum of hit, the window clipped to the image (scipy's `reflect` border for a maximum / minimum)
+ *    4 holes (:313)       rgb' = dil rgb + (1 - dil) (-1)
+ *    5 (:315)             mj = the 11 x 11 minimum of ((r' + g') + b' != -3)
+ *    6 (:316)             image = mj rgb' + (1 - mj) 0
+ *    7 (:325)             m' = dil m + (1 - mj) (-1)          -- mj, the RGB pass's eroded mask, as the reference has it
+ *    8 (:327)             mj2 = the 11 x 11 minimum of ((m' + m') + m' != -3)
+ *    9 (:328-330)         mask = mj2 m' + (1 - mj2) 0
+ *   10 (:355,357)         byte = rint(255 x), half to even; the reference's values lie in [0, 1], anything else is clamped to 0..255
+ *   image [V,H,W,3], mask [V,H,W] uint8;  pts, pt_off as for mom_tri_resample;  scratch: mom_pcd_compose_scratch_bytes(V, H, W) bytes
+ *   (five byte maps).
+ * Five launches on `stream`; no allocation, no copy, no synchronisation.  The shapes mom_tri_resample refuses, H < 5, W < 5, a null
+ * pointer, a misaligned pts / resampled or too small a scratch: MOM_EINVAL before anything is launched. */
+size_t mom_pcd_compose_scratch_bytes(int V, int H, int W);
+int mom_pcd_compose(int V, int H, int W, int N, const double* resampled, const double* pts, const int* pt_off, uint8_t* image,
+                    uint8_t* mask, void* scratch, size_t scratch_bytes, mom_stream_t stream);
+
 /* ---- rendered image -> 8-bit interleaved RGB (render_4DGS.py:64 torchvision.utils.save_image: x * 255 + 0.5, clamp, truncate;
  * CHW -> HWC) in one pass, so that a frame can leave the device as the bytes a PNG encoder takes.  img [C,H,W] floats, out [H,W,C]
  * bytes; C <= 4. */
