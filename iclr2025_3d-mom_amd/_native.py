@@ -206,7 +206,7 @@ def _sig(lib):
     lib.mom_deform_backward_scratch_bytes.argtypes = [i32]
     lib.mom_deform_backward.argtypes = [C.POINTER(MomDeformMLP), i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mom_deform_backward_split.argtypes = [C.POINTER(MomDeformMLP), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    # the same four with in_features (64, or 32: csrc/deform_mlp32.hip) after P
+    # the same four with in_features (64 or 32: csrc/deform_mlp.hip) after P
     lib.mom_deform_forward_n.argtypes = [C.POINTER(MomDeformMLP), i32, i32, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]
     lib.mom_deform_forward_activated_n.argtypes = [C.POINTER(MomDeformMLP), i32, i32, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp,
                                                    vp, vp, vp, vp]

@@ -2,9 +2,9 @@
 // defor_depth 0), forward, one timestamp for all points, gfx950.
 //
 // The result of mom_hexplane_forward (channels 16, two levels; hexplane.hip at C = 16) followed by mom_deform_forward_activated_n
-// (in_features 32; deform_mlp32.hip), bit for bit, without feat[P,32] in between: a wave gathers the 32 features of its tile of 32
-// Gaussians into LDS, reads them back as the trunk layer's B operand and runs deform32_fwd_kernel's MLP on them.  fp32 throughout
-// (v_mfma_f32_32x32x2_f32, the k-ascending chains of deform_mlp_dev.h / deform_mlp32_dev.h): no bf16 split and no per-frame time
+// (in_features 32; deform_mlp.hip), bit for bit, without feat[P,32] in between: a wave gathers the 32 features of its tile of 32
+// Gaussians into LDS, reads them back as the trunk layer's B operand and runs deform_fwd_kernel<1>'s MLP on them.  fp32 throughout
+// (v_mfma_f32_32x32x2_f32, the k-ascending chains of deform_mlp_dev.h): no bf16 split and no per-frame time
 // lines here -- both reassociate sums, and a no-grad render() of such a model has to give the image of the op-by-op route.
 //
 // Gather (the lane mapping of hexplane.hip at C = 16): sixteen lanes own one (point, level), lane = channel; the wave's four groups take
@@ -22,7 +22,7 @@
 //                                                               stride of 36 banks, spread sixteen consecutive lanes over all 64 banks)
 //             records      [2 levels][32 points] x 16 B  1024 B   (the four groups read four ADJACENT records: four banks apart)
 //   70 720 + 16 x 5632 = 160 832 B of the CU's 163 840.
-#include "deform_mlp32_dev.h"
+#include "deform_mlp_dev.h"
 #include "hexplane_dev.h"
 
 namespace {
@@ -30,7 +30,8 @@ namespace {
 constexpr int kC16 = 16;                             // channels = floats of one texel row
 constexpr unsigned kRow16B = kC16 * 4u;              // bytes of one texel row
 constexpr int kF16Waves = 16;                        // waves per workgroup
-constexpr int kTileStride = kIn32 + 4;               // floats of one Gaussian's row of the feature tile
+constexpr int kF16In = 32;                           // features of a Gaussian: two levels of kC16 channels
+constexpr int kTileStride = kF16In + 4;              // floats of one Gaussian's row of the feature tile
 constexpr int kTileFloats = 32 * kTileStride;
 constexpr int kRecFloats = 2 * 32 * 4;               // uint4 [level][point]
 constexpr int kLTile = kLFwdTotal;                   // [kF16Waves][kTileFloats]
@@ -134,7 +135,7 @@ __device__ __forceinline__ void gather16_tile(const HexArgs& a, const float* __r
             tile[pt * kTileStride + kC16 * lvl + ch] = prod;
             if (feat_save) {
                 const int g = __shfl(g_mine, pt);            // (lanes 0..31 hold the tile's 32 points; every lane is active)
-                if (g >= 0) feat_save[(size_t)g * kIn32 + kC16 * lvl + ch] = prod;
+                if (g >= 0) feat_save[(size_t)g * kF16In + kC16 * lvl + ch] = prod;
             }
         }
     }
@@ -142,7 +143,7 @@ __device__ __forceinline__ void gather16_tile(const HexArgs& a, const float* __r
 }
 
 // one workgroup of sixteen waves per CU around one copy of the weights; a contiguous, equal (+-1) share of the tiles per workgroup,
-// dealt to its waves (deform32_fwd_kernel's loop with the gather in front of each tile)
+// dealt to its waves (deform_fwd_kernel<1>'s loop with the gather in front of each tile)
 __global__ void __launch_bounds__(64 * kF16Waves)
 deform_field16_fwd_kernel(HexArgs a, MlpDev m, int tiles, const float* __restrict__ xyz, const float* __restrict__ scaling,
                           const float* __restrict__ rotation, const float* __restrict__ flow, float flow_coef,
@@ -150,7 +151,7 @@ deform_field16_fwd_kernel(HexArgs a, MlpDev m, int tiles, const float* __restric
                           float* __restrict__ feat_save, float* __restrict__ a0_save, ActOut act)
 {
     extern __shared__ float lds[];
-    load_weights32(m, lds);
+    load_weights<1>(m, lds);
     __syncthreads();
     const int lane = threadIdx.x & 63, col = lane & 31, h = lane >> 5, wv = threadIdx.x >> 6;
     float* __restrict__ tile = lds + kLTile + wv * kTileFloats;
@@ -166,20 +167,20 @@ deform_field16_fwd_kernel(HexArgs a, MlpDev m, int tiles, const float* __restric
         f32x16 a0[2];
         {
             // the tile's rows in the trunk layer's operand layout: register 4q+j of lane half h is feature 8q+4h+j
-            f32x16 x;
+            f32x16 x[1];
             const float* row = tile + col * kTileStride + 4 * h;
 #pragma unroll
             for (int qq = 0; qq < 4; qq++) {
                 float4 v = *reinterpret_cast<const float4*>(row + 8 * qq);
                 if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
-                x[4 * qq + 0] = v.x;
-                x[4 * qq + 1] = v.y;
-                x[4 * qq + 2] = v.z;
-                x[4 * qq + 3] = v.w;
+                x[0][4 * qq + 0] = v.x;
+                x[0][4 * qq + 1] = v.y;
+                x[0][4 * qq + 2] = v.z;
+                x[0][4 * qq + 3] = v.w;
             }
             __builtin_amdgcn_wave_barrier();                // (the next tile's gather writes these rows)
             init_bias(lds + kLB, a0, h);
-            trunk32(lds + kLW, x, a0, col, h);
+            layer64<false>(lds + kLW, x, a0, col, h);
         }
         relu_tile(a0);
         if (a0_save) store_feat(a0_save, g, ok, h, a0);     // relu(h0) [P,64], what the backward kernels reuse

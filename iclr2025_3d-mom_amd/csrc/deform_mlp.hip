@@ -25,13 +25,28 @@
 // MFMA operands are plain coalesced 256-byte loads (lane = feature), every byte is read exactly once, the four
 // 64x64 results live in 256 accumulator registers for the wave's whole range, and the bias gradients fall out of
 // the A operands for free.  No atomics until one float atomic per weight per workgroup at the very end.
+//
+// The three kernels are templates on KT, the trunk's input in tiles of 32 features (deform_mlp_dev.h): 2 for the 64 features of
+// two HexPlane levels of 32 channels, 1 for the 32 of two levels of 16 (dnerf/eulerian_150_16).  With KT = 1 the trunk layer reads
+// W0 [64,32] and f [32] (a0_save stays [P,64]); dx back-propagates dH0 through W0^T to dfeat [P,32]; dW forms dW0 [64,32] = dH0^T
+// feat with feat [P,32].  There the B operand's lane is still the input feature and its lane half the K slot (one of two
+// Gaussians): two consecutive 128-byte feature rows are ONE 256-byte load of all 64 lanes, so the trunk layer issues one operand
+// load and two MFMAs per K step where KT = 2 issues two and four, and no lane is masked.
+//
+// There is no bf16 one-kernel backward for 32 features (deform_bwd_b3.hip is 64 features only): such a call runs the two f32
+// kernels whatever MOM_MLP_BWD names -- unset, empty, "b3" or "split" -- and any other value is MOM_EINVAL as for 64 features.
 #include "deform_mlp_dev.h"
 #include <string.h>
+
+int mom_launch_deform_bwd_b3f(const MomDeformMLP* w, int P, const float* feat, const float* a0, const float* dpts, const float* dscales,
+                              const float* drots, float* dfeat, void* scratch, hipStream_t s, hipStream_t dw_stream);      // deform_bwd_b3.hip
+size_t mom_deform_bwd_b3f_scratch_bytes(void);
 
 namespace {
 
 // All threads of a workgroup share ONE copy of the weights in LDS (70 KB).  With 256 threads two workgroups = 8 waves fit per
 // CU although the registers allow 16: a workgroup of up to 1024 threads gets up to 16 waves for the same LDS.
+template <int KT>
 __global__ void __launch_bounds__(1024)
 deform_fwd_kernel(MlpDev m, int P, int tiles, const float* __restrict__ feat, const float* __restrict__ xyz,
                   const float* __restrict__ scaling, const float* __restrict__ rotation, const float* __restrict__ flow,
@@ -39,7 +54,7 @@ deform_fwd_kernel(MlpDev m, int P, int tiles, const float* __restrict__ feat, co
                   float* __restrict__ a0_save, ActOut act)
 {
     extern __shared__ float lds[];
-    load_weights(m, lds);
+    load_weights<KT>(m, lds);
     __syncthreads();
     const int lane = threadIdx.x & 63, col = lane & 31, h = lane >> 5;
     // Every workgroup takes a contiguous, equal (+-1) share of the tiles and deals it to its waves.  Dealing tiles to ALL the
@@ -52,13 +67,13 @@ deform_fwd_kernel(MlpDev m, int P, int tiles, const float* __restrict__ feat, co
         const bool ok = g < P;
         f32x16 a0[2];
         {
-            f32x16 x[2];
+            f32x16 x[KT];
             load_feat(feat, g, ok, h, x);
             init_bias(lds + kLB, a0, h);
             layer64<false>(lds + kLW, x, a0, col, h);
         }
         relu_tile(a0);
-        if (a0_save) store_feat(a0_save, g, ok, h, a0);     // relu(h0), reused by the backward kernels
+        if (a0_save) store_feat(a0_save, g, ok, h, a0);     // relu(h0) [P,64], reused by the backward kernels
 #pragma nounroll
         for (int head = 0; head < 3; head++) {
             f32x16 h1[2];
@@ -102,16 +117,17 @@ deform_fwd_kernel(MlpDev m, int P, int tiles, const float* __restrict__ feat, co
 }
 
 // ---------------------------------------------------------------------------------------------- backward
-// (A) activations backward: dH for the four layers, d(features), output-layer weight gradients
+// (A) activations backward: dH for the four layers, d(features) [P][32 KT], output-layer weight gradients
 // 512 threads: two waves per SIMD share one copy of the weights (142 KB of LDS with the staging tiles), so that one wave's vector
 // and memory phases -- the thin output layers, the dH stores -- run under the other's MFMAs (4 waves: 288 us for dx + dW, 8: 276)
+template <int KT>
 __global__ void __launch_bounds__(64 * kDxWaves)
 deform_bwd_dx_kernel(MlpDev m, int P, int tiles, const float* __restrict__ a0g, const float* __restrict__ dpts,
                      const float* __restrict__ dscales, const float* __restrict__ drots, float* __restrict__ dfeat,
                      float* __restrict__ dH /* [4][P][64] */)
 {
     extern __shared__ float lds[];
-    load_weights(m, lds);
+    load_weights<KT>(m, lds);
     __syncthreads();
     const int lane = threadIdx.x & 63, col = lane & 31, h = lane >> 5, wv = threadIdx.x >> 6;
     float* sA = lds + kLStage + wv * kStageFloats;
@@ -195,9 +211,9 @@ deform_bwd_dx_kernel(MlpDev m, int P, int tiles, const float* __restrict__ a0g, 
             for (int r = 0; r < 16; r++) dA0[mt][r] = a0[mt][r] > 0.f ? dA0[mt][r] : 0.f;
         store_feat(dH, g, ok, h, dA0);
         {
-            f32x16 df[2];
+            f32x16 df[KT];
             zero_tile(df);
-            layer64<true>(lds + kLW, dA0, df, col, h);  // dfeat = W0^T dH0
+            layer64<true>(lds + kLW, dA0, df, col, h);  // dfeat = W0^T dH0, 32 KT rows
             store_feat(dfeat, g, ok, h, df);
         }
     }
@@ -227,85 +243,58 @@ deform_bwd_dx_kernel(MlpDev m, int P, int tiles, const float* __restrict__ a0g, 
     }
 }
 
-// (B) weight gradients: dW_L[o][i] = sum_g dH_L[g][o] X_L[g][i], db_L[o] = sum_g dH_L[g][o];  X_0 = feat, X_1..3 = a0
-//
-// The kernel streams dwords and is bound by how many cache misses a CU keeps in flight, not by the matrix pipe (SQ counters
-// with all four layers in one wave: MFMA busy 30 % of the time, the rest issue stalls on VMEM).  So a wave takes ONE layer
-// of its range of Gaussians: 64 accumulators, four waves per SIMD, four times the loads in flight of the form with all four
-// layers (256 accumulators, one wave per SIMD); measured, dx + dW: 344 / 339 / 326 us for 4 / 2 / 1 layers per wave.  dH is
-// still read exactly once overall; a0 is read once per layer 1..3.
-__global__ void __launch_bounds__(256)
-deform_bwd_dw_kernel(MlpDev m, int P, int chunk, const float* __restrict__ feat, const float* __restrict__ a0g,
-                     const float* __restrict__ dH, int ny)
+// One layer's weight gradient over one wave's range of Gaussians, for the 32-feature trunk's form of kernel (B) below:
+// dW[o][i] = sum_g dH[g][o] X[g][i], db[o] = sum_g dH[g][o].
+// KT = tiles of 32 input features: 2 for the heads (X = a0 [P,64], as deform_bwd_dw_kernel), 1 for the trunk (X = feat [P,32]).
+// The B operand's lane half is the K slot, a Gaussian of the pair g0 + 2u + {0,1}: with KT = 1 the two halves read two consecutive
+// 128-byte rows, one 256-byte load of the whole wave.
+template <int KT>
+__device__ __forceinline__ void dw_layer(const float* __restrict__ xa, const float* __restrict__ dHl, int g_begin, int g_end,
+                                         float* __restrict__ dst, float* __restrict__ dbs, float* __restrict__ R)
 {
-    extern __shared__ float lds[];                     // [64][64] reduction scratch
-    constexpr int NL = 1;                              // layers per wave; ny = 4 / NL layer groups (written out for NL = 1 the same
-                                                       // source compiles to another schedule, so the loops over NL stay)
+    constexpr int kIn = 32 * KT;
     const int lane = threadIdx.x & 63, col = lane & 31, h = lane >> 5;
-    // One-dimensional grid of (ranges of Gaussians) x (ny layer groups), numbered so that the ny workgroups of one range are 8
-    // ids apart inside a run of 8 ny ids: workgroup ids go to the eight XCDs in turn, so the layer groups of a range land on the
-    // SAME XCD at about the same time, and the rows of a0 the three head layers all read come out of that XCD's L2 twice out of
-    // three times (a two-dimensional grid ran all ranges of layer 0, then all of layer 1, ...: three trips to memory).
-    const int lin = blockIdx.x, run = 8 * ny;
-    const int bx = (lin / run) * 8 + (lin % run) % 8, by = (lin % run) / 8;
-    const int wave = (bx * 256 + threadIdx.x) >> 6;
-    const int L0 = NL * by;                            // first layer of this workgroup
-    const size_t PH = (size_t)P * kHid;
-    const int g_begin = wave * chunk, g_end = min(P, g_begin + chunk);   // chunk is even
-
-    f32x16 dW[NL][2][2];
-    float db[NL][2];
+    f32x16 dW[2][KT];
+    float db[2] = {0.f, 0.f};
 #pragma unroll
-    for (int l = 0; l < NL; l++) {
-        zero_tile(dW[l][0]);
-        zero_tile(dW[l][1]);
-        db[l][0] = db[l][1] = 0.f;
-    }
-    // Operand loads are double buffered by hand.  A trip is UNR K-steps (2 gaussians each); the loads of trip t+1 are issued
-    // before the MFMAs of trip t.  They are issued UNCONDITIONALLY (rows past the end are clamped and masked by `ok`): vmcnt
-    // retires in order, and a prefetch behind a branch would make the compiler wait for it too.
+    for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+        for (int kt = 0; kt < KT; kt++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) dW[mt][kt][r] = 0.f;
+    // operand loads double buffered by hand and issued unconditionally (rows past the end are clamped and masked by `ok`), as in
+    // deform_bwd_dw_kernel
     constexpr int UNR = 4;
     struct Operands {
-        float x[UNR][2], da[UNR][NL][2];
+        float x[UNR][KT], da[UNR][2];
         bool ok[UNR];
     };
-    const float* __restrict__ xa = L0 == 0 ? feat : a0g;      // layer L reads X = feat (L == 0) or a0 (L >= 1)
     auto load = [&](Operands& o, int g0) {
 #pragma unroll
         for (int u = 0; u < UNR; u++) {
             const int g = g0 + 2 * u + h;               // K slot of this lane half
             const bool ok = g < g_end;
             o.ok[u] = ok;
-            const size_t row = (size_t)(ok ? g : g_begin) * kHid;
+            const size_t row = (size_t)(ok ? g : g_begin);
 #pragma unroll
-            for (int kt = 0; kt < 2; kt++) o.x[u][kt] = xa[row + 32 * kt + col];
-#pragma unroll
-            for (int l = 0; l < NL; l++) {
-                const float* __restrict__ d = dH + (size_t)(L0 + l) * PH + row;
-                o.da[u][l][0] = d[col];
-                o.da[u][l][1] = d[32 + col];
-            }
+            for (int kt = 0; kt < KT; kt++) o.x[u][kt] = xa[row * kIn + 32 * kt + col];
+            o.da[u][0] = dHl[row * kHid + col];
+            o.da[u][1] = dHl[row * kHid + 32 + col];
         }
     };
     auto compute = [&](const Operands& o) {
 #pragma unroll
         for (int u = 0; u < UNR; u++) {
+            const float a_lo = o.ok[u] ? o.da[u][0] : 0.f, a_hi = o.ok[u] ? o.da[u][1] : 0.f;
+            db[0] += a_lo;
+            db[1] += a_hi;
 #pragma unroll
-            for (int l = 0; l < NL; l++) {
-                const float a_lo = o.ok[u] ? o.da[u][l][0] : 0.f, a_hi = o.ok[u] ? o.da[u][l][1] : 0.f;
-                db[l][0] += a_lo;
-                db[l][1] += a_hi;
-                const float x0 = o.x[u][0], x1 = o.x[u][1];
-                dW[l][0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_lo, x0, dW[l][0][0], 0, 0, 0);
-                dW[l][0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_lo, x1, dW[l][0][1], 0, 0, 0);
-                dW[l][1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_hi, x0, dW[l][1][0], 0, 0, 0);
-                dW[l][1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_hi, x1, dW[l][1][1], 0, 0, 0);
-            }
+            for (int kt = 0; kt < KT; kt++) dW[0][kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_lo, o.x[u][kt], dW[0][kt], 0, 0, 0);
+#pragma unroll
+            for (int kt = 0; kt < KT; kt++) dW[1][kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_hi, o.x[u][kt], dW[1][kt], 0, 0, 0);
         }
     };
     if (g_begin < g_end) {
-        // single rotation (compute(cur); cur = nxt): the two-phase form (A/B alternating in one body) made the register
-        // allocator spill a whole operand buffer to scratch
         Operands cur, nxt;
         load(cur, g_begin);
         for (int g0 = g_begin; g0 < g_end; g0 += 2 * UNR) {
@@ -316,69 +305,201 @@ deform_bwd_dw_kernel(MlpDev m, int P, int chunk, const float* __restrict__ feat,
             cur = nxt;
         }
     }
-    // Combine the four waves in LDS, then one float atomic per weight per workgroup.  The waves take TURNS on the shared
-    // tile with plain read-add-write instead of LDS float atomics: ds_add_f32 runs at roughly 170 cycles per wave
-    // instruction here, and 16 waves per CU each issuing 66 of them kept the CU's LDS busy for ~80 us -- more than the whole
-    // MFMA loop (ablation: loop only 77 us, reduction only 88 us with every global atomic skipped, together 145 us).
-    float* R = lds;
+    // the four waves take turns on the shared tile with plain read-add-write, then one float atomic per weight per workgroup
     const int wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int l = 0; l < NL; l++) {
-        const int L = L0 + l;
-        // bias: the two lane halves hold different K slots of the same output feature
-        const float b_lo = db[l][0] + __shfl_xor(db[l][0], 32), b_hi = db[l][1] + __shfl_xor(db[l][1], 32);
+    const float b_lo = db[0] + __shfl_xor(db[0], 32), b_hi = db[1] + __shfl_xor(db[1], 32);
 #pragma unroll 1
-        for (int turn = 0; turn < 4; turn++) {
-            __syncthreads();
-            if (wv == turn) {
+    for (int turn = 0; turn < 4; turn++) {
+        __syncthreads();
+        if (wv == turn) {
 #pragma unroll
-                for (int mt = 0; mt < 2; mt++)
+            for (int mt = 0; mt < 2; mt++)
 #pragma unroll
-                    for (int kt = 0; kt < 2; kt++)
+                for (int kt = 0; kt < KT; kt++)
 #pragma unroll
-                        for (int r = 0; r < 16; r++) {     // tile row = out feature 32mt+fmap(r,h), column = in feature 32kt+col
-                            float* a = &R[(32 * mt + fmap(r, h)) * kHid + 32 * kt + col];
-                            *a = (turn == 0 ? 0.f : *a) + dW[l][mt][kt][r];
-                        }
-                if (h == 0) {
-                    float* a = &R[kHid * kHid + col];
-                    a[0] = (turn == 0 ? 0.f : a[0]) + b_lo;
-                    a[32] = (turn == 0 ? 0.f : a[32]) + b_hi;
-                }
+                    for (int r = 0; r < 16; r++) {     // tile row = out feature 32mt+fmap(r,h), column = in feature 32kt+col
+                        float* a = &R[(32 * mt + fmap(r, h)) * kIn + 32 * kt + col];
+                        *a = (turn == 0 ? 0.f : *a) + dW[mt][kt][r];
+                    }
+            if (h == 0) {
+                float* a = &R[kHid * kIn + col];
+                a[0] = (turn == 0 ? 0.f : a[0]) + b_lo;
+                a[32] = (turn == 0 ? 0.f : a[32]) + b_hi;
             }
         }
-        __syncthreads();
-        float* dst = L == 0 ? m.dW0 : m.dW1[L - 1];
-        float* dbs = L == 0 ? m.db0 : m.db1[L - 1];
-        for (int i = threadIdx.x; i < kHid * kHid; i += 256) {
-            const float v = R[i];
-            if (v != 0.f) atomicAdd(&dst[i], v);
-        }
-        if (threadIdx.x < kHid) {
-            const float v = R[kHid * kHid + threadIdx.x];
-            if (v != 0.f) atomicAdd(&dbs[threadIdx.x], v);
-        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kHid * kIn; i += 256) {
+        const float v = R[i];
+        if (v != 0.f) atomicAdd(&dst[i], v);
+    }
+    if (threadIdx.x < kHid) {
+        const float v = R[kHid * kIn + threadIdx.x];
+        if (v != 0.f) atomicAdd(&dbs[threadIdx.x], v);
     }
 }
 
-}  // namespace
-
-extern "C" int mom_deform_forward(const MomDeformMLP* w, int P, const float* feat, const float* xyz, const float* scaling,
-                                  const float* rotation, const float* scene_flow, float flow_coef, float* pts, float* scales,
-                                  float* rots, float* a0_save, mom_stream_t stream)
+// (B) weight gradients: dW_L[o][i] = sum_g dH_L[g][o] X_L[g][i], db_L[o] = sum_g dH_L[g][o];  X_0 = feat, X_1..3 = a0
+//
+// The kernel streams dwords and is bound by how many cache misses a CU keeps in flight, not by the matrix pipe (SQ counters
+// with all four layers in one wave: MFMA busy 30 % of the time, the rest issue stalls on VMEM).  So a wave takes ONE layer
+// of its range of Gaussians: 64 accumulators, four waves per SIMD, four times the loads in flight of the form with all four
+// layers (256 accumulators, one wave per SIMD); measured, dx + dW: 344 / 339 / 326 us for 4 / 2 / 1 layers per wave.  dH is
+// still read exactly once overall; a0 is read once per layer 1..3.
+//
+// KT = 2 is the body below.  KT = 1 runs dw_layer above: layer 0 (dW0 [64,32], half the MFMAs of the others) at one K tile, layers
+// 1..3 at two.  The two forms stay side by side because the body does not survive being called: as a __forceinline__ function or
+// a generic lambda, at KT = 2, it compiles to 895 instructions where it has 991 here -- the same loop, another reduction (LDS stores
+// merged in pairs, half the exec-mask regions) -- the way its NL comment warns, and the timings of this file are of these 991.
+template <int KT>
+__global__ void __launch_bounds__(256)
+deform_bwd_dw_kernel(MlpDev m, int P, int chunk, const float* __restrict__ feat, const float* __restrict__ a0g,
+                     const float* __restrict__ dH, int ny)
 {
-    return mom_deform_forward_activated(w, P, feat, xyz, scaling, rotation, scene_flow, flow_coef, pts, scales, rots, a0_save, nullptr,
-                                        nullptr, nullptr, nullptr, stream);
+    extern __shared__ float lds[];                     // [64][64] reduction scratch + [64] bias
+    if constexpr (KT == 2) {
+        constexpr int NL = 1;                              // layers per wave; ny = 4 / NL layer groups (written out for NL = 1 the same
+                                                           // source compiles to another schedule, so the loops over NL stay)
+        const int lane = threadIdx.x & 63, col = lane & 31, h = lane >> 5;
+        // One-dimensional grid of (ranges of Gaussians) x (ny layer groups), numbered so that the ny workgroups of one range are 8
+        // ids apart inside a run of 8 ny ids: workgroup ids go to the eight XCDs in turn, so the layer groups of a range land on the
+        // SAME XCD at about the same time, and the rows of a0 the three head layers all read come out of that XCD's L2 twice out of
+        // three times (a two-dimensional grid ran all ranges of layer 0, then all of layer 1, ...: three trips to memory).
+        const int lin = blockIdx.x, run = 8 * ny;
+        const int bx = (lin / run) * 8 + (lin % run) % 8, by = (lin % run) / 8;
+        const int wave = (bx * 256 + threadIdx.x) >> 6;
+        const int L0 = NL * by;                            // first layer of this workgroup
+        const size_t PH = (size_t)P * kHid;
+        const int g_begin = wave * chunk, g_end = min(P, g_begin + chunk);   // chunk is even
+
+        f32x16 dW[NL][2][2];
+        float db[NL][2];
+#pragma unroll
+        for (int l = 0; l < NL; l++) {
+            zero_tile(dW[l][0]);
+            zero_tile(dW[l][1]);
+            db[l][0] = db[l][1] = 0.f;
+        }
+        // Operand loads are double buffered by hand.  A trip is UNR K-steps (2 gaussians each); the loads of trip t+1 are issued
+        // before the MFMAs of trip t.  They are issued UNCONDITIONALLY (rows past the end are clamped and masked by `ok`): vmcnt
+        // retires in order, and a prefetch behind a branch would make the compiler wait for it too.
+        constexpr int UNR = 4;
+        struct Operands {
+            float x[UNR][2], da[UNR][NL][2];
+            bool ok[UNR];
+        };
+        const float* __restrict__ xa = L0 == 0 ? feat : a0g;      // layer L reads X = feat (L == 0) or a0 (L >= 1)
+        auto load = [&](Operands& o, int g0) {
+#pragma unroll
+            for (int u = 0; u < UNR; u++) {
+                const int g = g0 + 2 * u + h;               // K slot of this lane half
+                const bool ok = g < g_end;
+                o.ok[u] = ok;
+                const size_t row = (size_t)(ok ? g : g_begin) * kHid;
+#pragma unroll
+                for (int kt = 0; kt < 2; kt++) o.x[u][kt] = xa[row + 32 * kt + col];
+#pragma unroll
+                for (int l = 0; l < NL; l++) {
+                    const float* __restrict__ d = dH + (size_t)(L0 + l) * PH + row;
+                    o.da[u][l][0] = d[col];
+                    o.da[u][l][1] = d[32 + col];
+                }
+            }
+        };
+        auto compute = [&](const Operands& o) {
+#pragma unroll
+            for (int u = 0; u < UNR; u++) {
+#pragma unroll
+                for (int l = 0; l < NL; l++) {
+                    const float a_lo = o.ok[u] ? o.da[u][l][0] : 0.f, a_hi = o.ok[u] ? o.da[u][l][1] : 0.f;
+                    db[l][0] += a_lo;
+                    db[l][1] += a_hi;
+                    const float x0 = o.x[u][0], x1 = o.x[u][1];
+                    dW[l][0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_lo, x0, dW[l][0][0], 0, 0, 0);
+                    dW[l][0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_lo, x1, dW[l][0][1], 0, 0, 0);
+                    dW[l][1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_hi, x0, dW[l][1][0], 0, 0, 0);
+                    dW[l][1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_hi, x1, dW[l][1][1], 0, 0, 0);
+                }
+            }
+        };
+        if (g_begin < g_end) {
+            // single rotation (compute(cur); cur = nxt): the two-phase form (A/B alternating in one body) made the register
+            // allocator spill a whole operand buffer to scratch
+            Operands cur, nxt;
+            load(cur, g_begin);
+            for (int g0 = g_begin; g0 < g_end; g0 += 2 * UNR) {
+                load(nxt, g0 + 2 * UNR);
+                __builtin_amdgcn_sched_barrier(0);
+                compute(cur);
+                __builtin_amdgcn_sched_barrier(0);
+                cur = nxt;
+            }
+        }
+        // Combine the four waves in LDS, then one float atomic per weight per workgroup.  The waves take TURNS on the shared
+        // tile with plain read-add-write instead of LDS float atomics: ds_add_f32 runs at roughly 170 cycles per wave
+        // instruction here, and 16 waves per CU each issuing 66 of them kept the CU's LDS busy for ~80 us -- more than the whole
+        // MFMA loop (ablation: loop only 77 us, reduction only 88 us with every global atomic skipped, together 145 us).
+        float* R = lds;
+        const int wv = threadIdx.x >> 6;
+#pragma unroll
+        for (int l = 0; l < NL; l++) {
+            const int L = L0 + l;
+            // bias: the two lane halves hold different K slots of the same output feature
+            const float b_lo = db[l][0] + __shfl_xor(db[l][0], 32), b_hi = db[l][1] + __shfl_xor(db[l][1], 32);
+#pragma unroll 1
+            for (int turn = 0; turn < 4; turn++) {
+                __syncthreads();
+                if (wv == turn) {
+#pragma unroll
+                    for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+                        for (int kt = 0; kt < 2; kt++)
+#pragma unroll
+                            for (int r = 0; r < 16; r++) {     // tile row = out feature 32mt+fmap(r,h), column = in feature 32kt+col
+                                float* a = &R[(32 * mt + fmap(r, h)) * kHid + 32 * kt + col];
+                                *a = (turn == 0 ? 0.f : *a) + dW[l][mt][kt][r];
+                            }
+                    if (h == 0) {
+                        float* a = &R[kHid * kHid + col];
+                        a[0] = (turn == 0 ? 0.f : a[0]) + b_lo;
+                        a[32] = (turn == 0 ? 0.f : a[32]) + b_hi;
+                    }
+                }
+            }
+            __syncthreads();
+            float* dst = L == 0 ? m.dW0 : m.dW1[L - 1];
+            float* dbs = L == 0 ? m.db0 : m.db1[L - 1];
+            for (int i = threadIdx.x; i < kHid * kHid; i += 256) {
+                const float v = R[i];
+                if (v != 0.f) atomicAdd(&dst[i], v);
+            }
+            if (threadIdx.x < kHid) {
+                const float v = R[kHid * kHid + threadIdx.x];
+                if (v != 0.f) atomicAdd(&dbs[threadIdx.x], v);
+            }
+        }
+    } else {
+        const int lin = blockIdx.x, run = 8 * ny;
+        const int bx = (lin / run) * 8 + (lin % run) % 8, L = (lin % run) / 8;      // range of Gaussians, layer
+        const int wave = (bx * 256 + threadIdx.x) >> 6;
+        const int g_begin = wave * chunk, g_end = min(P, g_begin + chunk);   // chunk is even
+        const float* __restrict__ dHl = dH + (size_t)L * P * kHid;
+        if (L == 0)
+            dw_layer<1>(feat, dHl, g_begin, g_end, m.dW0, m.db0, lds);
+        else
+            dw_layer<2>(a0g, dHl, g_begin, g_end, m.dW1[L - 1], m.db1[L - 1], lds);
+    }
 }
 
-extern "C" int mom_deform_forward_activated(const MomDeformMLP* w, int P, const float* feat, const float* xyz, const float* scaling,
-                                            const float* rotation, const float* scene_flow, float flow_coef, float* pts, float* scales,
-                                            float* rots, float* a0_save, const float* opacity_raw, float* scales_act, float* rots_act,
-                                            float* opacity_act, mom_stream_t stream)
+template <int KT>
+int forward(const MomDeformMLP* w, int P, const float* feat, const float* xyz, const float* scaling, const float* rotation,
+            const float* scene_flow, float flow_coef, float* pts, float* scales, float* rots, float* a0_save, const float* opacity_raw,
+            float* scales_act, float* rots_act, float* opacity_act, mom_stream_t stream)
 {
     if (P < 0) return MOM_EINVAL;
     if (P == 0) return MOM_OK;
     if (!feat || !xyz || !scaling || !rotation || !scene_flow || !pts || !scales || !rots) return MOM_EINVAL;
+    if ((opacity_act != nullptr) != (opacity_raw != nullptr)) return MOM_EINVAL;
     MlpDev d;
     int rc = fill_dev(w, &d);
     if (rc) return rc;
@@ -390,62 +511,54 @@ extern "C" int mom_deform_forward_activated(const MomDeformMLP* w, int P, const 
     // workgroup, 39 -> 21 us at 5 k Gaussians) instead of filling sixteen waves of a few workgroups
     const int blocks = tiles < 256 ? tiles : 256;
     const size_t lds_bytes = sizeof(float) * kLFwdTotal;
-    if (!mom_lds_limit<deform_fwd_kernel>(lds_bytes)) return MOM_ELAUNCH;
-    if ((opacity_act != nullptr) != (opacity_raw != nullptr)) return MOM_EINVAL;
+    if (!mom_lds_limit<deform_fwd_kernel<KT>>(lds_bytes)) return MOM_ELAUNCH;
     const ActOut act = {scales_act, rots_act, opacity_act, opacity_raw};
     MomProfScope ps(MOM_P_MLP_FWD, (hipStream_t)stream);
-    hipLaunchKernelGGL(deform_fwd_kernel, dim3(blocks), dim3(block), lds_bytes, (hipStream_t)stream, d, P, tiles, feat, xyz, scaling,
+    hipLaunchKernelGGL(deform_fwd_kernel<KT>, dim3(blocks), dim3(block), lds_bytes, (hipStream_t)stream, d, P, tiles, feat, xyz, scaling,
                        rotation, scene_flow, flow_coef, pts, scales, rots, a0_save, act);
     return hipGetLastError() == hipSuccess ? MOM_OK : MOM_ELAUNCH;
 }
 
-int mom_launch_deform_bwd_b3f(const MomDeformMLP* w, int P, const float* feat, const float* a0, const float* dpts, const float* dscales,
-                              const float* drots, float* dfeat, void* scratch, hipStream_t s, hipStream_t dw_stream);      // deform_bwd_b3.hip
-size_t mom_deform_bwd_b3f_scratch_bytes(void);
-
-// the larger of what the two forms need: the two-kernel form's four [P,64] matrices, the one-kernel form's per-workgroup partial sums
-extern "C" size_t mom_deform_backward_scratch_bytes(int P)
+// MOM_MLP_BWD (read per call so that tests can compare the forms): unset or "b3" -- the one-kernel backward on the bf16 pipe
+// with role-specialised waves (deform_bwd_b3.hip; dfeat is complete on `stream`, the small reduction that completes the weight
+// gradients runs on dw_stream); "split" -- the two f32 kernels above (dx on `stream`, dW on `dw_stream`).  Empty counts as
+// unset, as for the integer switches; anything else is refused: a misspelt value must not quietly select a form.
+enum BwdForm { kBwdB3, kBwdSplit, kBwdRefused };
+BwdForm bwd_form()
 {
-    const size_t a = (size_t)4 * (size_t)(P > 0 ? P : 1) * kHid * sizeof(float), b = mom_deform_bwd_b3f_scratch_bytes();
-    return a > b ? a : b;
+    const char* e = getenv("MOM_MLP_BWD");
+    if (!e || !*e || !strcmp(e, "b3")) return kBwdB3;
+    return strcmp(e, "split") ? kBwdRefused : kBwdSplit;
 }
 
-extern "C" int mom_deform_backward(const MomDeformMLP* w, int P, const float* feat, const float* a0, const float* dpts,
-                                   const float* dscales, const float* drots, float* dfeat, void* scratch, mom_stream_t stream)
-{
-    return mom_deform_backward_split(w, P, feat, a0, dpts, dscales, drots, dfeat, scratch, stream, stream);
-}
-
-extern "C" int mom_deform_backward_split(const MomDeformMLP* w, int P, const float* feat, const float* a0, const float* dpts,
-                                         const float* dscales, const float* drots, float* dfeat, void* scratch, mom_stream_t stream,
-                                         mom_stream_t dw_stream)
+template <int KT>
+int backward(const MomDeformMLP* w, int P, const float* feat, const float* a0, const float* dpts, const float* dscales,
+             const float* drots, float* dfeat, void* scratch, mom_stream_t stream, mom_stream_t dw_stream)
 {
     if (P < 0) return MOM_EINVAL;
     if (P == 0) return MOM_OK;
     if (!feat || !a0 || !dpts || !dscales || !drots || !dfeat || !scratch) return MOM_EINVAL;
-    // MOM_MLP_BWD (read per call so that tests can compare the forms): unset or "b3" -- the one-kernel backward on the bf16 pipe
-    // with role-specialised waves (deform_bwd_b3.hip; dfeat is complete on `stream`, the small reduction that completes the weight
-    // gradients runs on dw_stream); "split" -- the two f32 kernels below (dx on `stream`, dW on `dw_stream`).  Empty counts as
-    // unset, as for the integer switches; anything else is refused: a misspelt value must not quietly select a form.
-    const char* e = getenv("MOM_MLP_BWD");
-    if (!e || !*e || !strcmp(e, "b3"))
+    // the bf16 form is 64 features only: at 32 every value that is valid there runs the f32 kernels, and a value that is refused
+    // there is refused here
+    const BwdForm form = bwd_form();
+    if (form == kBwdRefused) return MOM_EINVAL;
+    if (KT == 2 && form == kBwdB3)
         return mom_launch_deform_bwd_b3f(w, P, feat, a0, dpts, dscales, drots, dfeat, scratch, (hipStream_t)stream, (hipStream_t)dw_stream);
-    if (strcmp(e, "split")) return MOM_EINVAL;
     MlpDev d;
     int rc = fill_dev(w, &d);
     if (rc) return rc;
     if (!d.dW0 || !d.db0) return MOM_EINVAL;
     for (int i = 0; i < 3; i++)
         if (!d.dW1[i] || !d.db1[i] || !d.dW2[i] || !d.db2[i]) return MOM_EINVAL;
-    float* dH = (float*)scratch;
+    float* dH = (float*)scratch;                       // [4][P][64]: mom_deform_backward_scratch_bytes(P) holds it
     const int tiles = (P + 31) / 32;
     int blocks = tiles < 256 ? tiles : 256;             // persistent: one workgroup per CU; a small problem still uses every CU
     const size_t lds_a = sizeof(float) * kLBwdTotal;
     const size_t lds_b = sizeof(float) * (kHid * kHid + kHid);
-    if (!mom_lds_limit<deform_bwd_dx_kernel>(lds_a)) return MOM_ELAUNCH;
+    if (!mom_lds_limit<deform_bwd_dx_kernel<KT>>(lds_a)) return MOM_ELAUNCH;
     MomProfScope ps(MOM_P_MLP_BWD, (hipStream_t)stream);
-    hipLaunchKernelGGL(deform_bwd_dx_kernel, dim3(blocks), dim3(64 * kDxWaves), lds_a, (hipStream_t)stream, d, P, tiles, a0, dpts, dscales,
-                       drots, dfeat, dH);
+    hipLaunchKernelGGL(deform_bwd_dx_kernel<KT>, dim3(blocks), dim3(64 * kDxWaves), lds_a, (hipStream_t)stream, d, P, tiles, a0, dpts,
+                       dscales, drots, dfeat, dH);
     if (hipGetLastError() != hipSuccess) return MOM_ELAUNCH;
     hipStream_t ws = (hipStream_t)dw_stream;
     if (ws != (hipStream_t)stream) {
@@ -461,7 +574,78 @@ extern "C" int mom_deform_backward_split(const MomDeformMLP* w, int P, const flo
     int chunk = (P + waves - 1) / waves;
     chunk += chunk & 1;
     // one-dimensional grid: the kernel deals (range, layer) to the XCDs itself
-    hipLaunchKernelGGL(deform_bwd_dw_kernel, dim3((waves / 4) * layers), dim3(256), lds_b, ws, d, P, chunk, feat, a0, dH, layers);
+    hipLaunchKernelGGL(deform_bwd_dw_kernel<KT>, dim3((waves / 4) * layers), dim3(256), lds_b, ws, d, P, chunk, feat, a0, dH, layers);
     return hipGetLastError() == hipSuccess ? MOM_OK : MOM_ELAUNCH;
 }
 
+}  // namespace
+
+// The entry points with in_features (include/mom4d.h) are the ones that launch: 64 and 32 are the trunks there are.
+extern "C" int mom_deform_forward_activated_n(const MomDeformMLP* w, int P, int in_features, const float* feat, const float* xyz,
+                                              const float* scaling, const float* rotation, const float* scene_flow, float flow_coef,
+                                              float* pts, float* scales, float* rots, float* a0_save, const float* opacity_raw,
+                                              float* scales_act, float* rots_act, float* opacity_act, mom_stream_t stream)
+{
+    if (in_features != 64 && in_features != 32) return MOM_EINVAL;
+    return (in_features == 64 ? forward<2> : forward<1>)(w, P, feat, xyz, scaling, rotation, scene_flow, flow_coef, pts, scales, rots,
+                                                         a0_save, opacity_raw, scales_act, rots_act, opacity_act, stream);
+}
+
+extern "C" int mom_deform_backward_split_n(const MomDeformMLP* w, int P, int in_features, const float* feat, const float* a0,
+                                           const float* dpts, const float* dscales, const float* drots, float* dfeat, void* scratch,
+                                           mom_stream_t stream, mom_stream_t dw_stream)
+{
+    if (in_features != 64 && in_features != 32) return MOM_EINVAL;
+    return (in_features == 64 ? backward<2> : backward<1>)(w, P, feat, a0, dpts, dscales, drots, dfeat, scratch, stream, dw_stream);
+}
+
+// the larger of what the two forms need: the two-kernel form's four [P,64] matrices, the one-kernel form's per-workgroup partial sums
+extern "C" size_t mom_deform_backward_scratch_bytes(int P)
+{
+    const size_t a = (size_t)4 * (size_t)(P > 0 ? P : 1) * kHid * sizeof(float), b = mom_deform_bwd_b3f_scratch_bytes();
+    return a > b ? a : b;
+}
+
+extern "C" int mom_deform_forward_n(const MomDeformMLP* w, int P, int in_features, const float* feat, const float* xyz,
+                                    const float* scaling, const float* rotation, const float* scene_flow, float flow_coef, float* pts,
+                                    float* scales, float* rots, float* a0_save, mom_stream_t stream)
+{
+    return mom_deform_forward_activated_n(w, P, in_features, feat, xyz, scaling, rotation, scene_flow, flow_coef, pts, scales, rots,
+                                          a0_save, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int mom_deform_backward_n(const MomDeformMLP* w, int P, int in_features, const float* feat, const float* a0,
+                                     const float* dpts, const float* dscales, const float* drots, float* dfeat, void* scratch,
+                                     mom_stream_t stream)
+{
+    return mom_deform_backward_split_n(w, P, in_features, feat, a0, dpts, dscales, drots, dfeat, scratch, stream, stream);
+}
+
+extern "C" int mom_deform_forward(const MomDeformMLP* w, int P, const float* feat, const float* xyz, const float* scaling,
+                                  const float* rotation, const float* scene_flow, float flow_coef, float* pts, float* scales,
+                                  float* rots, float* a0_save, mom_stream_t stream)
+{
+    return mom_deform_forward_n(w, P, 64, feat, xyz, scaling, rotation, scene_flow, flow_coef, pts, scales, rots, a0_save, stream);
+}
+
+extern "C" int mom_deform_forward_activated(const MomDeformMLP* w, int P, const float* feat, const float* xyz, const float* scaling,
+                                            const float* rotation, const float* scene_flow, float flow_coef, float* pts, float* scales,
+                                            float* rots, float* a0_save, const float* opacity_raw, float* scales_act, float* rots_act,
+                                            float* opacity_act, mom_stream_t stream)
+{
+    return mom_deform_forward_activated_n(w, P, 64, feat, xyz, scaling, rotation, scene_flow, flow_coef, pts, scales, rots, a0_save,
+                                          opacity_raw, scales_act, rots_act, opacity_act, stream);
+}
+
+extern "C" int mom_deform_backward(const MomDeformMLP* w, int P, const float* feat, const float* a0, const float* dpts,
+                                   const float* dscales, const float* drots, float* dfeat, void* scratch, mom_stream_t stream)
+{
+    return mom_deform_backward_n(w, P, 64, feat, a0, dpts, dscales, drots, dfeat, scratch, stream);
+}
+
+extern "C" int mom_deform_backward_split(const MomDeformMLP* w, int P, const float* feat, const float* a0, const float* dpts,
+                                         const float* dscales, const float* drots, float* dfeat, void* scratch, mom_stream_t stream,
+                                         mom_stream_t dw_stream)
+{
+    return mom_deform_backward_split_n(w, P, 64, feat, a0, dpts, dscales, drots, dfeat, scratch, stream, dw_stream);
+}

@@ -318,23 +318,16 @@ def _backward(st, dcolor, ddepth, direct=True):
     gplanes, gmlp, hp, md, in_place = _field_grads(st, f, direct)
     dfeat, scratch = b["dfeat"], b["scratch"]
     # pts = xyz + dx(...): d xyz starts as d pts (already in gxyz); scale / rotation residuals likewise
-    if st.F == 32:
-        # the MLP backward on 32 features (csrc/deform_mlp32.hip), with or without the second stream as below
-        if overlap:
-            N.check(lib.mom_deform_backward_split_n(C.byref(md), P, 32, st.feat.data_ptr(), st.a0.data_ptr(), gxyz.data_ptr(),
-                                                    gsc.data_ptr(), grot.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), s, side),
-                    "deform_bwd")
-        else:
-            N.check(lib.mom_deform_backward_n(C.byref(md), P, 32, st.feat.data_ptr(), st.a0.data_ptr(), gxyz.data_ptr(), gsc.data_ptr(),
-                                              grot.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), s), "deform_bwd")
-    elif overlap:
+    if overlap:
         # with a second stream the MLP backward leaves an eighth of the chip free (for that Adam launch) and its partial-sum
-        # reduction goes there too (csrc/deform_bwd_b3.hip); joined below
-        N.check(lib.mom_deform_backward_split(C.byref(md), P, st.feat.data_ptr(), st.a0.data_ptr(), gxyz.data_ptr(), gsc.data_ptr(),
-                                              grot.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), s, side), "deform_bwd")
+        # reduction goes there too (csrc/deform_bwd_b3.hip; on 32 features: the weight-gradient kernel of csrc/deform_mlp.hip);
+        # joined below
+        N.check(lib.mom_deform_backward_split_n(C.byref(md), P, st.F, st.feat.data_ptr(), st.a0.data_ptr(), gxyz.data_ptr(),
+                                                gsc.data_ptr(), grot.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), s, side),
+                "deform_bwd")
     else:
-        N.check(lib.mom_deform_backward(C.byref(md), P, st.feat.data_ptr(), st.a0.data_ptr(), gxyz.data_ptr(), gsc.data_ptr(),
-                                        grot.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), s), "deform_bwd")
+        N.check(lib.mom_deform_backward_n(C.byref(md), P, st.F, st.feat.data_ptr(), st.a0.data_ptr(), gxyz.data_ptr(), gsc.data_ptr(),
+                                          grot.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), s), "deform_bwd")
     ops.wait_reg_pending(dev)          # the regulariser's gradient kernel (second stream) adds into the plane gradients too
     porders = st.porders
     hscratch = None

@@ -743,14 +743,9 @@ class FusedStep(_Step):
                 launch_early_cam()
                 early_cam = None
             if sl is None:
-                if self.F == 32:
-                    N.check(lib.mom_deform_backward_split_n(C.byref(md), P, 32, self.feat.data_ptr(), self.a0.data_ptr(), d_pts.data_ptr(),
-                                                            d_sc.data_ptr(), d_rot.data_ptr(), self.dfeat.data_ptr(),
-                                                            self.dh_scratch.data_ptr(), s, side), "deform_bwd")
-                else:
-                    N.check(lib.mom_deform_backward_split(C.byref(md), P, self.feat.data_ptr(), self.a0.data_ptr(), d_pts.data_ptr(),
-                                                          d_sc.data_ptr(), d_rot.data_ptr(), self.dfeat.data_ptr(),
-                                                          self.dh_scratch.data_ptr(), s, side), "deform_bwd")
+                N.check(lib.mom_deform_backward_split_n(C.byref(md), P, self.F, self.feat.data_ptr(), self.a0.data_ptr(), d_pts.data_ptr(),
+                                                        d_sc.data_ptr(), d_rot.data_ptr(), self.dfeat.data_ptr(),
+                                                        self.dh_scratch.data_ptr(), s, side), "deform_bwd")
                 if porders is not None:
                     self._hex_scratch_for(hp, P, dev)
                 if porders is not None and lines_kept:      # the forward's time lines are still in the field scratch

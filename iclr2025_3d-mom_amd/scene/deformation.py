@@ -89,7 +89,7 @@ class Deformation(nn.Module):
 
     def _mlp_fusable(self):
         """The fused MLP op (ops.deform_mlp) applies: the _fusable() model, or the same network on 32 features from exactly two
-        levels of 16 channels (dnerf/eulerian_150_16; csrc/deform_mlp32.hip).  Wider than _fusable() on purpose: it is
+        levels of 16 channels (dnerf/eulerian_150_16; csrc/deform_mlp.hip).  Wider than _fusable() on purpose: it is
         what the op-by-op path asks, whatever the planes' resolutions.  The fused step, no-grad render() and the one-node autograd
         path take 16-channel fields through _field16_fusable(), which adds the field kernel's resolution limit
         (fused_step.step_features, fused_autograd.node_width)."""

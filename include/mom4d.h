@@ -537,10 +537,10 @@ int mom_deform_backward(const MomDeformMLP* w, int P, const float* feat, const f
 int mom_deform_backward_split(const MomDeformMLP* w, int P, const float* feat, const float* a0, const float* dpts,
                               const float* dscales, const float* drots, float* dfeat, void* scratch, mom_stream_t stream,
                               mom_stream_t dw_stream);
-/* The four calls above for a trunk of `in_features` inputs (csrc/deform_mlp32.hip).  MomDeformMLP keeps its layout; W0 and dW0 point
+/* The four calls above for a trunk of `in_features` inputs (csrc/deform_mlp.hip: one set of kernel templates for both widths).  MomDeformMLP keeps its layout; W0 and dW0 point
  * at [64,in_features] tensors, feat and dfeat are [P,in_features], everything else (a0 [P,64], the heads, the scratch size) is as above.
- *   in_features == 64: exactly the call without _n.
- *   in_features == 32 (two HexPlane levels of 16 channels, dnerf/eulerian_150_16): fp32 kernels of their own.  The backward is the
+ *   in_features == 64: exactly the call without _n (which forwards here).
+ *   in_features == 32 (two HexPlane levels of 16 channels, dnerf/eulerian_150_16): the fp32 kernels at that width.  The backward is the
  *     two-kernel f32 form whatever MOM_MLP_BWD says -- unset, empty, "b3" or "split"; there is no bf16 one-kernel form for this
  *     shape -- with the stream contract of that form; any other value is MOM_EINVAL as above.
  *   anything else: MOM_EINVAL, before anything is launched. */

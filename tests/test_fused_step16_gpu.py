@@ -1,7 +1,7 @@
 """The fused training step (fused_step.FusedStep16, Trainer(fused=True)'s choice through fused_step.fine_step) on a model of the dnerf/eulerian_150_16 shape -- two HexPlane levels of 16-channel
 planes, 32 features into the shipped network -- against the render() + loss.backward() path of the same model and against the CPU
 oracle.  The step writes no kernel of its own: the one-launch field forward (csrc/deform_field16.hip), the MLP backward on 32
-features (csrc/deform_mlp32.hip) and the 16-channel HexPlane backward (csrc/hexplane.hip) in the launch sequence of the 32 x 2
+features (csrc/deform_mlp.hip) and the 16-channel HexPlane backward (csrc/hexplane.hip) in the launch sequence of the 32 x 2
 step.  Tolerances are those the suite already holds the 32 x 2 step to for the same comparisons (named at each test): both paths
 run the same kernels here too and differ in the order of their float atomics.  (The step activates the field's raw outputs with
 torch's exp / normalize / sigmoid, as the op-by-op path does: with the kernel's own activated outputs the gradients of the tiny

@@ -1,4 +1,4 @@
-"""Host side of the fused deformation MLP with a 32-feature trunk (csrc/deform_mlp32.hip; dnerf/eulerian_150_16: two HexPlane
+"""Host side of the fused deformation MLP with a 32-feature trunk (csrc/deform_mlp.hip at KT = 1; dnerf/eulerian_150_16: two HexPlane
 levels of 16 channels, net_width 64, defor_depth 0): which models Deformation routes to it, the *_n entry points of the C ABI and
 what they and ops.DeformMLPFunction refuse.  No GPU needed: every refused call is refused before anything is launched."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""The fused deformation MLP with a 32-feature trunk (csrc/deform_mlp32.hip; dnerf/eulerian_150_16: two HexPlane levels of
+"""The fused deformation MLP with a 32-feature trunk (csrc/deform_mlp.hip at KT = 1; dnerf/eulerian_150_16: two HexPlane levels of
 16 channels) on the GPU: against oracle.torch_ref.deform_mlp on the CPU, against the 64-feature kernels on the same features
 padded with zero columns (the same k-ascending fp32 chain: equal bits), its activated and two-stream forms, its refusals, the
 routing of a model of that shape, and determinism.
@@ -125,6 +125,59 @@ def test_same_bits_as_the_64_feature_kernels_on_zero_padded_features(P, monkeypa
     for i, (x, y) in enumerate(zip(g32, g64)):      # the same terms through float atomics in another order
         rel = float((x.double() - y.double()).norm() / (y.double().norm() + 1e-30))
         assert rel <= 2e-3, (i, rel)
+
+
+@pytest.mark.parametrize("P", [1, 33, 65])
+def test_the_n_entry_points_at_64_features_are_the_plain_entry_points(P, monkeypatch):
+    """in_features = 64 through the _n entry points and the entry points without _n run the same kernels: every forward output,
+    relu(h0), the activated copies and (f32 backward) dfeat are equal bit for bit; the weight gradients end in float atomics
+    across workgroups, so they are held to the two-stream test's tolerance, on one stream and (P = 65) with a second one."""
+    monkeypatch.setenv("MOM_MLP_BWD", "split")
+    g = torch.Generator().manual_seed(200 + P)
+    mk = lambda *s: (torch.randn(*s, generator=g) * 0.3).cuda()
+    params = _params(mk, 64)
+    feat, xyz, scal, rot, flow, opac = mk(P, 64) * 3, mk(P, 3), mk(P, 3), mk(P, 4), mk(P, 3), mk(P, 1)
+    dpts, dsc, drot = mk(P, 3), mk(P, 3), mk(P, 4)
+    lib, s = N.lib(), N.current_stream()
+    side = torch.cuda.Stream()
+    scratch = torch.empty(lib.mom_deform_backward_scratch_bytes(P), dtype=torch.uint8, device="cuda")
+    e = lambda *sh: torch.full(sh, float("nan"), device="cuda")
+
+    def run(n, second):
+        w = (64,) if n else ()           # in_features follows P in the _n forms
+        grads = [torch.zeros_like(p) for p in params]
+        d = ops.DeformMLPFunction._desc(params, grads)
+        pts, sc_d, rot_d, a0 = e(P, 3), e(P, 3), e(P, 4), e(P, 64)
+        fwd = lib.mom_deform_forward_n if n else lib.mom_deform_forward
+        N.check(fwd(C.byref(d), P, *w, feat.data_ptr(), xyz.data_ptr(), scal.data_ptr(), rot.data_ptr(), flow.data_ptr(), 0.7,
+                    pts.data_ptr(), sc_d.data_ptr(), rot_d.data_ptr(), a0.data_ptr(), s), "fwd")
+        pts2, sc_d2, rot_d2, sc, rt, op = e(P, 3), e(P, 3), e(P, 4), e(P, 3), e(P, 4), e(P, 1)
+        act = lib.mom_deform_forward_activated_n if n else lib.mom_deform_forward_activated
+        N.check(act(C.byref(d), P, *w, feat.data_ptr(), xyz.data_ptr(), scal.data_ptr(), rot.data_ptr(), flow.data_ptr(), 0.7,
+                    pts2.data_ptr(), sc_d2.data_ptr(), rot_d2.data_ptr(), None, opac.data_ptr(), sc.data_ptr(), rt.data_ptr(),
+                    op.data_ptr(), s), "fwd_act")
+        dfeat = e(P, 64)
+        if second:
+            bwd = lib.mom_deform_backward_split_n if n else lib.mom_deform_backward_split
+            N.check(bwd(C.byref(d), P, *w, feat.data_ptr(), a0.data_ptr(), dpts.data_ptr(), dsc.data_ptr(), drot.data_ptr(),
+                        dfeat.data_ptr(), scratch.data_ptr(), s, side.cuda_stream), "bwd_split")
+            torch.cuda.current_stream().wait_stream(side)      # the caller's join
+        else:
+            bwd = lib.mom_deform_backward_n if n else lib.mom_deform_backward
+            N.check(bwd(C.byref(d), P, *w, feat.data_ptr(), a0.data_ptr(), dpts.data_ptr(), dsc.data_ptr(), drot.data_ptr(),
+                        dfeat.data_ptr(), scratch.data_ptr(), s), "bwd")
+        torch.cuda.synchronize()
+        return (pts, sc_d, rot_d, a0, pts2, sc_d2, rot_d2, sc, rt, op, dfeat), grads
+
+    for second in ((False, True) if P == 65 else (False,)):
+        o_n, g_n = run(True, second)
+        o_p, g_p = run(False, second)
+        for i, (a, b) in enumerate(zip(o_n, o_p)):
+            assert bool(torch.isfinite(a).all()) and torch.equal(a, b), (second, i)
+        assert float(o_n[-1].abs().max()) > 0
+        for i, (a, b) in enumerate(zip(g_n, g_p)):         # float atomics: same terms, possibly another order
+            assert float(a.abs().max()) > 0, (second, i)
+            assert float((a - b).abs().max()) <= 1e-5 * max(1.0, float(a.abs().max())), (second, i)
 
 
 @pytest.mark.parametrize("P", [1, 65, 1000])

@@ -1,5 +1,5 @@
-"""The deformation MLP of a 32-feature trunk (csrc/deform_mlp32.hip; dnerf/eulerian_150_16: two HexPlane levels of 16 channels,
-net_width 64, defor_depth 0) beside the 64-feature f32 kernels (csrc/deform_mlp.hip, MOM_MLP_BWD=split) and beside the nn.Linear
+"""The deformation MLP of a 32-feature trunk (csrc/deform_mlp.hip at KT = 1; dnerf/eulerian_150_16: two HexPlane levels of 16 channels,
+net_width 64, defor_depth 0) beside the 64-feature f32 kernels (the same templates at KT = 2, MOM_MLP_BWD=split) and beside the nn.Linear
 sequence Deformation.forward_dynamic ran for this model before the 32-feature kernels existed, on the same tensors: 200 000
 Gaussians, forward alone and forward + backward.
 
