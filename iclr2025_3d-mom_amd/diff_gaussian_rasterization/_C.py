@@ -15,15 +15,28 @@ Differences a caller can observe, all documented in INTEGRATION.md:
 from __future__ import annotations
 
 import ctypes as C
+import time
+from collections import deque
 
 import torch
 
 from .. import _native as N
 
-from collections import deque
-
-_state = {"mode": "exact", "cap_hint": 0, "last_R": None, "flag": None, "pending": deque(), "keep_all_tiles": False,
-          "serial": 0, "verified": 0}
+# The rasterizer module's whole state.  Every key is here; nothing adds one later.
+_state = {
+    "mode": "exact",           # set_sync_mode(); train.py and render.py switch it to "exact" around a replay / a repair
+    "cap_hint": 0,             # async binning capacity: set_sync_mode(), raster_forward (1.5 x an earlier count), _check_overflow (doubles)
+    "last_R": None,            # the pinned count word of the latest forward: raster_forward
+    "flag": None,              # the sticky device overflow word: overflow_flag() makes it, _check_overflow clears it
+    "pending": deque(),        # (ring index, count word, serial) of async forwards not yet verified: raster_forward / _check_overflow
+    "keep_all_tiles": False,   # set_keep_all_tiles()
+    "serial": 0,               # number of the latest async forward: raster_forward
+    "verified": 0,             # every async forward up to this serial is known to be complete: _check_overflow
+    "exact_cap": 0,            # exact mode's speculative binning capacity (0: none yet): exact_render
+    "pin_ring": None,          # pinned count words and the next one to hand out: pinned_word() (made on first use -- importing
+    "pin_next": 0,             #   this module must not initialise the GPU)
+    "post_ring": None,         # PostRing of the async forwards' status words: raster_forward (made on first use, likewise)
+}
 _FLAG_LAG = 4
 
 
@@ -43,10 +56,9 @@ _PIN_RING = 256
 def pinned_word():
     """A pinned int32 word from a ring (page-locked allocations are slow and can stall the device: none per call).  A word is
     handed out again 256 calls later -- far beyond the few calls for which the rasterizer state refers to it."""
-    ring = _state.get("pin_ring")
+    ring = _state["pin_ring"]
     if ring is None:
         ring = _state["pin_ring"] = torch.zeros(_PIN_RING, dtype=torch.int32).pin_memory()
-        _state["pin_next"] = 0
     i = _state["pin_next"]
     _state["pin_next"] = (i + 1) % _PIN_RING
     w = ring[i:i + 1]
@@ -57,32 +69,38 @@ def pinned_word():
 COUNT_PENDING = -1             # no frame has 2^32 - 1 instances
 
 
-def post_slot(serial):
-    """(address, slot) of the pinned 64-bit word async-mode forward number `serial` posts its status bits into
-    (MomRasterArgs.status_post: the compositing kernel stores (serial << 32) | bits there itself -- no copy command and no event behind
-    the forward; they were 15 us of host time per call on a path the host paces).  A slot comes round again 256 forwards later."""
-    ring = _state.get("post_ring")
-    if ring is None:
-        ring = _state["post_ring"] = torch.zeros(_PIN_RING, dtype=torch.int64).pin_memory()
-        _state["post_np"] = ring.numpy()
-    slot = serial % _PIN_RING
-    return ring.data_ptr() + 8 * slot, slot
+class PostRing:
+    """n pinned 64-bit words that forwards post their status bits into (MomRasterArgs.status_post: the compositing kernel stores
+    (serial << 32) | bits there itself -- bit 0: this forward's binning overflowed.  No copy command and no event follows an
+    async forward: they were 15 us of host time per call on a path the host paces, and a blit kernel and a marker were 12 us of
+    the stream per frame).  Forward `serial` owns word serial % n, which comes round again n forwards later -- long after
+    whoever asks about it, a few forwards behind, has looked.  Serial 0 is never posted, so a fresh ring matches nothing."""
 
+    def __init__(self, n):
+        self.n = n
+        self.words = torch.zeros(n, dtype=torch.int64).pin_memory()
+        self.np = self.words.numpy()         # (a view of the same pinned words: reading one costs 0.1 us, indexing the tensor 2)
+        self.base = self.words.data_ptr()
 
-def posted(slot, serial, timeout_s=60.0):
-    """The status bits forward `serial` posted into `slot`; polled until they are there (wait_count explains why not an event)."""
-    import time
-    ring, want = _state["post_np"], serial & 0xFFFFFFFF
-    v = int(ring[slot])
-    if (v >> 32) & 0xFFFFFFFF != want:
-        t0 = time.perf_counter()
-        while True:
-            v = int(ring[slot])
-            if (v >> 32) & 0xFFFFFFFF == want:
-                break
-            if time.perf_counter() - t0 > timeout_s:
-                raise N.MomError(f"async forward {serial} never posted its status (slot {slot} holds {v:#x})")
-    return v & 0xFFFFFFFF
+    def slot(self, serial):
+        """(address, index) of the word forward `serial` posts into."""
+        i = serial % self.n
+        return self.base + 8 * i, i
+
+    def bits(self, index, serial, timeout_s=60.0):
+        """The status bits forward `serial` posted into word `index`: polled until the word's upper half carries that serial
+        (wait_count explains why not an event; the forwards that are asked about are a few forwards old: it is there)."""
+        ring, want = self.np, serial & 0xFFFFFFFF
+        v = int(ring[index])
+        if (v >> 32) & 0xFFFFFFFF != want:
+            t0 = time.perf_counter()
+            while True:
+                v = int(ring[index])
+                if (v >> 32) & 0xFFFFFFFF == want:
+                    break
+                if time.perf_counter() - t0 > timeout_s:
+                    raise N.MomError(f"async forward {serial} never posted its status (word {index} holds {v:#x})")
+        return v & 0xFFFFFFFF
 
 
 def wait_count(nr_host, ev=None, spin_s=float(__import__("os").environ.get("MOM_COUNT_SPIN_S", "0.02"))):
@@ -92,7 +110,6 @@ def wait_count(nr_host, ev=None, spin_s=float(__import__("os").environ.get("MOM_
     millisecond late (tools/probe/window20.py: a window ended by an event wait read 1100-1150 steps/s, the same window ended by a
     spinning device synchronisation 1181, twice), and exact mode pays that wait in EVERY iteration.  After `spin_s` seconds of
     polling the event (or the stream) is waited for the ordinary way."""
-    import time
     v = int(nr_host[0])
     if v != COUNT_PENDING:
         return v
@@ -128,7 +145,7 @@ def _check_overflow(lag):
     q = _state["pending"]
     while len(q) > lag:
         slot, count, serial = q.popleft()
-        if not (posted(slot, serial) & 1):
+        if not (_state["post_ring"].bits(slot, serial) & 1):
             _state["verified"] = serial
             continue
         q.clear()
@@ -213,7 +230,7 @@ def exact_render(lib, a, geom, img, out_color, out_depth, nr_host, P, W, H, dev,
     (regeometry(): the geometry stage, whose bucket cursors the truncated scatter has consumed; then the compositing with the exact
     size), before anything else has been enqueued: what the caller gets back is complete either way, and num_rendered is the
     frame's own count.  The buffer is merely larger than the reference's would be."""
-    guess = _state.get("exact_cap", 0)
+    guess = _state["exact_cap"]
     if guess:
         binning = torch.empty((lib.mom_raster_binning_bytes(P, W, H, guess),), dtype=torch.uint8, device=dev)
         N.check(lib.mom_raster_forward_render(C.byref(a), geom.data_ptr(), binning.data_ptr(), guess, img.data_ptr(),
@@ -233,10 +250,59 @@ def exact_render(lib, a, geom, img, out_color, out_depth, nr_host, P, W, H, dev,
                                               out_color.data_ptr(), out_depth.data_ptr(), None, stream), "mom_raster_forward_render")
     # next frame's guess: a quarter above the largest count seen, in steps (so that the allocator sees the same size again)
     want = ((int(count * 1.25) + 65535) // 65536) * 65536
-    if want > _state.get("exact_cap", 0) or _state.get("exact_cap", 0) > 4 * want:
+    if want > _state["exact_cap"] or _state["exact_cap"] > 4 * want:
         _state["exact_cap"] = want
-    _state["exact_last_capacity"] = guess
     return count, binning
+
+
+def raster_forward(lib, a, geom, img, radii, color, depth, nr_dev, P, W, H, dev, stream):
+    """Projection, binning and compositing of one forward into color / depth / radii on `stream`, with the binning capacity of
+    the sync mode (set_sync_mode): the one driver of the drop-in (rasterize_gaussians) and of the one-node render()
+    (fused_autograd._forward).  Returns (num_rendered, binning buffer) for the backward: the frame's TRUE instance count in exact
+    and blind mode, the buffer's capacity in async mode.
+
+    The buffer of an exact-mode forward may be laid out for more than the count (exact_render's guess).  The backward takes the
+    count all the same: point_list, all it reads of the buffer, lies at offset 0 whatever the capacity (csrc/mom_common.h,
+    bin_view), and the capacity only clamps the end of a tile's range (csrc/raster_render.hip, render_bwd_kernel), which never
+    lies above the count.  Count or capacity: same gradients, bit for bit."""
+    st = _state
+    a.keep_all_tiles = int(st["keep_all_tiles"])       # (set_keep_all_tiles(); the one-node backward launches from this same struct)
+    nr_host = pinned_word()
+
+    def geometry():
+        N.check(lib.mom_raster_forward_geometry(C.byref(a), geom.data_ptr(), img.data_ptr(), radii.data_ptr(), nr_dev.data_ptr(),
+                                                nr_host.data_ptr(), stream), "mom_raster_forward_geometry")
+    geometry()
+    # async with nothing to size from (no hint, no earlier frame): this one forward waits for its count, like exact mode
+    blind = st["mode"] == "async" and st["cap_hint"] == 0 and st["last_R"] is None
+    if st["mode"] == "exact" or blind:
+        # the frame's own count decides, but the compositing is enqueued before the host waits for it (exact_render, which runs
+        # geometry() again if its guess was too small)
+        count, binning = exact_render(lib, a, geom, img, color, depth, nr_host, P, W, H, dev, stream, geometry)
+        if blind:
+            st["cap_hint"] = int(count * 1.5) + 4096
+        st["last_R"] = nr_host
+        return count, binning
+    flag = overflow_flag(dev)
+    _check_overflow(_FLAG_LAG)
+    prev = st["last_R"]
+    if prev is not None and int(prev[0]) != COUNT_PENDING:      # an earlier call's count (a sizing hint; whichever copy has landed)
+        st["cap_hint"] = max(st["cap_hint"], int(int(prev[0]) * 1.5) + 4096)
+    cap = max(st["cap_hint"], 4096)
+    st["last_R"] = nr_host
+    binning = torch.empty((lib.mom_raster_binning_bytes(P, W, H, cap),), dtype=torch.uint8, device=dev)
+    # the frame's own status bits come back through a pinned word the compositing kernel writes (PostRing); the sticky device
+    # word (flag) is what gates the optimizer on the device
+    ring = st["post_ring"]
+    if ring is None:
+        ring = st["post_ring"] = PostRing(_PIN_RING)
+    serial = st["serial"] = st["serial"] + 1
+    a.status_post, slot = ring.slot(serial)
+    a.status_serial = serial & 0xFFFFFFFF
+    N.check(lib.mom_raster_forward_render(C.byref(a), geom.data_ptr(), binning.data_ptr(), cap, img.data_ptr(), color.data_ptr(),
+                                          depth.data_ptr(), flag.data_ptr(), stream), "mom_raster_forward_render")
+    st["pending"].append((slot, nr_host, serial))
+    return cap, binning
 
 
 def rasterize_gaussians(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
@@ -261,46 +327,10 @@ def rasterize_gaussians(bg, means3D, colors, opacity, scales, rotations, scale_m
         return 0, out_color, out_depth, radii, geom, torch.empty((0,), dtype=torch.uint8, device=dev), img
     a, keep = _args(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                     projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered, debug)
-    stream = N.current_stream()
     nr_dev = torch.empty((1,), dtype=torch.int32, device=dev)
-    nr_host = pinned_word()
-    N.check(lib.mom_raster_forward_geometry(C.byref(a), geom.data_ptr(), img.data_ptr(), radii.data_ptr(),
-                                            nr_dev.data_ptr(), nr_host.data_ptr(), stream), "mom_raster_forward_geometry")
-    # async with nothing to size from (no hint, no earlier frame): this one forward waits for its count, like exact mode
-    blind = _state["mode"] == "async" and _state["cap_hint"] == 0 and _state["last_R"] is None
-    if _state["mode"] == "exact" or blind:
-        def regeometry():
-            N.check(lib.mom_raster_forward_geometry(C.byref(a), geom.data_ptr(), img.data_ptr(), radii.data_ptr(), nr_dev.data_ptr(),
-                                                    nr_host.data_ptr(), stream), "mom_raster_forward_geometry")
-        cap, binning = exact_render(lib, a, geom, img, out_color, out_depth, nr_host, P, W, H, dev, stream, regeometry)
-        if blind:
-            _state["cap_hint"] = int(cap * 1.5) + 4096
-        _state["last_R"] = nr_host
-        del keep
-        return cap, out_color, out_depth, radii, geom, binning, img
-    else:
-        flag = overflow_flag(dev)
-        _check_overflow(_FLAG_LAG)
-        prev = _state["last_R"]
-        if prev is not None and int(prev[0]) != COUNT_PENDING:      # an earlier call's count (a sizing hint; whichever copy has landed)
-            _state["cap_hint"] = max(_state["cap_hint"], int(int(prev[0]) * 1.5) + 4096)
-        cap = max(_state["cap_hint"], 4096)
-    _state["last_R"] = nr_host
-    binning = torch.empty((lib.mom_raster_binning_bytes(P, W, H, cap),), dtype=torch.uint8, device=dev)
-    tracked = _state["mode"] == "async" and not blind
-    if tracked:
-        # the frame's own status bits come back through a pinned word the compositing kernel writes (post_slot); the sticky device
-        # word (flag) is what gates the optimizer on the device
-        _state["serial"] += 1
-        a.status_post, slot = post_slot(_state["serial"])
-        a.status_serial = _state["serial"] & 0xFFFFFFFF
-    N.check(lib.mom_raster_forward_render(C.byref(a), geom.data_ptr(), binning.data_ptr(), cap, img.data_ptr(),
-                                          out_color.data_ptr(), out_depth.data_ptr(), flag.data_ptr() if tracked else None, stream),
-            "mom_raster_forward_render")
-    if tracked:
-        _state["pending"].append((slot, nr_host, _state["serial"]))
+    R, binning = raster_forward(lib, a, geom, img, radii, out_color, out_depth, nr_dev, P, W, H, dev, N.current_stream())
     del keep
-    return cap, out_color, out_depth, radii, geom, binning, img
+    return R, out_color, out_depth, radii, geom, binning, img
 
 
 def rasterize_gaussians_backward(bg, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,

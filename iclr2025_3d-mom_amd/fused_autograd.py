@@ -190,50 +190,11 @@ def _forward(pc, cam, bg, delta_scale, scaling_modifier, debug, coarse):
             ops.field_forward(hp, md, P, st.xyz, st.cam_time, st.order, st.scal, st.rotq, flow, st.coef, st.pts, st.sc_d, st.rot_d,
                               st.feat, st.a0, st.opac, st.sc, st.rot, st.op, s)
     st.a = ops.raster_args(cam, view, proj, campos, bg, P, pc.active_sh_degree, means, st.f_dc, st.f_rest, op, sc, rot, coarse,
-                           scaling_modifier, debug, RC._state["keep_all_tiles"])   # set_keep_all_tiles(): the reference's lists
-    _raster_forward(lib, st.a, st, b["nr_dev"], P, W, H, dev, s)
+                           scaling_modifier, debug, False)
+    # projection, binning and compositing under the rasterizer module's settings (set_sync_mode: the binning capacity;
+    # set_keep_all_tiles: the reference's lists, written into st.a for the backward too): the drop-in's own driver
+    st.cap, st.binning = RC.raster_forward(lib, st.a, st.geom, st.img, st.radii, st.color, st.depth, b["nr_dev"], P, W, H, dev, s)
     return st
-
-
-def _raster_forward(lib, a, st, nr_dev, P, W, H, dev, s):
-    """Projection, binning and compositing of one render() call into st.color / st.depth / st.radii, with the binning capacity
-    of the rasterizer module's sync mode; leaves st.binning and st.cap for the backward."""
-    nr_host = RC.pinned_word()
-    N.check(lib.mom_raster_forward_geometry(C.byref(a), st.geom.data_ptr(), st.img.data_ptr(), st.radii.data_ptr(), nr_dev.data_ptr(),
-                                            nr_host.data_ptr(), s), "raster_geometry")
-    # binning capacity exactly as diff_gaussian_rasterization._C.rasterize_gaussians sizes it
-    state = RC._state
-    # async with nothing to size from (no hint, no earlier frame): this one forward waits for its count, like exact mode
-    blind = state["mode"] == "async" and state["cap_hint"] == 0 and state["last_R"] is None
-    if state["mode"] == "exact" or blind:
-        # the drop-in's default: the frame's own count decides, but the compositing is enqueued before the host waits for it
-        # (RC.exact_render)
-        def regeometry():
-            N.check(lib.mom_raster_forward_geometry(C.byref(a), st.geom.data_ptr(), st.img.data_ptr(), st.radii.data_ptr(),
-                                                    nr_dev.data_ptr(), nr_host.data_ptr(), s), "raster_geometry")
-        count, st.binning = RC.exact_render(lib, a, st.geom, st.img, st.color, st.depth, nr_host, P, W, H, dev, s, regeometry)
-        cap, flag = state["exact_last_capacity"], None
-        if blind:
-            state["cap_hint"] = int(count * 1.5) + 4096
-        state["last_R"] = nr_host
-        st.cap = cap
-    else:
-        flag = RC.overflow_flag(dev)
-        RC._check_overflow(RC._FLAG_LAG)
-        prev = state["last_R"]
-        if prev is not None and int(prev[0]) != RC.COUNT_PENDING:
-            state["cap_hint"] = max(state["cap_hint"], int(int(prev[0]) * 1.5) + 4096)
-        cap = max(state["cap_hint"], 4096)
-        state["last_R"] = nr_host
-        st.cap = cap
-        st.binning = torch.empty(lib.mom_raster_binning_bytes(P, W, H, cap), dtype=torch.uint8, device=dev)
-        # the frame's status bits come back through a pinned word the compositing kernel writes (RC.post_slot): no copy, no event
-        state["serial"] += 1
-        a.status_post, slot = RC.post_slot(state["serial"])
-        a.status_serial = state["serial"] & 0xFFFFFFFF
-        N.check(lib.mom_raster_forward_render(C.byref(a), st.geom.data_ptr(), st.binning.data_ptr(), cap, st.img.data_ptr(),
-                                              st.color.data_ptr(), st.depth.data_ptr(), flag.data_ptr(), s), "raster_render")
-        state["pending"].append((slot, nr_host, state["serial"]))
 
 
 def _field_grads(st, f, direct=True):
