@@ -256,6 +256,14 @@ def _sig(lib):
     lib.mom_png_encode.argtypes = [i32, i32, i32, vp, vp, sz, vp, vp, vp]
     lib.mom_png_encode_host.argtypes = [i32, i32, i32, vp, vp, sz, vp]
     lib.mom_png_tables.argtypes = [i32, vp, vp, vp, i32, vp]
+    lib.mom_jpeg_bound.restype = sz
+    lib.mom_jpeg_bound.argtypes = [i32, i32]
+    lib.mom_jpeg_scratch_bytes.restype = sz
+    lib.mom_jpeg_scratch_bytes.argtypes = [i32, i32]
+    lib.mom_jpeg_encode.argtypes = [i32, i32, vp, sz, i32, vp, sz, vp, vp, vp]
+    lib.mom_jpeg_encode_chw.argtypes = [i32, i32, i32, i32, i32, i32, vp, i32, vp, sz, vp, vp, vp]
+    lib.mom_jpeg_encode_host.argtypes = [i32, i32, vp, sz, i32, vp, sz, vp]
+    lib.mom_jpeg_tables.argtypes = [i32, vp, vp, vp, vp, vp]
     lib.mom_profile_enable.argtypes = [i32, i32]
     lib.mom_profile_read.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_longlong), i32]
     lib.mom_profile_name.restype = C.c_char_p
@@ -313,6 +321,7 @@ EXPORTS = [
     "mom_densify_scratch_bytes", "mom_densify_plan", "mom_densify_apply",
     "mom_sceneflow_fit_scratch_bytes", "mom_sceneflow_fit", "mom_flow_sample",
     "mom_png_bound", "mom_png_scratch_bytes", "mom_png_encode", "mom_png_encode_host", "mom_png_tables",
+    "mom_jpeg_bound", "mom_jpeg_scratch_bytes", "mom_jpeg_encode", "mom_jpeg_encode_chw", "mom_jpeg_encode_host", "mom_jpeg_tables",
     "mom_tri_resample_scratch_bytes", "mom_tri_resample", "mom_pcd_compose_scratch_bytes", "mom_pcd_compose",
 ]
 

@@ -8,10 +8,18 @@ one quantisation kernel (mom_image_to_rgb8), an async copy into a ring of pinned
 finished frames behind it (PIL releases the GIL inside zlib).  With MOM_PNG_ENCODER=device (or AsyncPNGWriter(encoder="device"))
 the frame is deflated on the GPU as well (mom_png_encode, csrc/png_encode.hip): what crosses to the host is a finished zlib
 stream, and the threads only frame it in PNG chunks and write it.  `scripted=True` keeps the reference's blocking order for
-comparison.  Frames whose binning buffer overflowed in async mode are rendered again at the end (FusedRender.overflowed)."""
+comparison.  Frames whose binning buffer overflowed in async mode are rendered again at the end (FusedRender.overflowed).
+
+The video: MOM_VIDEO_ENCODER unset (or "imageio") is the reference's imageio.mimwrite of the retained frames, when imageio is
+installed.  "device" and "host" need nothing installed but Pillow: vid_result/<name>.avi, Motion-JPEG -- every cropped frame a
+baseline JPEG (AsyncVideoWriter), encoded behind the frame's own kernels on the frame's stream (mom_jpeg_encode_chw,
+csrc/jpeg_encode.hip; only the finished file crosses to the host), or by PIL on the worker threads with the same bytes as result."""
 import contextlib
+import io
 import os
 import queue
+import struct
+import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
 
@@ -124,6 +132,152 @@ class AsyncPNGWriter:
         self.pool.shutdown()
 
 
+VIDEO_ENCODERS = ("imageio", "host", "device")       # MOM_VIDEO_ENCODER: who makes render_set's video
+JPEG_PIL_OPTIONS = dict(subsampling=2, optimize=False)          # with quality and restart_marker_blocks: the file mom_jpeg_encode writes
+
+
+def video_encoder(encoder=None):
+    """"imageio", "host" or "device": the argument, or MOM_VIDEO_ENCODER when it is None (unset or empty: "imageio", the reference's
+    vid_result/<name>.mp4 where imageio is installed); anything else is a ValueError."""
+    if encoder is None:
+        encoder = os.environ.get("MOM_VIDEO_ENCODER") or "imageio"
+    if encoder not in VIDEO_ENCODERS:
+        raise ValueError(f"the video encoder must be one of {VIDEO_ENCODERS}, got {encoder!r}")
+    return encoder
+
+
+def avi_file(frames, H, W, fps=30):
+    """The bytes of an AVI file with one Motion-JPEG video stream: RIFF 'AVI ' = LIST 'hdrl' (avih, LIST 'strl' (strh, strf)),
+    LIST 'movi' (one 00dc chunk per frame, padded to even length), idx1.  No OpenDML: a file of 2^31 bytes or more is refused."""
+    fps = int(fps)
+    chunk = lambda cc, body: cc + struct.pack("<I", len(body)) + body + (b"\0" if len(body) & 1 else b"")
+    biggest = max((len(f) for f in frames), default=0)
+    total = sum(8 + len(f) + (len(f) & 1) for f in frames)
+    if total + 16 * len(frames) + 4096 >= 1 << 31:
+        raise ValueError(f"the video would be {total} bytes: an AVI without OpenDML extensions ends below 2^31")
+    avih = struct.pack("<14I", 1000000 // fps, biggest * fps, 0, 0x10, len(frames), 0, 1, biggest, W, H, 0, 0, 0, 0)
+    strh = b"vids" + b"MJPG" + struct.pack("<IHHIIIIIIII", 0, 0, 0, 0, 1, fps, 0, len(frames), biggest, 0xFFFFFFFF, 0) \
+        + struct.pack("<4h", 0, 0, W, H)
+    strf = struct.pack("<IiiHH4sIiiII", 40, W, H, 1, 24, b"MJPG", 3 * W * H, 0, 0, 0, 0)
+    hdrl = chunk(b"LIST", b"hdrl" + chunk(b"avih", avih) + chunk(b"LIST", b"strl" + chunk(b"strh", strh) + chunk(b"strf", strf)))
+    movi, index, at = [b"movi"], [], 4
+    for f in frames:
+        movi.append(chunk(b"00dc", f))
+        index.append(struct.pack("<4sIII", b"00dc", 0x10, at, len(f)))
+        at += len(movi[-1])
+    body = b"AVI " + hdrl + chunk(b"LIST", b"".join(movi)) + chunk(b"idx1", b"".join(index))
+    return b"RIFF" + struct.pack("<I", len(body)) + body
+
+
+class AsyncVideoWriter:
+    """submit(image [3,IH,IW] floats, index, y0, x0): the H x W window at (y0, x0) becomes frame `index` of a Motion-JPEG AVI,
+    quantised like the reference's to8b; close() writes the file, frames in index order.  Submitting an index again replaces
+    that frame (render_set renders frames again whose binning buffer overflowed).
+
+    encoder: "device" -- mom_jpeg_encode_chw runs behind the frame's kernels on the current stream; the slot's pinned buffer
+    receives the length word and the first `prefix` bytes of the file in one copy (a frame of a rendered scene is far below
+    the worst-case capacity the encoder asks for), and a worker fetches the rest in the rare case that there is more; "host"
+    -- the window crosses to the host and a worker encodes it with PIL, whose file has the same DQT, SOF0, DHT, DRI, SOS and scan
+    (a CPU tensor always goes this way).  None reads MOM_VIDEO_ENCODER; unset, or "imageio", which is not this writer's: "host"."""
+
+    def __init__(self, path, H, W, fps=30, quality=None, encoder=None, slots=16, workers=None):
+        if encoder is None:
+            encoder = video_encoder()
+            encoder = "host" if encoder == "imageio" else encoder
+        if encoder not in ("host", "device"):
+            raise ValueError(f"AsyncVideoWriter encodes on the \"host\" or the \"device\", got {encoder!r}")
+        self.quality = int(os.environ.get("MOM_VIDEO_QUALITY") or 90) if quality is None else int(quality)
+        if not 1 <= self.quality <= 100:
+            raise ValueError(f"the JPEG quality must be in 1..100, got {self.quality}")
+        if H < 1 or W < 1:
+            raise ValueError(f"the video's frame is empty: {H} x {W}")
+        self.path, self.H, self.W, self.fps, self.encoder = path, H, W, fps, encoder
+        self.frames, self.lock = {}, threading.Lock()
+        self.restart = _jpeg_restart()
+        self.cap = 0
+        if encoder == "device":
+            self.cap = int(N.lib().mom_jpeg_bound(H, W))
+            if not self.cap:
+                raise ValueError(f"mom_jpeg_encode does not take a frame of {H} x {W}")
+            self.prefix = min(self.cap, max(4096, (H * W * 3 // 4 + 15) & ~15))
+            self.zhost = [torch.empty(16 + self.prefix, dtype=torch.uint8).pin_memory() for _ in range(slots)]
+            self.zdev = [None] * slots          # (length word and file, scratch) per slot
+        self.free = queue.Queue()
+        for i in range(slots):
+            self.free.put(i)
+        self.pool = ThreadPoolExecutor(max_workers=workers or min(slots, max(4, (os.cpu_count() or 8) // 2)))
+        self.futures = []
+
+    def submit(self, image, index, y0=0, x0=0):
+        IH, IW = int(image.shape[1]), int(image.shape[2])
+        if image.shape[0] != 3 or y0 < 0 or x0 < 0 or y0 + self.H > IH or x0 + self.W > IW:
+            raise ValueError(f"the window {self.H} x {self.W} at ({y0}, {x0}) is not inside an image of shape {tuple(image.shape)}")
+        if self.encoder == "device" and image.is_cuda:
+            slot = self.free.get()
+            if self.zdev[slot] is None or self.zdev[slot][0].device != image.device:
+                self.zdev[slot] = (torch.empty(16 + self.cap, dtype=torch.uint8, device=image.device),
+                                   torch.empty(N.lib().mom_jpeg_scratch_bytes(self.H, self.W), dtype=torch.uint8, device=image.device))
+            z, scratch = self.zdev[slot]
+            img = image if (image.is_contiguous() and image.dtype == torch.float32) else image.contiguous().float()
+            N.check(N.lib().mom_jpeg_encode_chw(IH, IW, y0, x0, self.H, self.W, img.data_ptr(), self.quality, z.data_ptr() + 16, self.cap,
+                                                z.data_ptr(), scratch.data_ptr(), N.current_stream()), "mom_jpeg_encode_chw")
+            self.zhost[slot].copy_(z[:16 + self.prefix], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self.futures.append(self.pool.submit(self._collect, slot, ev, index))
+            return
+        window = image[:, y0:y0 + self.H, x0:x0 + self.W]
+        self.futures.append(self.pool.submit(self._encode, to8b(window).transpose(1, 2, 0), index))
+
+    def _collect(self, slot, ev, index):
+        try:
+            ev.synchronize()
+            z = self.zhost[slot].numpy()
+            size = int(z[:4].view(np.uint32)[0])
+            if not 0 < size <= self.cap:
+                raise N.MomError(f"mom_jpeg_encode_chw reported a file of {size} bytes for frame {index} (capacity {self.cap})")
+            data = z[16:16 + min(size, self.prefix)].tobytes()
+            if size > self.prefix:                  # the event says the whole file is in the slot's device buffer
+                data += self.zdev[slot][0][16 + self.prefix:16 + size].cpu().numpy().tobytes()
+            with self.lock:
+                self.frames[index] = data
+        finally:
+            self.free.put(slot)
+
+    def _encode(self, rgb8, index):
+        from PIL import Image
+        buf = io.BytesIO()
+        Image.fromarray(np.ascontiguousarray(rgb8)).save(buf, "JPEG", quality=self.quality, restart_marker_blocks=self.restart,
+                                                         **JPEG_PIL_OPTIONS)
+        with self.lock:
+            self.frames[index] = buf.getvalue()
+
+    def drain(self):
+        for f in self.futures:
+            f.result()
+        self.futures.clear()
+
+    def close(self):
+        """Waits for the frames and writes the file; returns its path."""
+        try:
+            self.drain()
+        finally:
+            self.pool.shutdown()
+        data = avi_file([self.frames[k] for k in sorted(self.frames)], self.H, self.W, self.fps)
+        os.makedirs(os.path.dirname(os.path.abspath(self.path)), exist_ok=True)
+        with open(self.path, "wb") as f:
+            f.write(data)
+        return self.path
+
+
+def _jpeg_restart():
+    """The restart interval of mom_jpeg_encode's files, in MCUs (the host route asks PIL for the same)."""
+    import ctypes as C
+    quant, counts, symbols, n, r = (C.c_uint8 * 128)(), (C.c_uint8 * 64)(), (C.c_uint8 * 648)(), (C.c_int * 4)(), C.c_int(0)
+    N.check(N.lib().mom_jpeg_tables(90, quant, counts, symbols, n, C.byref(r)), "mom_jpeg_tables")
+    return r.value
+
+
 # Streams render_set deals consecutive frames to when it writes them asynchronously (1: every frame on the current stream).  Two,
 # not three: the device has four hardware queues, and a process that has trained (the step's two streams) and then renders on three
 # more lands two of them on one queue -- 4400 frames/s instead of 5700, where two streams give 5300 every time
@@ -173,6 +327,8 @@ def _render_set_body(model_path, name, views, gaussians, pipeline, background, c
     own_writer = None
     crop = 32
     frames, images = [], []
+    venc = video_encoder() if video else None           # refused before anything is rendered
+    vw = None                                           # the Motion-JPEG writer of the "host" and "device" routes
     with torch.no_grad():
         t0 = time.time()
         pooled = fr is not None and hasattr(fr, "slots")
@@ -189,7 +345,17 @@ def _render_set_body(model_path, name, views, gaussians, pipeline, background, c
                 with (torch.cuda.stream(out["stream"]) if "stream" in out else contextlib.nullcontext()):
                     (writer or own_writer).submit(rendering, path)
             frames.append((idx, view, path))
-            if video:
+            if venc in ("host", "device"):
+                if vw is None:
+                    vh, vwid = rendering.shape[1] - 2 * crop, rendering.shape[2] - 2 * crop
+                    if vh < 1 or vwid < 1:
+                        raise ValueError(f"a frame of {rendering.shape[1]} x {rendering.shape[2]} is empty after the video's crop of "
+                                         f"{crop} pixels on every side")
+                    vw = AsyncVideoWriter(os.path.join(model_path, 'vid_result', name + '.avi'), vh, vwid, fps=30,
+                                          encoder=venc if (rendering.is_cuda and not scripted) else "host")
+                with (torch.cuda.stream(out["stream"]) if "stream" in out else contextlib.nullcontext()):
+                    vw.submit(rendering, idx, crop, crop)          # on the stream the frame was rendered on, like the PNG
+            elif video:
                 images.append(rendering)
         w = writer or own_writer
         if w is not None:
@@ -209,7 +375,9 @@ def _render_set_body(model_path, name, views, gaussians, pipeline, background, c
                         if 0 <= idx < len(views):
                             rendering = render(views[idx], gaussians, pipeline, background, cam_type=cam_type, delta_scale=delta_scale)["render"]
                             w.submit(rendering, frames[idx][2])
-                            if video:
+                            if vw is not None:
+                                vw.submit(rendering, idx, crop, crop)
+                            elif video:
                                 images[idx] = rendering
                 finally:
                     RC._state["mode"] = mode
@@ -221,7 +389,9 @@ def _render_set_body(model_path, name, views, gaussians, pipeline, background, c
     print("FPS:", fps)
     if own_writer is not None:
         own_writer.close()
-    if video:
+    if vw is not None:
+        vw.close()
+    elif video:
         try:
             import imageio
             video_path = os.path.join(model_path, 'vid_result')

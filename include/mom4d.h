@@ -721,6 +721,34 @@ int mom_png_encode(int C, int H, int W, const uint8_t* rgb8, uint8_t* out, size_
 int mom_png_encode_host(int C, int H, int W, const uint8_t* rgb8, uint8_t* out, size_t capacity, uint32_t* out_size);
 int mom_png_tables(int index, uint8_t* litlen, uint8_t* dist, uint8_t* header, int header_capacity, int* header_bits);
 
+/* ---- a rendered frame -> a baseline JPEG file, on the device (csrc/jpeg_encode.hip, csrc/jpeg_dev.h): the frames of the Motion-JPEG
+ * video render.AsyncVideoWriter writes (the reference hands its frames to imageio on the host, render_4DGS.py:74-76).  The file is
+ * what libjpeg writes for the same pixels with the quality Q, 4:2:0 sampling, the tables of ITU T.81 Annex K, the "islow" integer
+ * transform and a restart interval of R MCUs (R: mom_jpeg_tables) -- every segment but APPn, and the scan bit for bit:
+ *   SOI, APP0 (JFIF 1.01), DQT x 2, SOF0, DHT x 4, DRI, SOS, the intervals with RSTn between them, EOI.
+ *   the bound        the capacity that always suffices: the header and every block of every interval at its longest code, every byte
+ *                    stuffed.  0 for an unsupported shape: H or W outside 1..65535, or a bound of 2^31 and above
+ *   the scratch size bytes of device scratch for mom_jpeg_encode / _chw (0 for an unsupported shape)
+ *   the encoder      rgb8 [H][row_stride] bytes, R G B interleaved (row_stride >= 3 W), out [capacity], out_size [1], scratch: device
+ *                    pointers.  Three launches on `stream`; no allocation, no copy, no synchronisation.  out[*out_size ..] is not written.
+ *   _chw             the same encoder reading the window [y0, y0 + H) x [x0, x0 + W) of a [3, IH, IW] float image through the
+ *                    reference's to8b: uint8(255 * clip(x, 0, 1)), truncated (not mom_image_to_rgb8's rounding)
+ *   the host form    the same file, byte for byte, computed on the host from host pointers
+ *   the tables       for the quality Q: quant [2][64] (luminance, chrominance; row-major 8x8), the four Huffman tables in the file's
+ *                    order (DC luminance, AC luminance, DC chrominance, AC chrominance) as dht_counts [4][16], dht_symbols [4][162]
+ *                    (zero-filled behind dht_nsymbols [4]), and *restart_interval = R
+ * Q outside 1..100, an unsupported shape, a window outside the image, a row_stride below 3 W, a null pointer or a capacity below the
+ * bound: MOM_EINVAL before anything is launched or written. */
+size_t mom_jpeg_bound(int H, int W);
+size_t mom_jpeg_scratch_bytes(int H, int W);
+int mom_jpeg_encode(int H, int W, const uint8_t* rgb8, size_t row_stride, int Q, uint8_t* out, size_t capacity, uint32_t* out_size,
+                    void* scratch, mom_stream_t stream);
+int mom_jpeg_encode_chw(int IH, int IW, int y0, int x0, int H, int W, const float* image, int Q, uint8_t* out, size_t capacity,
+                        uint32_t* out_size, void* scratch, mom_stream_t stream);
+int mom_jpeg_encode_host(int H, int W, const uint8_t* rgb8, size_t row_stride, int Q, uint8_t* out, size_t capacity,
+                         uint32_t* out_size);
+int mom_jpeg_tables(int Q, uint8_t* quant, uint8_t* dht_counts, uint8_t* dht_symbols, int* dht_nsymbols, int* restart_interval);
+
 const char* mom_version(void);
 
 /* Per-kernel HIP-event timing (bench.py's live roofline figure).  Slots: see mom_profile_name(0..15).
