@@ -52,3 +52,34 @@ def install_dropin(only=None) -> None:
     names = _DROPIN if only is None else {k: _DROPIN[k] for k in only}
     for public, rel in names.items():
         sys.modules[public] = importlib.import_module(rel, __name__)
+
+
+# the three modules of the reference's video generator whose names .cinemagraph mirrors (its warp: the Euler integration, the splat,
+# warp_one_level); kept apart from _DROPIN, which is what train_4DGS.py / render_4DGS.py import
+_VIDEO_DROPIN = ("thirdparty.StyleCineGAN.utils.softmax_splatting", "thirdparty.StyleCineGAN.utils.joint_splatting",
+                 "thirdparty.StyleCineGAN.utils.cinemagraph_utils")
+
+
+def install_video_dropin() -> None:
+    """Register .cinemagraph under the names the reference's video generator imports its warp from (`from
+    thirdparty.StyleCineGAN.utils.softmax_splatting import FunctionSoftsplat`, `...utils.joint_splatting import joint_splatting,
+    backwarp`, `...utils.cinemagraph_utils import warp_one_level, ...`), so that its cupy kernel is never compiled.  The parent
+    packages are the caller's own (a checkout of the reference on sys.path); one that cannot be imported is stood in for by an
+    empty package."""
+    import types
+    module = importlib.import_module(".cinemagraph", __name__)
+    for public in _VIDEO_DROPIN:
+        parts = public.split(".")
+        for i in range(1, len(parts)):
+            name = ".".join(parts[:i])
+            if name not in sys.modules:
+                try:
+                    importlib.import_module(name)
+                except ImportError:
+                    pkg = types.ModuleType(name)
+                    pkg.__path__ = []
+                    sys.modules[name] = pkg
+                    if i > 1:
+                        setattr(sys.modules[".".join(parts[:i - 1])], parts[i - 1], pkg)
+        sys.modules[public] = module
+        setattr(sys.modules[".".join(parts[:-1])], parts[-1], module)

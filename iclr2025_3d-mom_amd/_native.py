@@ -242,6 +242,11 @@ def _sig(lib):
     lib.mom_pcd_compose_scratch_bytes.restype = sz
     lib.mom_pcd_compose_scratch_bytes.argtypes = [i32, i32, i32]
     lib.mom_pcd_compose.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.mom_euler_integrate.argtypes = [i32, i32, i32, i32, vp, vp, vp]
+    lib.mom_softsplat_sum.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.mom_eulerian_geometry.argtypes = [i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    lib.mom_eulerian_blend.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.mom_eulerian_finish.argtypes = [i32, i32, i32, vp, vp, vp, vp]
     lib.mom_ssim_forward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.mom_ssim_forward_slab.argtypes = [i32, i32, i32, sz, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.mom_ssim_backward_slab.argtypes = [i32, i32, i32, sz, vp, vp, vp, vp, C.c_float, vp, vp, vp]
@@ -323,6 +328,7 @@ EXPORTS = [
     "mom_png_bound", "mom_png_scratch_bytes", "mom_png_encode", "mom_png_encode_host", "mom_png_tables",
     "mom_jpeg_bound", "mom_jpeg_scratch_bytes", "mom_jpeg_encode", "mom_jpeg_encode_chw", "mom_jpeg_encode_host", "mom_jpeg_tables",
     "mom_tri_resample_scratch_bytes", "mom_tri_resample", "mom_pcd_compose_scratch_bytes", "mom_pcd_compose",
+    "mom_euler_integrate", "mom_softsplat_sum", "mom_eulerian_geometry", "mom_eulerian_blend", "mom_eulerian_finish",
 ]
 
 

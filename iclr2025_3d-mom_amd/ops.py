@@ -610,6 +610,110 @@ def flow_sample(flow_images, pix, valid, diagonals, records=None):
     return records
 
 
+# --------------------------------------------------------------------------- the video generator's warp (csrc/eulerian_warp.hip)
+def _f32_device(what, **tensors):
+    first = next(iter(tensors.values()))
+    for name, t_ in tensors.items():
+        if t_.dtype != torch.float32 or not t_.is_contiguous() or t_.device != first.device:
+            raise N.MomError(f"{what}: {name} must be a contiguous torch.float32 tensor on {first.device}, got {t_.dtype}, "
+                             f"strides {tuple(t_.stride())} on {t_.device}")
+        if t_.requires_grad and torch.is_grad_enabled():
+            raise N.MomError(f"{what}: forward only (the reference's generator runs under no_grad); {name} requires grad")
+    _need_cuda(first, what)
+
+
+def eulerian_geometry(S):
+    """(cut, pad, padded, crop0) of blend_feature / crop_padded_tensor for a square feature of size S (mom_eulerian_geometry)."""
+    out = [C.c_int() for _ in range(4)]
+    if N.lib().mom_eulerian_geometry(int(S), *[C.byref(o) for o in out]) != N.MOM_OK:
+        raise N.MomError(f"eulerian_geometry: no cut / reflection padding / crop exists for a feature of size {S}")
+    return tuple(o.value for o in out)
+
+
+def euler_integrate(motion, steps, all_frames=False):
+    """euler_integration of the reference's video generator (cinemagraph_utils.py:9-59) in one launch: motion [2,H,W] ->
+    the displacement after `steps` steps [2,H,W], or every step's [steps+1,2,H,W].  The reference's bits; non-finite motion gives
+    displacement 0 where the reference would index out of range (include/mom4d.h)."""
+    if motion.dim() != 3 or motion.shape[0] != 2 or motion.shape[1] < 1 or motion.shape[2] < 1:
+        raise N.MomError(f"euler_integrate: motion must be [2,H,W], got {tuple(motion.shape)}")
+    steps = int(steps)
+    if steps < 0:
+        raise N.MomError(f"euler_integrate: steps must be >= 0, got {steps}")
+    _f32_device("euler_integrate", motion=motion)
+    H, W = motion.shape[1:]
+    disp = torch.empty(((steps + 1, 2, H, W) if all_frames else (2, H, W)), dtype=torch.float32, device=motion.device)
+    N.check(N.lib().mom_euler_integrate(H, W, steps, int(bool(all_frames)), N.ptr(motion), N.ptr(disp), N.current_stream()),
+            "mom_euler_integrate")
+    return disp
+
+
+def softsplat_sum(input, flow):
+    """The forward of the reference's _FunctionSoftsplat (softmax_splatting.py:8-53, 236-269): input [N,C,H,W] splatted along
+    flow [N,2,H,W] with bilinear weights into a new [N,C,H,W]; targets outside the canvas are dropped."""
+    if input.dim() != 4 or flow.dim() != 4 or flow.shape[1] != 2 or flow.shape[0] != input.shape[0] \
+            or flow.shape[2:] != input.shape[2:] or 0 in input.shape:
+        raise N.MomError(f"softsplat_sum: input [N,C,H,W] and flow [N,2,H,W] are needed, got {tuple(input.shape)} and "
+                         f"{tuple(flow.shape)}")
+    _f32_device("softsplat_sum", input=input, flow=flow)
+    n, c, H, W = input.shape
+    out = torch.zeros_like(input)
+    N.check(N.lib().mom_softsplat_sum(n, c, H, W, N.ptr(input), N.ptr(flow), N.ptr(out), N.current_stream()), "mom_softsplat_sum")
+    return out
+
+
+EULERIAN_FORM = {"channels": 0, "pixels": 1}     # mom_eulerian_blend's `form`: which index runs on the fastest lanes
+
+
+def eulerian_blend(feature, motion, idx, n_frames, acc=None, form="channels"):
+    """blend_feature's cut, reflection padding, two Euler chains and joint splat (cinemagraph_utils.py:131-178) as one launch
+    into the channel-last accumulator acc [padded,padded,C+1] (feature Z in the first C channels, Z in the last), which is
+    cleared first and returned.  feature [C,S,S], motion [2,S,S]."""
+    if feature.dim() != 3 or motion.dim() != 3 or motion.shape[0] != 2 or feature.shape[0] < 1:
+        raise N.MomError(f"eulerian_blend: feature [C,S,S] and motion [2,S,S] are needed, got {tuple(feature.shape)} and "
+                         f"{tuple(motion.shape)}")
+    c, H, W = feature.shape
+    if H != W or tuple(motion.shape[1:]) != (H, W):
+        raise N.MomError(f"eulerian_blend: the feature must be square and the motion at its size, got {tuple(feature.shape)} and "
+                         f"{tuple(motion.shape)}")
+    idx, n_frames = int(idx), int(n_frames)
+    if n_frames < 2 or not 0 <= idx < n_frames:
+        raise N.MomError(f"eulerian_blend: n_frames >= 2 and 0 <= idx < n_frames are needed, got idx {idx}, n_frames {n_frames}")
+    if form not in EULERIAN_FORM:
+        raise N.MomError(f"eulerian_blend: form must be one of {sorted(EULERIAN_FORM)}, got {form!r}")
+    padded = eulerian_geometry(H)[2]
+    tensors = dict(feature=feature, motion=motion)
+    if acc is not None:
+        if tuple(acc.shape) != (padded, padded, c + 1):
+            raise N.MomError(f"eulerian_blend: acc must be [{padded},{padded},{c + 1}], got {tuple(acc.shape)}")
+        tensors["acc"] = acc
+    _f32_device("eulerian_blend", **tensors)
+    if acc is None:
+        acc = torch.empty((padded, padded, c + 1), dtype=torch.float32, device=feature.device)
+    N.check(N.lib().mom_eulerian_blend(c, H, W, idx, n_frames, EULERIAN_FORM[form], N.ptr(feature), N.ptr(motion), N.ptr(acc),
+                                       N.current_stream()), "mom_eulerian_blend")
+    return acc
+
+
+def eulerian_finish(acc, S, full=False, return_blank=False, out=None):
+    """The rest of warp_one_level in one launch (softmax_splatting.py:341-344, cinemagraph_utils.py:498-531, 77-83): acc
+    [padded,padded,C+1] as eulerian_blend leaves it -> [C,S,S], normalised, the blank pixels (weight 0) filled with the 7 x 7 box
+    mean, cropped.  full=True: the whole normalised map [C,padded,padded] without the fill (blend_feature's return).
+    return_blank: also the blank mask of what is returned, torch.uint8."""
+    cut, pad, padded, crop0 = eulerian_geometry(S)
+    if acc.dim() != 3 or tuple(acc.shape[:2]) != (padded, padded) or acc.shape[2] < 2:
+        raise N.MomError(f"eulerian_finish: acc must be [{padded},{padded},C+1] for S = {S}, got {tuple(acc.shape)}")
+    _f32_device("eulerian_finish", acc=acc)
+    c, size = acc.shape[2] - 1, padded if full else S
+    if out is None:
+        out = torch.empty((c, size, size), dtype=torch.float32, device=acc.device)
+    elif tuple(out.shape) != (c, size, size) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != acc.device:
+        raise N.MomError(f"eulerian_finish: out must be a contiguous torch.float32 [{c},{size},{size}] tensor on {acc.device}")
+    blank = torch.empty((size, size), dtype=torch.uint8, device=acc.device) if return_blank else None
+    N.check(N.lib().mom_eulerian_finish(c, S, int(bool(full)), N.ptr(acc), N.ptr(out), N.ptr(blank), N.current_stream()),
+            "mom_eulerian_finish")
+    return (out, blank) if return_blank else out
+
+
 # --------------------------------------------------------------------------- PNG: the IDAT's zlib stream on the device
 def png_bound(C_, H, W):
     """Bytes that always hold the stream of an [H,W,C_] image (mom_png_bound; 0: unsupported shape)."""

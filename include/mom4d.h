@@ -689,6 +689,57 @@ size_t mom_pcd_compose_scratch_bytes(int V, int H, int W);
 int mom_pcd_compose(int V, int H, int W, int N, const double* resampled, const double* pts, const int* pt_off, uint8_t* image,
                     uint8_t* mask, void* scratch, size_t scratch_bytes, mom_stream_t stream);
 
+/* ---- the warp of the reference's video generator (thirdparty/StyleCineGAN; csrc/eulerian_warp.hip) ----
+ * The part of that generator that is neither a network nor a checkpoint.  All arithmetic is fp32 without contraction, operation by
+ * operation what the reference's torch ops and its CUDA string compute.  Every call is stream-ordered on `stream`, allocates nothing,
+ * copies nothing and does not synchronise; a shape it refuses is MOM_EINVAL before anything is launched.
+ *
+ * mom_euler_integrate (utils/cinemagraph_utils.py:9-59, euler_integration): one launch, each lane walks its own pixel's chain.
+ *   motion [2,H,W] (x then y); disp [2,H,W], or [steps+1,2,H,W] when all_frames (return_all_frames; frame 0 is zero).  Per step, as
+ *   :43-57: gather at (rintf(y), rintf(x)) -- half to even, torch.round's -- add; out of bounds if x > W-1, x < 0, y > H-1 or y < 0; the
+ *   flag is sticky; an invalid pixel is reset to its own coordinate (displacement 0).  Integers and fp32 adds only: the reference's bits.
+ *   NOT the reference: a coordinate that becomes NaN also sets the flag (the reference's comparisons are false for a NaN and its next
+ *   step indexes with garbage), and every gather index is clamped, so non-finite motion reads nothing out of range and gives
+ *   displacement 0.  H < 1, W < 1, H W >= 2^31, steps < 0 or a null pointer: MOM_EINVAL.
+ *
+ * mom_softsplat_sum (utils/softmax_splatting.py:8-53, kernel_Softsplat_updateOutput; the forward of _FunctionSoftsplat, :236-269):
+ *   input [N,C,H,W], flow [N,2,H,W]; output [N,C,H,W] is ADDED to (the caller zeroes it).  Per element: o = (float)x + flow, the four
+ *   corners of floor(o) with the weights as written there (:32-35), input * weight added atomically; a corner outside the canvas is
+ *   dropped.  NOT the reference: a coordinate that is NaN or not below 2^30 in magnitude is dropped whole instead of being converted.
+ *   N, C, H or W < 1, H W >= 2^31 or a null pointer: MOM_EINVAL.
+ *
+ * mom_eulerian_geometry: the sizes blend_feature / crop_padded_tensor derive from a square feature of size S (:139-147, 62-66, 77-83):
+ *   cut = 3 / 2 / 1 at S = 1024 / 512 / 256, else 0; s = S - 2 cut; pad = s/4 + s/8; padded = s + 2 pad; crop0 = (padded - S) / 2.
+ *   S < 1, pad >= s (ReflectionPad2d's own condition) or a crop that does not fit: MOM_EINVAL.  Any output pointer may be null.
+ *
+ * mom_eulerian_blend (cinemagraph_utils.py:131-178, blend_feature; utils/joint_splatting.py:23-42, joint_splatting mode "full"):
+ *   feature [C,S,S], motion [2,S,S] (already at the feature's size; H and W are both passed so that a non-square call is refused,
+ *   not misread), acc [padded,padded,C+1] channel-last, cleared by this call (a memset node) and then added to by one launch.  Per
+ *   source pixel of the cut, reflection-padded domain (index arithmetic; nothing is padded or concatenated in memory): the future chain
+ *   of idx steps on +motion and the past chain of n_frames-idx-1 steps on -motion (mom_euler_integrate's walk on the padded field);
+ *   then (feature Z) w and Z w are added for the four corners of both halves, Z = (float)(1-alpha) for the future half and (float)alpha
+ *   for the past half, alpha = idx / (n_frames-1) in double.  The reference puts the past half padded columns to the right
+ *   with `padded` taken off its x flow and crops the result: the same canvas.  Its two fp32 roundings, (float)(x + padded) + (d -
+ *   (float)padded), are reproduced, so only the order of the adds differs from the reference.
+ *   form 0: the channel runs on the fastest lanes (a wave-instruction adds to contiguous bytes of a texel); form 1: a lane adds its
+ *   own pixel's channels in a loop (measured for C = 1 and 3: DESIGN.md 3.18).
+ *   C < 1, H != W, a size mom_eulerian_geometry refuses, n_frames < 2, idx outside [0, n_frames), form outside 0..1, a null pointer:
+ *   MOM_EINVAL.
+ *
+ * mom_eulerian_finish (softmax_splatting.py:341-344; cinemagraph_utils.py:498-531 feature_inpaint_conv; :77-83 crop_padded_tensor):
+ *   acc as mom_eulerian_blend leaves it.  out = acc[.. c] / metric with metric = acc[.. C], 0 -> 1.  full == 0: out [C,S,S] is the
+ *   crop starting at crop0, and a pixel with metric == 0 -- the blank mask, which the reference gets from a second blend of a
+ *   tensor of ones: a sum of non-negative terms is zero only if every term is -- takes the 7 x 7 box mean of the normalised map, 49
+ *   products with (float)(1/49), zero padding at the padded map's border.  full != 0: out [C,padded,padded], the whole normalised
+ *   map without the fill (blend_feature's own return).  blank (or null): [S,S] or [padded,padded] bytes, 1 where metric == 0.
+ *   One launch.  C < 1, a size mom_eulerian_geometry refuses, padded > 65535 when full, a null acc or out: MOM_EINVAL. */
+int mom_euler_integrate(int H, int W, int steps, int all_frames, const float* motion, float* disp, mom_stream_t stream);
+int mom_softsplat_sum(int N, int C, int H, int W, const float* input, const float* flow, float* output, mom_stream_t stream);
+int mom_eulerian_geometry(int S, int* cut, int* pad, int* padded, int* crop0);
+int mom_eulerian_blend(int C, int H, int W, int idx, int n_frames, int form, const float* feature, const float* motion, float* acc,
+                       mom_stream_t stream);
+int mom_eulerian_finish(int C, int S, int full, const float* acc, float* out, uint8_t* blank, mom_stream_t stream);
+
 /* ---- rendered image -> 8-bit interleaved RGB (render_4DGS.py:64 torchvision.utils.save_image: x * 255 + 0.5, clamp, truncate;
  * CHW -> HWC) in one pass, so that a frame can leave the device as the bytes a PNG encoder takes.  img [C,H,W] floats, out [H,W,C]
  * bytes; C <= 4. */
