@@ -54,21 +54,28 @@ def install_dropin(only=None) -> None:
         sys.modules[public] = importlib.import_module(rel, __name__)
 
 
-# the three modules of the reference's video generator whose names .cinemagraph mirrors (its warp: the Euler integration, the splat,
-# warp_one_level); kept apart from _DROPIN, which is what train_4DGS.py / render_4DGS.py import
+# the modules of the reference's video generator that this package mirrors, kept apart from _DROPIN, which is what train_4DGS.py /
+# render_4DGS.py import.  _VIDEO_DROPIN: the three modules whose names .cinemagraph mirrors (the generator's warp: the Euler
+# integration, the splat, warp_one_level).  _STYLEGAN_OP_DROPIN: the `op` package of its StyleGAN2 and that package's two
+# submodules, whose names .stylegan_op mirrors (upfirdn2d and the fused bias + leaky ReLU, which the reference compiles from CUDA
+# sources at import); the model files that import them and the checkpoints stay the caller's
 _VIDEO_DROPIN = ("thirdparty.StyleCineGAN.utils.softmax_splatting", "thirdparty.StyleCineGAN.utils.joint_splatting",
                  "thirdparty.StyleCineGAN.utils.cinemagraph_utils")
+_STYLEGAN_OP_DROPIN = ("thirdparty.StyleCineGAN.models.stylegan2.op", "thirdparty.StyleCineGAN.models.stylegan2.op.fused_act",
+                       "thirdparty.StyleCineGAN.models.stylegan2.op.upfirdn2d")
 
 
 def install_video_dropin() -> None:
     """Register .cinemagraph under the names the reference's video generator imports its warp from (`from
     thirdparty.StyleCineGAN.utils.softmax_splatting import FunctionSoftsplat`, `...utils.joint_splatting import joint_splatting,
-    backwarp`, `...utils.cinemagraph_utils import warp_one_level, ...`), so that its cupy kernel is never compiled.  The parent
-    packages are the caller's own (a checkout of the reference on sys.path); one that cannot be imported is stood in for by an
-    empty package."""
+    backwarp`, `...utils.cinemagraph_utils import warp_one_level, ...`), so that its cupy kernel is never compiled, and
+    .stylegan_op under the names its StyleGAN2 imports its native ops from (`from thirdparty.StyleCineGAN.models.stylegan2.op import
+    FusedLeakyReLU, fused_leaky_relu, upfirdn2d`, `...op.fused_act`, `...op.upfirdn2d`), so that its CUDA sources are never
+    compiled.  The parent packages are the caller's own (a checkout of the reference on sys.path); one that cannot be imported is
+    stood in for by an empty package."""
     import types
-    module = importlib.import_module(".cinemagraph", __name__)
-    for public in _VIDEO_DROPIN:
+    warp, op = importlib.import_module(".cinemagraph", __name__), importlib.import_module(".stylegan_op", __name__)
+    for public, module in [(n, warp) for n in _VIDEO_DROPIN] + [(n, op) for n in _STYLEGAN_OP_DROPIN]:
         parts = public.split(".")
         for i in range(1, len(parts)):
             name = ".".join(parts[:i])
@@ -82,4 +89,6 @@ def install_video_dropin() -> None:
                     if i > 1:
                         setattr(sys.modules[".".join(parts[:i - 1])], parts[i - 1], pkg)
         sys.modules[public] = module
-        setattr(sys.modules[".".join(parts[:-1])], parts[-1], module)
+        parent = sys.modules[".".join(parts[:-1])]
+        if parent is not module:       # op.upfirdn2d stays the function, as the reference's op/__init__.py leaves it
+            setattr(parent, parts[-1], module)

@@ -13,8 +13,13 @@ module mirrors the names of the three reference modules that hold that warp --
 -- with the reference's signatures, on the kernels of csrc/eulerian_warp.hip (`install_video_dropin()` of the package registers it
 under those three names).  Forward only: the generator runs under no_grad.
 
-`pixel_video` is NOT the reference's output.  The reference's frames come out of StyleGAN, which needs checkpoints this package does
-not have; `pixel_video` warps the PIXELS of the input image with the same `warp_one_level` and composites them like the reference
+The same call registers stylegan_op.py, the mirror of the generator's other native dependency -- the `op` package of its StyleGAN2
+(models/stylegan2/op: upfirdn2d and the fused bias + leaky ReLU) -- under `thirdparty.StyleCineGAN.models.stylegan2.op`, so the
+reference's model.py, which imports `warp_one_level` from here and those ops from there, imports on ROCm.  The model files and the
+checkpoints are not mirrored.
+
+`pixel_video` is NOT the reference's output.  The reference's frames come out of StyleGAN, which needs a model file and checkpoints
+this package does not have; `pixel_video` warps the PIXELS of the input image with the same `warp_one_level` and composites them like the reference
 (main_jih.py:160-161).  It is a substitute that makes stage 2 runnable from this package's own stage-1 outputs, no more.
 """
 from __future__ import annotations

@@ -714,6 +714,69 @@ def eulerian_finish(acc, S, full=False, return_blank=False, out=None):
     return (out, blank) if return_blank else out
 
 
+# --------------------------------------------------------------------------- StyleGAN2's native ops (csrc/stylegan_ops.hip)
+def upfirdn2d_out_size(H, W, kh, kw, up, down, pad):
+    """(out_h, out_w) of op/upfirdn2d.py:100-101; Python's floor division, so a negative numerator gives a size below 1."""
+    (ux, uy), (dx, dy), (px0, px1, py0, py1) = up, down, pad
+    return (H * uy + py0 + py1 - kh) // dy + 1, (W * ux + px0 + px1 - kw) // dx + 1
+
+
+def upfirdn2d(input, kernel, up=(1, 1), down=(1, 1), pad=(0, 0, 0, 0)):
+    """upfirdn2d of the reference's StyleGAN2 (op/upfirdn2d.py:85-121): input [N,C,H,W], kernel [kh,kw], up (ux,uy), down (dx,dy),
+    pad (px0,px1,py0,py1) of either sign -> [N,C,out_h,out_w].  One launch; the definition is include/mom4d.h's."""
+    if input.dim() != 4 or kernel.dim() != 2 or 0 in input.shape or 0 in kernel.shape:
+        raise N.MomError(f"upfirdn2d: input [N,C,H,W] and kernel [kh,kw] are needed, got {tuple(input.shape)} and "
+                         f"{tuple(kernel.shape)}")
+    try:
+        (ux, uy), (dx, dy), (px0, px1, py0, py1) = ([int(v) for v in t] for t in (up, down, pad))
+    except (TypeError, ValueError):
+        raise N.MomError(f"upfirdn2d: up (ux,uy), down (dx,dy) and pad (px0,px1,py0,py1) are needed, got {up!r}, {down!r}, "
+                         f"{pad!r}") from None
+    n, c, H, W = input.shape
+    kh, kw = kernel.shape
+    if min(ux, uy, dx, dy) < 1 or max(kh, kw) > 32:
+        raise N.MomError(f"upfirdn2d: factors >= 1 and a kernel of at most 32 x 32 are needed, got up {(ux, uy)}, down {(dx, dy)}, "
+                         f"kernel {(kh, kw)}")
+    out_h, out_w = upfirdn2d_out_size(H, W, kh, kw, (ux, uy), (dx, dy), (px0, px1, py0, py1))
+    if out_h < 1 or out_w < 1:
+        raise N.MomError(f"upfirdn2d: the output would be [{out_h},{out_w}] for input {tuple(input.shape)}, kernel {(kh, kw)}, "
+                         f"up {(ux, uy)}, down {(dx, dy)}, pad {(px0, px1, py0, py1)}")
+    _f32_device("upfirdn2d", input=input, kernel=kernel)
+    out = torch.empty((n, c, out_h, out_w), dtype=torch.float32, device=input.device)
+    N.check(N.lib().mom_upfirdn2d(n * c, H, W, kh, kw, ux, uy, dx, dy, px0, px1, py0, py1, N.ptr(input), N.ptr(kernel), N.ptr(out),
+                                  N.current_stream()), "mom_upfirdn2d")
+    return out
+
+
+def fused_bias_act(input, bias, ref, act, grad, alpha, scale):
+    """fused_bias_act of the reference's StyleGAN2 (fused_bias_act_kernel.cu): input of 1 to 5 dimensions, bias (or None) 1-D with
+    size(1) elements (size(0) for a 1-D input), ref (or None) like input; act 1 (linear) or 3 (leaky ReLU), grad 0..2 -> like input.
+    One launch; the table of cases is include/mom4d.h's."""
+    if not 1 <= input.dim() <= 5 or input.numel() < 1:
+        raise N.MomError(f"fused_bias_act: an input of 1 to 5 dimensions is needed, got {tuple(input.shape)}")
+    act, grad = int(act), int(grad)
+    if act not in (1, 3) or not 0 <= grad <= 2:
+        raise N.MomError(f"fused_bias_act: act must be 1 or 3 and grad 0, 1 or 2, got act {act}, grad {grad}")
+    channels = input.shape[1] if input.dim() > 1 else input.shape[0]
+    tensors = dict(input=input)
+    if bias is not None:
+        if bias.dim() != 1 or bias.shape[0] != channels:
+            raise N.MomError(f"fused_bias_act: bias must be [{channels}] for input {tuple(input.shape)}, got {tuple(bias.shape)}")
+        tensors["bias"] = bias
+    if ref is not None:
+        if ref.shape != input.shape:
+            raise N.MomError(f"fused_bias_act: ref must be {tuple(input.shape)} like input, got {tuple(ref.shape)}")
+        tensors["ref"] = ref
+    elif act == 3 and grad == 1:
+        raise N.MomError("fused_bias_act: act 3, grad 1 selects by the sign of ref; ref is None")
+    _f32_device("fused_bias_act", **tensors)
+    step_b = math.prod(input.shape[2:])
+    out = torch.empty_like(input)
+    N.check(N.lib().mom_fused_bias_act(input.numel(), step_b, channels, act, grad, float(alpha), float(scale), N.ptr(input),
+                                       N.ptr(bias), N.ptr(ref), N.ptr(out), N.current_stream()), "mom_fused_bias_act")
+    return out
+
+
 # --------------------------------------------------------------------------- PNG: the IDAT's zlib stream on the device
 def png_bound(C_, H, W):
     """Bytes that always hold the stream of an [H,W,C_] image (mom_png_bound; 0: unsupported shape)."""

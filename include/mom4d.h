@@ -740,6 +740,36 @@ int mom_eulerian_blend(int C, int H, int W, int idx, int n_frames, int form, con
                        mom_stream_t stream);
 int mom_eulerian_finish(int C, int S, int full, const float* acc, float* out, uint8_t* blank, mom_stream_t stream);
 
+/* ---- the native ops of the StyleGAN2 under that generator (thirdparty/StyleCineGAN/models/stylegan2/op, and the encoder's copy under
+ * external_modules/feature_style_encoder/pixel2style2pixel; csrc/stylegan_ops.hip) ----
+ * The reference compiles both from CUDA sources when the package is imported and has no other path.  fp32, caller-allocated outputs,
+ * stream-ordered on `stream`, no allocation, copy or synchronisation; MOM_EINVAL before anything is launched.  Forward and both
+ * backward orders of the reference's autograd functions are these two calls with other arguments (stylegan_op.py).  The model files
+ * and the checkpoints are not part of this library.
+ *
+ * mom_upfirdn2d (op/upfirdn2d.py:85-121; upfirdn2d_kernel.cu): x is M planes of [H,W], k is [kh,kw], out is M planes of [out_h,out_w],
+ *   out_h = (H up_y + pad_y0 + pad_y1 - kh) / down_y + 1 and out_w likewise (op/upfirdn2d.py:100-101); pads of either sign.
+ *     out[m,oy,ox] = sum over a < kh, b < kw of k[kh-1-a][kw-1-b] U[oy down_y + a - pad_y0][ox down_x + b - pad_x0]
+ *     U[Y][X]      = x[m][Y/up_y][X/up_x] if Y, X >= 0, up_y | Y, up_x | X and the quotients lie in [0,H) x [0,W); 0 otherwise
+ *   Each output is one fp32 sum in a fixed order (a ascending, then b; only the taps with up | coordinate are visited), without
+ *   atomics: two calls give the same bits.  up_x == up_y, down_x == down_y and (up, down, kh x kw) one of (1,1,4x4) (1,1,3x3)
+ *   (2,1,4x4) (2,1,2x2) (1,2,4x4) (1,2,2x2) -- the reference's six dispatch modes, upfirdn2d_kernel.cu:172-268 -- run compile-time
+ *   instantiations that stage the input tile in LDS; everything else runs one general kernel.
+ *   M, H, W < 1, a factor < 1, kh or kw outside 1..32, out_h or out_w < 1, H up, |pad| or down not below 2^29, H W or out_h out_w not
+ *   below 2^31, 2^24 or more output tiles of 64 x 16, or a null pointer: MOM_EINVAL.
+ *
+ * mom_fused_bias_act (op/fused_act.py; fused_bias_act_kernel.cu:18-49 as its switch writes it): n elements; x' = x + b[(i / step_b)
+ *   % size_b] when b is not null; with act * 10 + grad =
+ *     10, 11: y = x'      12, 32: y = 0      30: y = x' > 0 ? x' : x' alpha      31: y = ref > 0 ? x' : x' alpha
+ *   out = y scale.  Three fp32 roundings in that order (add, multiply, multiply), no contraction: bit-equal to the same statement in
+ *   numpy float32.  ref is read for 31 alone.
+ *   act outside {1,3}, grad outside 0..2, n < 1, n >= 2^31 (the reference's own int), step_b < 1, b with size_b < 1, 31 without ref,
+ *   a null x or out: MOM_EINVAL. */
+int mom_upfirdn2d(int M, int H, int W, int kh, int kw, int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0,
+                  int pad_y1, const float* x, const float* k, float* out, mom_stream_t stream);
+int mom_fused_bias_act(size_t n, int step_b, int size_b, int act, int grad, float alpha, float scale, const float* x, const float* b,
+                       const float* ref, float* out, mom_stream_t stream);
+
 /* ---- rendered image -> 8-bit interleaved RGB (render_4DGS.py:64 torchvision.utils.save_image: x * 255 + 0.5, clamp, truncate;
  * CHW -> HWC) in one pass, so that a frame can leave the device as the bytes a PNG encoder takes.  img [C,H,W] floats, out [H,W,C]
  * bytes; C <= 4. */
