@@ -10,9 +10,16 @@
  * {0,0,0}-seeded min/max reduction in simple-knn ...).
  *
  * Parity status: the reference holds NO tests or golden vectors for this path
- *  and its CUDA sources cannot be built here (no nvcc, no
- * CUDA GPU) => "parity unpinned by the reference".  The oracle is pinned
- * instead by tests/test_oracle_*.py: hand-derived known answers, structural
+ *  and there is no nvcc binary of it to compare with.  Its
+ * CUDA SOURCE, however, compiles with hipcc for gfx950 (oracle/ref_gpu.py,
+ * oracle/ref_gpu/): tests/test_reference_kernels_gpu.py runs the reference's
+ * own forward.cu / backward.cu / rasterizer_impl.cu / simple_knn.cu beside
+ * this file and beside the HIP kernels on the same inputs and holds this file
+ * to them -- integer outputs, sort keys and order, depth / centre / conic bits
+ * equal; images and all ten gradient tensors inside the suite's gates.  What
+ * is pinned is that source built by hipcc with -ffp-contract=off, not an nvcc
+ * build; oracle/ref_gpu/PINNED.md holds the measured table.  Without a GPU
+ * the oracle is held by tests/test_oracle_*.py: hand-derived known answers, structural
  * invariants, finite differences of the fp64 build of this same file
  * (tests/test_oracle_raster.py), an independent pure-torch statement of the
  * forward whose torch.autograd gradients equal this file's backward to 1e-7

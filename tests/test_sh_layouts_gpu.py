@@ -13,7 +13,8 @@ import torch
 
 from oracle import raster_oracle as ro
 from scenes import clamp_some_channels, posed_gaussians
-from test_raster_gpu import DIR_SUM_TOL, DIR_TOL, _check_sh_fp64, _cmp_forward, _cmp_grads
+from raster_compare import _cmp_forward, _cmp_grads
+from test_raster_gpu import DIR_SUM_TOL, DIR_TOL, _check_sh_fp64
 
 pytestmark = pytest.mark.gpu
 

@@ -11,6 +11,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 from hip_helpers import hip_backward, hip_forward  # noqa: E402
 from oracle import raster_oracle as ro  # noqa: E402
 from scenes import POSES, posed_gaussians  # noqa: E402
+import raster_compare as RC  # noqa: E402
 import test_raster_gpu as T  # noqa: E402
 
 ro.set_threads(16)
@@ -24,8 +25,8 @@ def forward_case(s, label):
         fw = hip_forward(s, keep_all_tiles=keep)
         dc = np.abs(fw["color"] - st.out_color)
         dd = np.abs(fw["depth"] - st.out_depth)
-        a = T._last_contributor(fw["n_contrib"], fw["ranges"], fw["point_list"], W, H)
-        b = T._last_contributor(st.n_contrib, st.ranges, st.point_list, W, H)
+        a = RC._last_contributor(fw["n_contrib"], fw["ranges"], fw["point_list"], W, H)
+        b = RC._last_contributor(st.n_contrib, st.ranges, st.point_list, W, H)
         nc = int((fw["n_contrib"] != st.n_contrib).sum()) if keep else -1
         print(f"  {label} {W}x{H} keep={int(keep)} | {dc.mean():.2e} | {dc.max():.2e} | {int((dc.max(0) > 1e-5).sum())} of {W * H} | {nc} | "
               f"{int((a != b).sum())} | {np.abs(fw['final_T'] - st.final_T).mean():.2e} | depth mean {dd.mean():.2e} max {dd.max():.2e}")
@@ -42,7 +43,7 @@ def backward_case(s, seed, label, **kw):
         a, b = g[name], go[name].reshape(g[name].shape)
         scale = max(float(np.abs(b).max()), 1e-30)
         row = np.abs(a - b).reshape(a.shape[0], -1).max(axis=1) / scale
-        print(f"  {label} | {name:14s} | {T._relerr(a, b):.2e} | {int((row > 2e-5).sum())} | {int((row > 1e-4).sum())} | {row.max():.2e}")
+        print(f"  {label} | {name:14s} | {RC._relerr(a, b):.2e} | {int((row > 2e-5).sum())} | {int((row > 1e-4).sum())} | {row.max():.2e}")
 
 
 print("forward: case | mean L1 | max | pixels > 1e-5 | n_contrib mismatches | last-contributor mismatches | final_T mean")
