@@ -25,13 +25,21 @@ border and mask morphology and the 8-bit cast run on the device (ops.tri_resampl
     render_pcd         the reference's render_PCD: the multi-view images and masks of the point cloud
     refit_scene_flow   a stage-1 directory's MOM/train_data.pth -> MOM/scene_flow.pth
     write_pixel_video  MOM/video/%06d.png from the centre frame's image, our_flow and mask by warping pixels (cinemagraph.pixel_video)
+    pcd_gen_poses      the reference's 'lookaround' and 'hemisphere' poses (utils/trajectory.py)
+    read_json          the hints of a labelme image.json
+    hint_arguments     the hints of one frame as the reference's flow step selects them, quirks included
+    estimate_flows     the reference's estimate_flow: every frame's T2C_flow, the arithmetic around the estimator on the device
+    flow_image         helpmotion.flow2img, the colour-wheel image of a flow
+    build_stage1       the reference's train_motion.py main: an input folder -> MOM/train_data.pth, scene_flow.pth, Flow_viz
 
-The rest of stage 1 (the depth network, the pose generators, the 2D flow estimator, the video generator's GAN) is not part of this
-package; the video generator's warp is (cinemagraph.py), and `--video pixels` makes the looping video with it from the image's
-pixels -- a substitute for the reference's StyleGAN output, not that output.
+The networks of stage 1 (the depth network, the 2D flow estimator, the video generator's GAN) are not part of this package: the depth
+is an argument, the estimator is a callable of the user's, and each of the other two has a checkpoint-free SUBSTITUTE that is not
+the reference's output -- `--flow hints` takes the dense hint field itself as the estimated motion, and `--video pixels` makes the
+looping video with the video generator's warp (cinemagraph.py) from the image's pixels instead of StyleGAN features.
 
     python -m iclr2025_3d-mom_amd.motion --input_dir DIR [--train_iteration N] [--sampler device] [--resampler device]
     python -m iclr2025_3d-mom_amd.motion --input_dir DIR --video pixels [--n_frames 120] [--video_size 1024]
+    python -m iclr2025_3d-mom_amd.motion --input_dir DIR --build --depth FILE [--flow hints] [--video pixels]
 """
 import functools
 import os
@@ -632,6 +640,230 @@ def write_pixel_video(input_dir, n_frames=120, size=1024, center_idx=2):
     return cinemagraph.save_video(frames, mom, int(data["W"]), int(data["H"]))
 
 
+def _rotation(th_deg, phi_deg):
+    """Ry(th) Rx(phi) with the reference's signs and its degree -> radian expression (utils/trajectory.py:224,296).  Every entry of the
+    product has one non-zero term, so the result does not depend on how a BLAS orders a 3 x 3 matmul."""
+    th, phi = th_deg / 180 * np.pi, phi_deg / 180 * np.pi
+    return np.matmul(np.array([[np.cos(th), 0, -np.sin(th)], [0, 1, 0], [np.sin(th), 0, np.cos(th)]]),
+                     np.array([[1, 0, 0], [0, np.cos(phi), -np.sin(phi)], [0, np.sin(phi), np.cos(phi)]]))
+
+
+# utils/trajectory.py:210-226 generate_seed_preset: entries 0, 1, 4, 7, 14 of its 21-pose table, (theta, phi) in degrees
+LOOKAROUND_DEG = ((0.0, 0.0), (20.0, 0.0), (-20.0, 0.0), (0.0, -22.5), (0.0, 22.5))
+# utils/trajectory.py:282-300 generate_seed_hemisphere: its `degree` argument is overwritten by 5, and d is the literal 4.3 -- the
+# centre depth train_motion.py:41 passes is ignored (:293-294)
+HEMISPHERE_DEG = ((5, 0), (0, -5), (0, 0), (0, 5), (-5, 0))
+HEMISPHERE_D = 4.3
+
+
+def pcd_gen_poses(name):
+    """utils/trajectory.py get_pcdGenPoses(name) for the two names stage 1 uses (train_motion.py:38,41), [5,3,4] float64
+    world-to-camera: 'lookaround' is generate_seed_preset -- five pure rotations, not the fourteen train_motion.py's comment speaks
+    of -- and 'hemisphere' five poses on a sphere of radius 4.3 about the scene, 5 degrees apart.  Another name raises ValueError
+    (the reference raises a TypeError from `raise("...")`, or serves trajectories stage 1 never asks for)."""
+    if name == "lookaround":
+        poses = np.zeros((len(LOOKAROUND_DEG), 3, 4))
+        for i, (th, phi) in enumerate(LOOKAROUND_DEG):
+            poses[i, :3, :3] = _rotation(th, phi)
+        return poses
+    if name == "hemisphere":
+        d, poses = HEMISPHERE_D, np.zeros((len(HEMISPHERE_DEG), 3, 4))
+        for i, (th, phi) in enumerate(HEMISPHERE_DEG):
+            poses[i, :3, :3] = _rotation(th, phi)
+            poses[i, :3, 3:4] = (np.array([d * np.sin(th / 180 * np.pi), 0, d - d * np.cos(th / 180 * np.pi)]).reshape(3, 1)
+                                 + np.array([0, d * np.sin(phi / 180 * np.pi), d - d * np.cos(phi / 180 * np.pi)]).reshape(3, 1))
+        return poses
+    raise ValueError(f"pcd_gen_poses knows 'lookaround' and 'hemisphere' (what stage 1 uses), got {name!r}")
+
+
+def read_json(source):
+    """train_motion.py:376-392: the hints of a labelme file (a path, or the parsed dict) as four lists of ints -- start x, start y,
+    end x, end y -- of every shape whose label starts with 'hint', truncated towards zero as int() does."""
+    import json
+    if isinstance(source, dict):
+        data = source
+    else:
+        with open(source) as f:
+            data = json.load(f)
+    out = [[], [], [], []]
+    for shape in data["shapes"]:
+        if shape["label"].startswith("hint"):
+            start, end = np.array(shape["points"])
+            for lst, val in zip(out, (start[0], start[1], end[0], end[1])):
+                lst.append(int(val))
+    return out
+
+
+HINT_BOUND = 512          # demo.py:57: a literal, whatever the image's size
+
+
+def hint_arguments(frame, sigma=None):
+    """The hints generate_mask_hints_from_user hands its arithmetic (thirdparty/cinemagraphy/demo.py:47-86) for one frame of
+    render_pcd: (pos int64 [n,2], start float64 [n,2], end float64 [n,2], sigma), columns (x, y); hint k sits at pos[k] and moves by
+    (end[k] - start[k]) / 50.  The reference's quirks, as written:
+      * a hint is kept if 0 <= x < 512 and 0 <= y < 512 -- the literal 512, not the image's size (:57).  In an image smaller than
+        512 a kept hint can lie outside it; the reference then indexes its pixel grid out of range and raises IndexError, and so
+        does this function;
+      * when no hint is kept, one hint at (0, 0) is used (:61-63);
+      * the motion of kept hint number k is read from the UNFILTERED lists at index k (:67-70): after a dropped hint every later
+        hint moves with an earlier hint's motion, and the (0, 0) fallback moves with hint 0's;
+      * sigma=None draws np.random.randint(height // (n * 2), height // (n / 2)) from numpy's global generator, the reference's
+        expression (:86), so a seeded run draws what the seeded reference draws; an int is taken as it is."""
+    sx, sy, ex, ey = (frame[k] for k in ("final_hint_start_x", "final_hint_start_y", "final_hint_end_x", "final_hint_end_y"))
+    height, width = np.array(frame["mask"]).shape[:2]
+    pos = [(int(x[0]), int(y[0])) for x, y in zip(sx, sy) if 0 <= x[0] < HINT_BOUND and 0 <= y[0] < HINT_BOUND]
+    if not pos:
+        pos = [(0, 0)]
+    for x, y in pos:
+        if x >= width or y >= height:
+            raise IndexError(f"a hint at ({x}, {y}) passes the reference's literal bound of {HINT_BOUND} but lies outside the "
+                             f"{width} x {height} image")
+    n = len(pos)
+    first = lambda lst: np.array([np.asarray(lst[k], np.float64).reshape(-1)[0] for k in range(n)])
+    start, end = np.stack([first(sx), first(sy)], axis=1), np.stack([first(ex), first(ey)], axis=1)
+    if sigma is None:
+        sigma = np.random.randint(height // (n * 2), height // (n / 2))
+    return np.asarray(pos, np.int64).reshape(n, 2), start, end, int(sigma)
+
+
+def motion_rgbs(frames, size):
+    """[V,3,S,S] float32 in [-1, 1]: every frame's image resized bicubically to S x S, ToTensor, Normalize(0.5, 0.5) (demo.py:109-127).
+    PIL's Image.resize(BICUBIC) is what torchvision's Resize calls for a PIL image."""
+    from PIL import Image
+    out = np.empty((len(frames), 3, size, size), np.float32)
+    for k, fr in enumerate(frames):
+        im = np.asarray(fr["image"].convert("RGB").resize((size, size), Image.BICUBIC), np.uint8)
+        out[k] = ((torch.from_numpy(im.transpose(2, 0, 1).copy()).float().div(255) - 0.5) / 0.5).numpy()
+    return torch.from_numpy(out)
+
+
+def estimate_flows(train_data, estimator=None, size=768, device=None):
+    """MotionOptimization.estimate_flow (train_motion.py:368-374): appends a [1,2,H,W] float32 CPU tensor to every frame's T2C_flow.
+    The reference builds its estimator, loads its weights and runs the arithmetic around it on the CPU once per view; here the
+    hints of all views are selected on the host (hint_arguments, in frame order, so sigma is drawn as the reference draws it) and
+    the arithmetic runs on the device for all views at once: ops.hint_field in front of the estimator, ops.flow_finish behind it.
+    estimator: a callable (motion_rgbs [V,3,S,S], mask_s [V,1,S,S], hints [V,2,S,S]) -> pred [V,2,S,S] on the device -- the user's
+    own network (the reference's SPADEUnetMaskMotion.forward_flow(...)["PredMotion"]), loaded once.  estimator=None takes pred = hints:
+    the dense hint field itself as the motion -- a SUBSTITUTE for the reference's estimator that needs no checkpoint, not its output
+    (as cinemagraph.pixel_video is for the video generator).  size: the estimator's working size (config.yaml's data.W)."""
+    dev = torch.device("cuda" if device is None else device)
+    frames = train_data["frames"]
+    if not frames:
+        raise ValueError("train_data has no frames")
+    args = [hint_arguments(fr) for fr in frames]
+    masks = np.stack([np.array(fr["mask"]) for fr in frames])
+    if masks.ndim != 3:
+        raise ValueError(f"every frame's mask must be one channel of one size, got {masks.shape}")
+    V, n = len(frames), max(len(a[0]) for a in args)
+    pos, start, end = np.zeros((V, n, 2), np.int32), np.zeros((V, n, 2), np.float64), np.zeros((V, n, 2), np.float64)
+    for k, (p, s, e, _) in enumerate(args):
+        pos[k, :len(p)], start[k, :len(p)], end[k, :len(p)] = p, s, e
+    up = lambda a: _upload(a, dev)
+    hints, mask_s = ops.hint_field(up(pos), up(start), up(end), up(np.asarray([len(a[0]) for a in args], np.int32)),
+                                   up(np.asarray([a[3] for a in args], np.float32)), up((masks != 0).astype(np.uint8)), size)
+    if estimator is None:
+        pred = hints
+    else:
+        with torch.no_grad():
+            pred = estimator(up(motion_rgbs(frames, size)), mask_s, hints)
+        if tuple(pred.shape) != tuple(hints.shape):
+            raise ValueError(f"the estimator must return [{V}, 2, {size}, {size}], got {tuple(pred.shape)}")
+        pred = pred.detach().to(torch.float32).contiguous()
+    flow = ops.flow_finish(pred, mask_s, masks.shape[1], masks.shape[2]).cpu()
+    for k, fr in enumerate(frames):
+        fr["T2C_flow"].append(flow[k:k + 1].clone())
+    return train_data
+
+
+def _color_wheel():
+    """The 55-entry Middlebury colour wheel (Baker et al., ICCV 2007) as helpmotion.make_colorwheel fills it: six segments, in each
+    one channel at 255 and one ramping by floor(255 i / n), up or down."""
+    wheel, row = np.zeros((55, 3)), 0
+    for n, full, ramp, down in ((15, 0, 1, False), (6, 1, 0, True), (4, 1, 2, False), (11, 2, 1, True), (13, 2, 0, False), (6, 0, 2, True)):
+        steps = np.floor(255 * np.arange(0, n) / n)
+        wheel[row:row + n, full] = 255
+        wheel[row:row + n, ramp] = 255 - steps if down else steps
+        row += n
+    return wheel
+
+
+def flow_image(flow):
+    """helpmotion.flow2img: a [2,H,W] flow (tensor or array) as the [H,W,3] uint8 colour-wheel image train_motion.viz_flow saves,
+    in the flow's own dtype as the reference computes it.  As written there: the flow is normalised by its largest magnitude + 1e-5;
+    the hue index next to the last wheel entry wraps to entry 1, not 0 (helpmotion.py:113); magnitudes above 1 are dimmed by 0.75."""
+    f = flow.detach().cpu().numpy() if torch.is_tensor(flow) else np.asarray(flow)
+    if f.ndim != 3 or f.shape[0] != 2:
+        raise ValueError(f"flow must be [2,H,W], got {f.shape}")
+    H, W = f.shape[1:]
+    u, v = f[0].reshape(-1), f[1].reshape(-1)
+    rad_max = np.max(np.sqrt(np.square(u) + np.square(v)))
+    u, v = u / (rad_max + 1e-5), v / (rad_max + 1e-5)
+    wheel = _color_wheel()
+    ncols = wheel.shape[0]
+    rad = np.sqrt(np.square(u) + np.square(v))
+    fk = (np.arctan2(-v, -u) / np.pi + 1) / 2 * (ncols - 1)
+    k0 = np.floor(fk).astype(np.int32)
+    k1 = k0 + 1
+    k1[k1 == ncols] = 1
+    frac = fk - k0
+    image, inside = np.zeros((H * W, 3), np.uint8), rad <= 1
+    for c in range(3):
+        col = (1 - frac) * (wheel[k0, c] / 255.0) + frac * (wheel[k1, c] / 255.0)
+        col[inside] = 1 - rad[inside] * (1 - col[inside])
+        col[~inside] = col[~inside] * 0.75
+        image[:, c] = np.floor(255 * col)
+    return image.reshape(H, W, 3)
+
+
+def build_stage1(input_dir, depth, flow="hints", train_iteration=200, video="none", render_poses=None, internal_poses=None, size=768,
+                 n_frames=120, video_size=1024, device=None):
+    """Stage 1 from an input folder, as train_motion.py:442-464 runs it: image.png, image_json/mask.png and the hints of image.json ->
+    MOM/train_data.pth, MOM/scene_flow.pth and MOM/Flow_viz/%03d.png, what stage 2 (Trainer) reads.
+    depth: float32 [H,W] or the path of a .npy holding it -- what the reference's depth network returns for the image
+    (d_model.infer_pil; the network is not part of this package).  flow: "hints" (estimate_flows without an estimator: the hint
+    field as the motion, a SUBSTITUTE for the reference's flow estimator) or the estimator callable of estimate_flows.
+    render_poses / internal_poses: [n,3,4] world-to-camera, by default pcd_gen_poses('lookaround') / ('hemisphere').
+    video="pixels" also writes MOM/video/%06d.png with write_pixel_video (again a substitute, for the reference's GAN).
+    The renders, the flow arithmetic, the sampling, the fit and our_flow all run on the device (render_pcd, estimate_flows,
+    optimize_motion with the device sampler and resampler).  Returns (train_data, scene_flow [3,P] CPU)."""
+    from PIL import Image
+    if video not in ("none", "pixels"):
+        raise ValueError(f"video must be 'none' or 'pixels', got {video!r}")
+    if not (flow == "hints" or callable(flow)):
+        raise ValueError(f"flow must be 'hints' or an estimator callable, got {flow!r}")
+    src_img = Image.open(os.path.join(input_dir, "image.png"))
+    if src_img.mode != "RGB":
+        src_img = src_img.convert("RGB")
+    src_mask = Image.open(os.path.join(input_dir, "image_json", "mask.png"))
+    hints = read_json(os.path.join(input_dir, "image.json"))
+    W, H = src_img.size
+    depth = np.load(depth) if isinstance(depth, (str, os.PathLike)) else np.asarray(depth)
+    if depth.shape != (H, W):
+        raise ValueError(f"the depth must be [{H}, {W}] like image.png, got {depth.shape}")
+    if np.array(src_mask).shape != (H, W):
+        raise ValueError(f"image_json/mask.png must be one channel of {W} x {H} like image.png, got {np.array(src_mask).shape}")
+    K = stage1_intrinsics(H, W)
+    render_poses = pcd_gen_poses("lookaround") if render_poses is None else np.asarray(render_poses)
+    internal_poses = pcd_gen_poses("hemisphere") if internal_poses is None else np.asarray(internal_poses)
+    mom = os.path.join(input_dir, "MOM")
+    os.makedirs(mom, exist_ok=True)
+    train_data, none_idx = render_pcd(src_img, src_mask, depth.astype(np.float32), hints, render_poses, internal_poses, device=device)
+    train_data = estimate_flows(train_data, None if flow == "hints" else flow, size=size, device=device)
+    train_data, scene_flow = optimize_motion(train_data, render_poses, internal_poses, K, H, W, non_frame_idx=none_idx,
+                                             train_iteration=train_iteration, device=device, sampler="device", resampler="device")
+    scene_flow = scene_flow.cpu()
+    viz = os.path.join(mom, "Flow_viz")
+    os.makedirs(viz, exist_ok=True)
+    for idx, fr in enumerate(train_data["frames"]):                       # train_motion.py:394-399 viz_flow
+        if len(fr["our_flow"]):
+            Image.fromarray(flow_image(fr["our_flow"][0][0])).save(os.path.join(viz, f"{idx:03d}.png"))
+    torch.save(train_data, os.path.join(mom, "train_data.pth"))
+    torch.save(scene_flow, os.path.join(mom, "scene_flow.pth"))
+    if video == "pixels":
+        write_pixel_video(input_dir, n_frames, video_size)
+    return train_data, scene_flow
+
+
 def main(argv=None):
     from argparse import ArgumentParser
     ap = ArgumentParser(description="Fit MOM/scene_flow.pth of a stage-1 directory to the 2D flows in its MOM/train_data.pth")
@@ -647,7 +879,27 @@ def main(argv=None):
                     "for the reference's StyleGAN video, which needs checkpoints; no mp4 is written")
     ap.add_argument("--n_frames", type=int, default=120, help="frames of the --video loop (the reference's option.py:35)")
     ap.add_argument("--video_size", type=int, default=1024, help="side of the square the --video warp runs at (main_jih.py:33-39)")
+    ap.add_argument("--build", action="store_true", help="build stage 1 from the folder's image.png, image.json and image_json/mask.png "
+                    "(build_stage1): writes MOM/train_data.pth, MOM/scene_flow.pth and MOM/Flow_viz; with --video pixels the frames too")
+    ap.add_argument("--depth", help="--build: a .npy with the image's float32 [H,W] depth (the depth network is the user's own)")
+    ap.add_argument("--flow", choices=("hints",), default="hints", help="--build: where the 2D flows come from.  hints: the dense hint "
+                    "field itself -- a substitute for the reference's flow estimator, which needs a checkpoint (an estimator of "
+                    "one's own is passed to build_stage1 in Python)")
+    ap.add_argument("--size", type=int, default=768, help="--build: the flow estimator's working size (config.yaml's data.W)")
+    ap.add_argument("--render_poses", type=int, default=None, help="--build: use only the first N of the five 'lookaround' poses")
+    ap.add_argument("--seed", type=int, default=None, help="--build: seed numpy's global generator, which draws every view's sigma")
     a = ap.parse_args(argv)
+    if a.build:
+        if not a.depth:
+            ap.error("--build needs --depth FILE")
+        if a.seed is not None:
+            np.random.seed(a.seed)
+        poses = None if a.render_poses is None else pcd_gen_poses("lookaround")[:a.render_poses]
+        data, flow = build_stage1(a.input_dir, a.depth, flow=a.flow, train_iteration=a.train_iteration, video=a.video,
+                                  render_poses=poses, size=a.size, n_frames=a.n_frames, video_size=a.video_size)
+        print(f"{os.path.join(a.input_dir, 'MOM')}: {len(data['frames'])} frames; scene_flow.pth: {tuple(flow.shape)}, largest "
+              f"magnitude {float(flow.abs().max()):.6g}")
+        return
     if a.video == "pixels":
         paths = write_pixel_video(a.input_dir, a.n_frames, a.video_size)
         print(f"{os.path.dirname(paths[0])}: {len(paths)} frames")

@@ -777,6 +777,63 @@ def fused_bias_act(input, bias, ref, act, grad, alpha, scale):
     return out
 
 
+# --------------------------------------------------------------------------- around stage 1's flow estimator (csrc/flow_frame.hip)
+def _typed(what, dev, *want):
+    for name, t_, shape, dtype in want:
+        if tuple(t_.shape) != tuple(shape) or t_.dtype != dtype or t_.device != dev or not t_.is_contiguous():
+            raise N.MomError(f"{what}: {name} must be a contiguous {dtype} {list(shape)} tensor on {dev}, "
+                             f"got {t_.dtype} {list(t_.shape)} on {t_.device}")
+
+
+def hint_field(hint_pos, hint_start, hint_end, hint_count, sigma, mask, size):
+    """The dense hint field and the resized mask in front of the reference's flow estimator (demo.py:73-105,
+    generate_mask_hints_from_user) for all V views in one call: hint_pos [V,n,2] int32 (x, y), hint_start / hint_end [V,n,2] float64
+    (the motion is (end - start) / 50), hint_count [V] int32 (rows used per view), sigma [V] float32, mask [V,H,W] uint8, size = S
+    -> (hints [V,2,S,S], mask_s [V,1,S,S]) float32.  Two launches; the arithmetic is include/mom4d.h's."""
+    if mask.dim() != 3 or hint_pos.dim() != 3 or 0 in mask.shape:
+        raise N.MomError(f"hint_field: mask [V,H,W] and hint_pos [V,n,2] are needed, got {tuple(mask.shape)} and {tuple(hint_pos.shape)}")
+    (V, H, W), n, S, dev = mask.shape, hint_pos.shape[1], int(size), mask.device
+    if S < 1 or n > N.HINTS_MAX:
+        raise N.MomError(f"hint_field: size >= 1 and at most {N.HINTS_MAX} hints a view are needed, got size {S}, {n} hints")
+    _typed("hint_field", dev, ("mask", mask, (V, H, W), torch.uint8), ("hint_pos", hint_pos, (V, n, 2), torch.int32),
+           ("hint_start", hint_start, (V, n, 2), torch.float64), ("hint_end", hint_end, (V, n, 2), torch.float64),
+           ("hint_count", hint_count, (V,), torch.int32), ("sigma", sigma, (V,), torch.float32))
+    _need_cuda(mask, "hint_field")
+    nbytes = int(N.lib().mom_hint_field_scratch_bytes(V, H, W))
+    if nbytes == 0:
+        raise N.MomError(f"hint_field: {V} views of {H} x {W} pixels are more than the kernels index")
+    scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    hints = torch.empty((V, 2, S, S), dtype=torch.float32, device=dev)
+    mask_s = torch.empty((V, 1, S, S), dtype=torch.float32, device=dev)
+    N.check(N.lib().mom_hint_field(V, H, W, S, n, N.ptr(hint_pos), N.ptr(hint_start), N.ptr(hint_end), N.ptr(hint_count), N.ptr(sigma),
+                                   N.ptr(mask), N.ptr(hints), N.ptr(mask_s), scratch.data_ptr(), nbytes, N.current_stream()),
+            "mom_hint_field")
+    return hints, mask_s
+
+
+def flow_finish(pred, mask_s, H, W):
+    """What the reference does to its estimator's output (renderer.py:598-606) for all V views in one call: pred [V,2,S,S],
+    mask_s [V,1,S,S] -> flow [V,2,H,W]: pred * mask, the 15 x 15 box mean with a zero border (the reference's loop of seven blurs
+    keeps one), * mask, scale by (W / S, H / S), bilinear resize.  Two launches."""
+    if pred.dim() != 4 or pred.shape[1] != 2 or pred.shape[2] != pred.shape[3] or 0 in pred.shape:
+        raise N.MomError(f"flow_finish: pred must be [V,2,S,S], got {tuple(pred.shape)}")
+    V, _, S, _ = pred.shape
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise N.MomError(f"flow_finish: H and W >= 1 are needed, got {H} x {W}")
+    if tuple(mask_s.shape) != (V, 1, S, S):
+        raise N.MomError(f"flow_finish: mask_s must be [{V},1,{S},{S}] like pred, got {tuple(mask_s.shape)}")
+    _f32_device("flow_finish", pred=pred, mask_s=mask_s)
+    nbytes = int(N.lib().mom_flow_finish_scratch_bytes(V, S))
+    if nbytes == 0 or V * 2 * H * W >= 2 ** 31:
+        raise N.MomError(f"flow_finish: {V} views of {S} x {S} -> {H} x {W} pixels are more than the kernels index")
+    scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=pred.device)
+    flow = torch.empty((V, 2, H, W), dtype=torch.float32, device=pred.device)
+    N.check(N.lib().mom_flow_finish(V, S, H, W, N.ptr(pred), N.ptr(mask_s), N.ptr(flow), scratch.data_ptr(), nbytes,
+                                    N.current_stream()), "mom_flow_finish")
+    return flow
+
+
 # --------------------------------------------------------------------------- PNG: the IDAT's zlib stream on the device
 def png_bound(C_, H, W):
     """Bytes that always hold the stream of an [H,W,C_] image (mom_png_bound; 0: unsupported shape)."""

@@ -770,6 +770,46 @@ int mom_upfirdn2d(int M, int H, int W, int kh, int kw, int up_x, int up_y, int d
 int mom_fused_bias_act(size_t n, int step_b, int size_b, int act, int grad, float alpha, float scale, const float* x, const float* b,
                        const float* ref, float* out, mom_stream_t stream);
 
+/* ---- the arithmetic around stage 1's 2D flow estimator (train_motion.py:368-374 estimate_flow; csrc/flow_frame.hip) ----
+ * The reference runs it on the CPU once per view; both calls take all V views.  fp32 in the reference's order of operations, without
+ * contraction except in the bilinear resize (below), caller-allocated outputs, stream-ordered on `stream`, no allocation, copy, synchronisation or atomic: two calls give the
+ * same bits.  The estimator between the two calls (SPADEUnetMaskMotion.forward_flow) is not part of this library.
+ *
+ * mom_hint_field (thirdparty/cinemagraphy/demo.py:24-105, generate_mask_hints_from_user, from :73 on; the selection of the hints in
+ *   front of it is host code, motion.hint_arguments):
+ *   hint_pos [V,max_hints,2] int32 (x, y), hint_start / hint_end [V,max_hints,2] float64 (x, y): view v uses its first hint_count[v]
+ *   rows (clamped to 0..max_hints); the hint's motion is (end - start) / 50 in float64 (:68-70).  sigma [V] float32; mask [V,H,W] bytes;
+ *   hints [V,2,S,S], mask_s [V,1,S,S] float32.  Per pixel (x, y) of the H x W image, with fp32 coordinates (:77-81):
+ *     dist = sqrt(dx dx + dy dy); w = expf(-(dist / sigma)^2); m_c = (float)((double)m_c + (double)w motion_c); norm += w    (:90-94)
+ *     norm == 0 -> 1; field_c = m_c / norm * (mask != 0) * (float)(S / W or S / H)                                              (:95-101)
+ *   then hints = the field resized bilinearly to S x S (:102) as torch's CPU kernels run F.interpolate(align_corners=False): the source
+ *   coordinate fma(in / S, o + 0.5, -0.5), clamped at 0, its integer part and fraction in fp32, and fma(l0, a, l1 b) for each sum; and
+ *   mask_s = F.interpolate(mode='area') of mask != 0 (:103): over the window [floor(o in / S), ceil((o + 1) in / S)) the count of
+ *   ones, divided by the window's height and then by its width.  sqrt and the divisions are correctly rounded; expf is the device
+ *   library's (1 ulp), the one operation that is not the reference's bits.  A hint's position is only ever a coordinate: nothing is
+ *   indexed by it (the reference indexes its pixel grid with it and raises outside the image; the host mirrors that).
+ *   Two launches: the field at H x W into scratch (V 2 H W floats, mom_hint_field_scratch_bytes), then the three S x S planes of
+ *   every view.  One launch would evaluate every hint's exponential at the four source pixels of every output pixel: 9 times the
+ *   exponentials at the reference's 512 -> 768.
+ *
+ * mom_flow_finish (thirdparty/cinemagraphy/lib/renderer.py:598-606, the tail of compute_flow_and_inpaint):
+ *   pred [V,2,S,S], mask_s [V,1,S,S] -> flow [V,2,H,W]:  p = pred mask_s; b = the 15 x 15 box mean of p, zeros outside the image (the sum of
+ *   15 row sums of 15 terms, divided by 225); flow = bilinear resize to H x W of b mask_s (float)(W / S or H / S).  The reference's
+ *   `for _ in range(7)` blurs the SAME input seven times and keeps the last result (:600-601): one blur is what it computes.
+ *   Two launches: blur, mask and scale into scratch (V 2 S S floats, mom_flow_finish_scratch_bytes), then the resize.
+ *
+ * V < 1, V > 21845, H, W or S < 1, V 2 H W or V 2 S S >= 2^31, max_hints outside 0..MOM_HINTS_MAX, a null pointer that would be read or
+ * written, a misaligned scratch or a scratch_bytes below the sizing function's value (0 for an unsupported shape): MOM_EINVAL before
+ * anything is launched. */
+#define MOM_HINTS_MAX 1024
+size_t mom_hint_field_scratch_bytes(int V, int H, int W);
+int mom_hint_field(int V, int H, int W, int S, int max_hints, const int* hint_pos, const double* hint_start, const double* hint_end,
+                   const int* hint_count, const float* sigma, const uint8_t* mask, float* hints, float* mask_s, void* scratch,
+                   size_t scratch_bytes, mom_stream_t stream);
+size_t mom_flow_finish_scratch_bytes(int V, int S);
+int mom_flow_finish(int V, int S, int H, int W, const float* pred, const float* mask_s, float* flow, void* scratch,
+                    size_t scratch_bytes, mom_stream_t stream);
+
 /* ---- rendered image -> 8-bit interleaved RGB (render_4DGS.py:64 torchvision.utils.save_image: x * 255 + 0.5, clamp, truncate;
  * CHW -> HWC) in one pass, so that a frame can leave the device as the bytes a PNG encoder takes.  img [C,H,W] floats, out [H,W,C]
  * bytes; C <= 4. */
