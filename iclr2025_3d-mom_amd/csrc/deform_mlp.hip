@@ -491,6 +491,40 @@ deform_bwd_dw_kernel(MlpDev m, int P, int chunk, const float* __restrict__ feat,
     }
 }
 
+// The f32 backward's weight and bias gradients meet in a zeroed staging area at the head of `scratch` (the workgroups' float
+// atomics land there) and reach the caller's buffers in ONE addition per element: the += of mom4d.h to one rounding of what the
+// buffer held, as deform_bwd_reduce_kernel gives the bf16 form.  (Atomics straight onto the buffers rounded its content once per
+// workgroup: 5 times at 33 Gaussians, ~200 at 8 k -- and once more per camera of a batch.)
+//   [4 layers (W0, W1_0..2)][64*64 weights + 64 biases]  then  [3 heads][4*64 weights + 4 biases]
+constexpr int kStgLayer = kHid * kHid + kHid;
+constexpr int kStgThin = 4 * kHid + 4;
+constexpr int kStgUsed = 4 * kStgLayer + 3 * kStgThin;
+constexpr int kStgFloats = (kStgUsed + 63) / 64 * 64;            // dH behind it stays 256-byte aligned
+// dst[i] += staged[i] for the elements first .. first + count - 1 of the map above; an element whose sum is zero is left alone
+__global__ void __launch_bounds__(256) deform_bwd_add_kernel(MlpDev m, const float* __restrict__ staged, int n_in, int first, int count)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= count) return;
+    const int i = first + t;
+    if (i >= kStgUsed) return;
+    const float v = staged[i];
+    if (v == 0.f) return;
+    float* dst = nullptr;
+    if (i < 4 * kStgLayer) {
+        const int L = i / kStgLayer, j = i - L * kStgLayer;
+        if (j >= kHid * kHid) dst = (L == 0 ? m.db0 : m.db1[L - 1]) + (j - kHid * kHid);
+        else if (L > 0) dst = m.dW1[L - 1] + j;
+        else if (j < kHid * n_in) dst = m.dW0 + j;
+    } else {
+        const int k = (i - 4 * kStgLayer) / kStgThin, j = (i - 4 * kStgLayer) - k * kStgThin;
+        const int nout = k == 2 ? 4 : 3;
+        if (j < 4 * kHid) {
+            if ((j >> 6) < nout) dst = m.dW2[k] + j;
+        } else if (j - 4 * kHid < nout) dst = m.db2[k] + (j - 4 * kHid);
+    }
+    if (dst) *dst += v;
+}
+
 template <int KT>
 int forward(const MomDeformMLP* w, int P, const float* feat, const float* xyz, const float* scaling, const float* rotation,
             const float* scene_flow, float flow_coef, float* pts, float* scales, float* rots, float* a0_save, const float* opacity_raw,
@@ -550,14 +584,26 @@ int backward(const MomDeformMLP* w, int P, const float* feat, const float* a0, c
     if (!d.dW0 || !d.db0) return MOM_EINVAL;
     for (int i = 0; i < 3; i++)
         if (!d.dW1[i] || !d.db1[i] || !d.dW2[i] || !d.db2[i]) return MOM_EINVAL;
-    float* dH = (float*)scratch;                       // [4][P][64]: mom_deform_backward_scratch_bytes(P) holds it
+    // mom_deform_backward_scratch_bytes(P) holds both: the staging area of the weight gradients, then dH [4][P][64]
+    float* staged = (float*)scratch;
+    float* dH = staged + kStgFloats;
+    MlpDev g = d;                                       // the kernels' gradient pointers: into the staging area
+    g.dW0 = staged;
+    g.db0 = staged + kHid * kHid;
+    for (int i = 0; i < 3; i++) {
+        g.dW1[i] = staged + (1 + i) * kStgLayer;
+        g.db1[i] = g.dW1[i] + kHid * kHid;
+        g.dW2[i] = staged + 4 * kStgLayer + i * kStgThin;
+        g.db2[i] = g.dW2[i] + 4 * kHid;
+    }
     const int tiles = (P + 31) / 32;
     int blocks = tiles < 256 ? tiles : 256;             // persistent: one workgroup per CU; a small problem still uses every CU
     const size_t lds_a = sizeof(float) * kLBwdTotal;
     const size_t lds_b = sizeof(float) * (kHid * kHid + kHid);
     if (!mom_lds_limit<deform_bwd_dx_kernel<KT>>(lds_a)) return MOM_ELAUNCH;
     MomProfScope ps(MOM_P_MLP_BWD, (hipStream_t)stream);
-    hipLaunchKernelGGL(deform_bwd_dx_kernel<KT>, dim3(blocks), dim3(64 * kDxWaves), lds_a, (hipStream_t)stream, d, P, tiles, a0, dpts,
+    if (hipMemsetAsync(staged, 0, sizeof(float) * kStgFloats, (hipStream_t)stream) != hipSuccess) return MOM_ELAUNCH;
+    hipLaunchKernelGGL(deform_bwd_dx_kernel<KT>, dim3(blocks), dim3(64 * kDxWaves), lds_a, (hipStream_t)stream, g, P, tiles, a0, dpts,
                        dscales, drots, dfeat, dH);
     if (hipGetLastError() != hipSuccess) return MOM_ELAUNCH;
     hipStream_t ws = (hipStream_t)dw_stream;
@@ -573,8 +619,15 @@ int backward(const MomDeformMLP* w, int P, const float* feat, const float* a0, c
     const int waves = 1024, layers = 4;
     int chunk = (P + waves - 1) / waves;
     chunk += chunk & 1;
+    // the thin output layers' gradients are complete in the staging area: into the caller's buffers on `stream` (mom4d.h), beside
+    // the weight-gradient kernel
+    hipLaunchKernelGGL(deform_bwd_add_kernel, dim3((3 * kStgThin + 255) / 256), dim3(256), 0, (hipStream_t)stream, d, staged, 32 * KT,
+                       4 * kStgLayer, 3 * kStgThin);
+    if (hipGetLastError() != hipSuccess) return MOM_ELAUNCH;
     // one-dimensional grid: the kernel deals (range, layer) to the XCDs itself
-    hipLaunchKernelGGL(deform_bwd_dw_kernel<KT>, dim3((waves / 4) * layers), dim3(256), lds_b, ws, d, P, chunk, feat, a0, dH, layers);
+    hipLaunchKernelGGL(deform_bwd_dw_kernel<KT>, dim3((waves / 4) * layers), dim3(256), lds_b, ws, g, P, chunk, feat, a0, dH, layers);
+    if (hipGetLastError() != hipSuccess) return MOM_ELAUNCH;
+    hipLaunchKernelGGL(deform_bwd_add_kernel, dim3((4 * kStgLayer + 255) / 256), dim3(256), 0, ws, d, staged, 32 * KT, 0, 4 * kStgLayer);
     return hipGetLastError() == hipSuccess ? MOM_OK : MOM_ELAUNCH;
 }
 
@@ -599,10 +652,11 @@ extern "C" int mom_deform_backward_split_n(const MomDeformMLP* w, int P, int in_
     return (in_features == 64 ? backward<2> : backward<1>)(w, P, feat, a0, dpts, dscales, drots, dfeat, scratch, stream, dw_stream);
 }
 
-// the larger of what the two forms need: the two-kernel form's four [P,64] matrices, the one-kernel form's per-workgroup partial sums
+// the larger of what the two forms need: the two-kernel form's staging area and four [P,64] matrices, the one-kernel form's
+// per-workgroup partial sums
 extern "C" size_t mom_deform_backward_scratch_bytes(int P)
 {
-    const size_t a = (size_t)4 * (size_t)(P > 0 ? P : 1) * kHid * sizeof(float), b = mom_deform_bwd_b3f_scratch_bytes();
+    const size_t a = ((size_t)kStgFloats + (size_t)4 * (size_t)(P > 0 ? P : 1) * kHid) * sizeof(float), b = mom_deform_bwd_b3f_scratch_bytes();
     return a > b ? a : b;
 }
 

@@ -522,8 +522,9 @@ int mom_deform_forward_activated(const MomDeformMLP* w, int P, const float* feat
                                  float* opacity_act, mom_stream_t stream);
 /* d{pts,scales,rots}: gradients of the three outputs; writes dfeat [P,64]; weight/bias gradients accumulate into w->d*.
  * (The identity paths d xyz += dpts etc. are the caller's.) */
-size_t mom_deform_backward_scratch_bytes(int P);   /* the larger of 4 x [P,64] floats (the two-kernel form's pre-activation gradients) and the
-                                                       one-kernel form's per-workgroup partial sums (17.8 MB) */
+size_t mom_deform_backward_scratch_bytes(int P);   /* the larger of 4 x [P,64] floats + 70 KB (the two-kernel form's pre-activation gradients and the
+                                                       staging area its weight gradients meet in) and the one-kernel form's per-workgroup partial
+                                                       sums (17.8 MB).  Either form adds to a weight-gradient buffer ONCE per element. */
 int mom_deform_backward(const MomDeformMLP* w, int P, const float* feat, const float* a0, const float* dpts,
                         const float* dscales, const float* drots, float* dfeat, void* scratch, mom_stream_t stream);
 /* The same with a second stream at the callee's disposal.  Default form (one kernel on the bf16 matrix pipe, csrc/deform_bwd_b3.hip:

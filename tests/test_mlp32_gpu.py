@@ -5,11 +5,13 @@ routing of a model of that shape, and determinism.
 
 Tolerances of the parity test are those of tests/test_ops_gpu.py::test_fused_deform_mlp_forward_backward, with its rule for the
 per-Gaussian gradients: a hidden unit whose pre-activation is within rounding of zero may take the other ReLU branch, which
-changes that Gaussian's gradient rows, so they may differ on at most 2 Gaussians.  That cap is a condition on the inputs: with
-the seeds used here (seed = P) the reference in fp64 on the CPU has a pre-activation within 2^-24 * sum |terms| of zero (the
-worst rounding of an fp32 chain in any order, inherited error of relu(h0) included) on 0, 0, 0, 0, 0 and 2 Gaussians at the six
-sizes (smallest |pre-activation| 1.3e-6 at P = 20011, 8.4e-6 at P = 1000), and the reference in fp32 against itself in fp64
-flips no ReLU and has no gradient row beyond the tolerance at any size."""
+changes that Gaussian's gradient rows, so they may differ on at most 2 Gaussians, and only on Gaussians that
+tests/deform_mlp_cases.py::ambiguous_rows marks for the seed: those where the float64 evaluation has a pre-activation within the
+worst-case fp32 rounding bound of zero (gamma_{n+1} sum |terms| for a sum in any order, inherited error of relu(h0) included).
+With the seeds used here (seed = P) that is 0, 0, 1, 0, 8 and 167 Gaussians at the six sizes (within 2^-24 sum |terms|, the
+typical rather than the worst rounding: 0, 0, 0, 0, 0 and 2), so at P = 1, 31 and 65 no row is excused; the reference in fp32
+against itself in fp64 flips no ReLU and has no gradient row beyond the tolerance at any size.  The test of the parameter
+gradients here is a norm; element by element they are held to derived bounds in tests/test_deform_mlp_ref_gpu.py."""
 import ctypes as C
 import importlib
 
@@ -17,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+import deform_mlp_cases
 from oracle import torch_ref as tr
 
 pytestmark = pytest.mark.gpu
@@ -63,10 +66,13 @@ def test_forward_and_every_gradient_match_the_cpu_reference(P):
     assert gi[0].shape == (P, 32) and gp[0].shape == (64, 32)
     for a, b in zip(o, o_ref):
         np.testing.assert_allclose(a, b, rtol=2e-5, atol=2e-5)
+    ambiguous = deform_mlp_cases.ambiguous_rows([p.numpy() for p in params], feat.numpy(), bf16=False, margin=1.0, composed=1.0)
+    print("ambiguous Gaussians:", int(ambiguous.sum()), "of", P)
     for a, b in zip(gi, gi_ref):
-        bad_rows = (np.abs(a - b) > _row_tol(b)).reshape(P, -1).any(1).sum()
-        print("per-Gaussian gradient", a.shape, "rows beyond tolerance:", int(bad_rows), "max |diff| %.3e" % float(np.abs(a - b).max()))
-        assert bad_rows <= 2, (a.shape, int(bad_rows))
+        bad_rows = (np.abs(a - b) > _row_tol(b)).reshape(P, -1).any(1)
+        print("per-Gaussian gradient", a.shape, "rows beyond tolerance:", int(bad_rows.sum()), "max |diff| %.3e" % float(np.abs(a - b).max()))
+        assert not (bad_rows & ~ambiguous).any(), (a.shape, np.flatnonzero(bad_rows & ~ambiguous))
+        assert bad_rows.sum() <= 2, (a.shape, int(bad_rows.sum()))
     for a, b in zip(gp, gp_ref):
         rel = np.linalg.norm(a.astype(np.float64) - b) / (np.linalg.norm(b) + 1e-30)
         print("parameter gradient", a.shape, "relative norm %.3e" % rel)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import deform_mlp_cases
 from oracle import raster_oracle as ro
 from oracle import torch_ref as tr
 
@@ -202,11 +203,17 @@ def test_fused_deform_mlp_forward_backward(P):
         np.testing.assert_allclose(a, b, rtol=2e-5, atol=2e-5)
     # A hidden unit whose pre-activation is within rounding of 0 may take the other ReLU branch (k-ordered fma chain on the
     # matrix cores vs BLAS on the CPU).  That legitimately changes that one Gaussian's gradient rows, so: per-Gaussian
-    # gradients may differ on at most 2 Gaussians, parameter gradients are compared in norm.
+    # gradients may differ on at most 2 Gaussians, and only on Gaussians the float64 evaluation marks ambiguous for this
+    # seed (a pre-activation within the worst-case rounding bound of zero, tests/deform_mlp_cases.py: none at P = 1, so
+    # nothing is excused there); parameter gradients are compared in norm (element by element under derived bounds:
+    # tests/test_deform_mlp_ref_gpu.py).
+    ambiguous = deform_mlp_cases.ambiguous_rows([p.numpy() for p in params], feat.numpy(), bf16=True, margin=1.0, composed=1.0)
+    print("ambiguous Gaussians:", int(ambiguous.sum()), "of", P)
     for a, b in zip(gi, gi_ref):
         tol = 2e-4 * np.abs(b) + 2e-5 * max(1.0, float(np.abs(b).max()))
-        bad_rows = (np.abs(a - b) > tol).reshape(P, -1).any(1).sum()
-        assert bad_rows <= 2, (a.shape, int(bad_rows))
+        bad_rows = (np.abs(a - b) > tol).reshape(P, -1).any(1)
+        assert not (bad_rows & ~ambiguous).any(), (a.shape, np.flatnonzero(bad_rows & ~ambiguous))
+        assert bad_rows.sum() <= 2, (a.shape, int(bad_rows.sum()))
     for a, b in zip(gp, gp_ref):
         rel = np.linalg.norm(a.astype(np.float64) - b) / (np.linalg.norm(b) + 1e-30)
         assert rel <= 2e-3, (a.shape, rel)
