@@ -277,15 +277,9 @@ def _as_uint8_hwc(image, size, what):
     return np.array(image.resize((size, size)))
 
 
-def pixel_video(image, our_flow, mask, n_frames=120, size=1024, device=None):
-    """A looping video from one image and its Eulerian flow WITHOUT the reference's StyleGAN: the frames of the reference's
-    VideoGenerator (thirdparty/StyleCineGAN/main_jih.py) with the input image standing where the GAN's result would.  This is a
-    substitute that warps pixels, not the reference's deep-feature output.
-
-    image: PIL image or uint8 [H,W,3]; our_flow [1,2,h,w] (stage 1's, pixels per frame); mask: PIL image or uint8 [H,W], 255 where
-    the scene moves.  As main_jih.py:33-39 all three are resized to size x size (the flow bilinearly, its values unscaled, as
-    there).  Per frame idx: warp_one_level(image, flow, idx, n_frames), then result mask + image (1 - mask) (:160-161).
-    Returns n_frames arrays [size,size,3] float32 in [0, 1], as VideoGenerator does (to_numpy)."""
+def pixel_video_frames(image, our_flow, mask, n_frames=120, size=1024, device=None):
+    """pixel_video's frames one at a time, where they are made: a generator of n_frames contiguous [size,size,3] float32 tensors in
+    [0, 1] on the device, so that a consumer on the device (save_video(writer="device")) never holds the video."""
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     rgb = _as_uint8_hwc(image, size, "image")
     if rgb.ndim != 3 or rgb.shape[2] < 3:
@@ -296,23 +290,63 @@ def pixel_video(image, our_flow, mask, n_frames=120, size=1024, device=None):
         x = torch.from_numpy(rgb[..., :3].copy()).float().permute(2, 0, 1).unsqueeze(0).to(dev) / 127.5 - 1     # ip_utils.to_tensor
         flow = F.interpolate(torch.as_tensor(our_flow).float().to(dev), size=(size, size), mode='bilinear', align_corners=False)
         up_mask = resize_feature((torch.from_numpy(np.array(m) / 255).unsqueeze(0).unsqueeze(0).to(dev)).float(), size)
-        frames = []
-        for idx in range(n_frames):
+    for idx in range(n_frames):
+        with torch.no_grad():                       # per frame: a generator must not leave the caller's grad mode switched off
             result = warp_one_level(x, flow, idx, n_frames)
             result = result * up_mask + x * (1 - up_mask)
-            frames.append(((result + 1) / 2).permute(0, 2, 3, 1)[0].cpu().numpy())                               # ip_utils.to_numpy
-    return frames
+            frame = ((result + 1) / 2).permute(0, 2, 3, 1)[0].contiguous()                                      # ip_utils.to_numpy
+        yield frame
 
 
-def save_video(frames, output_path, W, H):
+def pixel_video(image, our_flow, mask, n_frames=120, size=1024, device=None):
+    """A looping video from one image and its Eulerian flow WITHOUT the reference's StyleGAN: the frames of the reference's
+    VideoGenerator (thirdparty/StyleCineGAN/main_jih.py) with the input image standing where the GAN's result would.  This is a
+    substitute that warps pixels, not the reference's deep-feature output.
+
+    image: PIL image or uint8 [H,W,3]; our_flow [1,2,h,w] (stage 1's, pixels per frame); mask: PIL image or uint8 [H,W], 255 where
+    the scene moves.  As main_jih.py:33-39 all three are resized to size x size (the flow bilinearly, its values unscaled, as
+    there).  Per frame idx: warp_one_level(image, flow, idx, n_frames), then result mask + image (1 - mask) (:160-161).
+    Returns n_frames arrays [size,size,3] float32 in [0, 1], as VideoGenerator does (to_numpy)."""
+    return [f.cpu().numpy() for f in pixel_video_frames(image, our_flow, mask, n_frames=n_frames, size=size, device=device)]
+
+
+VIDEO_WRITERS = ("host", "device")
+
+
+def save_video(frames, output_path, W, H, writer=None):
     """The frames as train_motion.save_video names them (train_motion.py:402-412): <output_path>/video/%06d.png at W x H, through
-    this package's PNG writer.  No mp4 is written."""
+    this package's PNG writer.  No mp4 is written.
+    writer "host" (the default, also None): frames are float arrays [h,w,3]; each is quantised with (frame * 255).astype(uint8),
+    resized by PIL (bicubic) and deflated by zlib, on the calling thread.  writer "device": frames are [h,w,3] float32 tensors on the
+    GPU, taken one at a time as the iterable makes them (pixel_video_frames); each goes through ops.pil_resize(to8b=True) -- the same
+    quantisation and PIL's bytes -- and render.AsyncPNGWriter(encoder="device"), so what crosses to the host is the finished zlib
+    stream.  The files of both writers decode to the same pixels; their zlib streams differ.  Returns the paths, in frame order."""
     import os
-    from PIL import Image
-    from .utils import image_io
+    if writer not in (None,) + VIDEO_WRITERS:
+        raise ValueError(f"save_video: writer must be one of {VIDEO_WRITERS}, got {writer!r}")
     out = os.path.join(output_path, "video")
     os.makedirs(out, exist_ok=True)
     paths = []
+    if writer == "device":
+        from .render import AsyncPNGWriter
+        png = AsyncPNGWriter(H, W, 3, slots=8, encoder="device")
+        rgb8 = scratch = None
+        try:
+            for i, frame in enumerate(frames):
+                if not (torch.is_tensor(frame) and frame.is_cuda and frame.dim() == 3 and frame.shape[2] == 3):
+                    raise MomError("save_video(writer='device') takes [h,w,3] float32 tensors on the GPU (pixel_video_frames), got "
+                                   + (f"{frame.dtype} {list(frame.shape)} on {frame.device}" if torch.is_tensor(frame) else type(frame).__name__))
+                if rgb8 is None:       # one output and one intermediate for all frames: every use is ordered on the frames' stream
+                    rgb8 = torch.empty((H, W, 3), dtype=torch.uint8, device=frame.device)
+                    scratch = ops.pil_resize_scratch(frame.shape, (W, H), frame.device)
+                ops.pil_resize(frame, (W, H), to8b=True, out=rgb8, scratch=scratch)
+                paths.append(os.path.join(out, f"{str(i).zfill(6)}.png"))
+                png.submit_rgb8(rgb8, paths[-1])
+        finally:
+            png.close()
+        return paths
+    from PIL import Image
+    from .utils import image_io
     for i, frame in enumerate(frames):
         a = np.array(Image.fromarray((frame * 255).astype(np.uint8)).resize((W, H)))
         paths.append(os.path.join(out, f"{str(i).zfill(6)}.png"))

@@ -38,7 +38,7 @@ the reference's output -- `--flow hints` takes the dense hint field itself as th
 looping video with the video generator's warp (cinemagraph.py) from the image's pixels instead of StyleGAN features.
 
     python -m iclr2025_3d-mom_amd.motion --input_dir DIR [--train_iteration N] [--sampler device] [--resampler device]
-    python -m iclr2025_3d-mom_amd.motion --input_dir DIR --video pixels [--n_frames 120] [--video_size 1024]
+    python -m iclr2025_3d-mom_amd.motion --input_dir DIR --video pixels [--n_frames 120] [--video_size 1024] [--video-writer device]
     python -m iclr2025_3d-mom_amd.motion --input_dir DIR --build --depth FILE [--flow hints] [--video pixels]
 """
 import functools
@@ -624,10 +624,12 @@ def refit_scene_flow(input_dir, train_iteration=200, device=None, sampler="gridd
     return flow
 
 
-def write_pixel_video(input_dir, n_frames=120, size=1024, center_idx=2):
+def write_pixel_video(input_dir, n_frames=120, size=1024, center_idx=2, writer=None):
     """MOM/video/%06d.png of a stage-1 directory from the centre frame of its MOM/train_data.pth -- image, our_flow[0] and mask, what
     the reference hands its VideoGenerator (main_jih.py:27-39) -- by cinemagraph.pixel_video, saved at the data's W x H as
-    train_motion.save_video names the frames (train_motion.py:402-412).  A pixel warp, not the reference's StyleGAN output."""
+    train_motion.save_video names the frames (train_motion.py:402-412).  A pixel warp, not the reference's StyleGAN output.
+    writer: cinemagraph.save_video's -- "host" (the default) copies every frame to the host and resizes and deflates it there; "device"
+    resizes and deflates each frame on the GPU as it is made; the files decode to the same pixels."""
     from . import cinemagraph
     from .scene.dataset_readers import load_train_data
     mom = os.path.join(input_dir, "MOM")
@@ -636,8 +638,11 @@ def write_pixel_video(input_dir, n_frames=120, size=1024, center_idx=2):
     missing = [k for k in ("image", "our_flow", "mask") if k not in frame or (k == "our_flow" and not len(frame[k]))]
     if missing:
         raise ValueError(f"{mom}/train_data.pth: frame {center_idx} lacks {missing}, which the video is made from")
-    frames = cinemagraph.pixel_video(frame["image"], frame["our_flow"][0], frame["mask"], n_frames=n_frames, size=size)
-    return cinemagraph.save_video(frames, mom, int(data["W"]), int(data["H"]))
+    if writer not in (None,) + cinemagraph.VIDEO_WRITERS:
+        raise ValueError(f"writer must be one of {cinemagraph.VIDEO_WRITERS}, got {writer!r}")
+    make = cinemagraph.pixel_video_frames if writer == "device" else cinemagraph.pixel_video
+    frames = make(frame["image"], frame["our_flow"][0], frame["mask"], n_frames=n_frames, size=size)
+    return cinemagraph.save_video(frames, mom, int(data["W"]), int(data["H"]), writer=writer)
 
 
 def _rotation(th_deg, phi_deg):
@@ -726,10 +731,30 @@ def hint_arguments(frame, sigma=None):
     return np.asarray(pos, np.int64).reshape(n, 2), start, end, int(sigma)
 
 
-def motion_rgbs(frames, size):
+RESIZERS = ("pil", "device")
+
+
+def motion_rgbs(frames, size, resizer="pil", device=None):
     """[V,3,S,S] float32 in [-1, 1]: every frame's image resized bicubically to S x S, ToTensor, Normalize(0.5, 0.5) (demo.py:109-127).
-    PIL's Image.resize(BICUBIC) is what torchvision's Resize calls for a PIL image."""
+    PIL's Image.resize(BICUBIC) is what torchvision's Resize calls for a PIL image.
+    resizer "pil": one Image.resize per view on the host; a CPU tensor.  "device": the images -- all RGB and of one size, anything
+    else raises -- are uploaded once as [V,H,W,3] bytes and resized in one ops.pil_resize call, PIL's bytes; the normalisation is a
+    256-entry table made on the host by the host route's own statements, so the floats are the host route's bit for bit (a division
+    on the device is a product with a reciprocal, which is not).  A tensor on `device` (default: the current GPU)."""
     from PIL import Image
+    if resizer not in RESIZERS:
+        raise ValueError(f"resizer must be one of {RESIZERS}, got {resizer!r}")
+    if resizer == "device":
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        images = [fr["image"] for fr in frames]
+        odd = [(k, getattr(im, "mode", type(im).__name__), getattr(im, "size", None)) for k, im in enumerate(images)
+               if not isinstance(im, Image.Image) or im.mode != "RGB" or im.size != images[0].size]
+        if not images or odd:
+            raise ValueError(f"motion_rgbs(resizer='device') takes RGB PIL images of one size; (frame, mode, size) of the others: {odd}")
+        rgb8 = ops.pil_resize(_upload(np.stack([np.asarray(im, np.uint8) for im in images]), dev), (size, size))
+        table = (torch.arange(256).float().div(255) - 0.5) / 0.5
+        floats = torch.index_select(table.to(dev), 0, rgb8.reshape(-1).int())          # (a uint8 index would be read as a mask)
+        return floats.view(rgb8.shape).permute(0, 3, 1, 2).contiguous()
     out = np.empty((len(frames), 3, size, size), np.float32)
     for k, fr in enumerate(frames):
         im = np.asarray(fr["image"].convert("RGB").resize((size, size), Image.BICUBIC), np.uint8)
@@ -737,16 +762,19 @@ def motion_rgbs(frames, size):
     return torch.from_numpy(out)
 
 
-def estimate_flows(train_data, estimator=None, size=768, device=None):
+def estimate_flows(train_data, estimator=None, size=768, device=None, resizer="pil"):
     """MotionOptimization.estimate_flow (train_motion.py:368-374): appends a [1,2,H,W] float32 CPU tensor to every frame's T2C_flow.
     The reference builds its estimator, loads its weights and runs the arithmetic around it on the CPU once per view; here the
     hints of all views are selected on the host (hint_arguments, in frame order, so sigma is drawn as the reference draws it) and
     the arithmetic runs on the device for all views at once: ops.hint_field in front of the estimator, ops.flow_finish behind it.
     estimator: a callable (motion_rgbs [V,3,S,S], mask_s [V,1,S,S], hints [V,2,S,S]) -> pred [V,2,S,S] on the device -- the user's
-    own network (the reference's SPADEUnetMaskMotion.forward_flow(...)["PredMotion"]), loaded once.  estimator=None takes pred = hints:
+    own network (the reference's SPADEUnetMaskMotion.forward_flow(...)["PredMotion"]), loaded once; resizer: who resizes the images
+    it is given, motion_rgbs' argument ("pil" on the host, "device": the same floats).  estimator=None takes pred = hints:
     the dense hint field itself as the motion -- a SUBSTITUTE for the reference's estimator that needs no checkpoint, not its output
     (as cinemagraph.pixel_video is for the video generator).  size: the estimator's working size (config.yaml's data.W)."""
     dev = torch.device("cuda" if device is None else device)
+    if resizer not in RESIZERS:
+        raise ValueError(f"resizer must be one of {RESIZERS}, got {resizer!r}")
     frames = train_data["frames"]
     if not frames:
         raise ValueError("train_data has no frames")
@@ -765,7 +793,7 @@ def estimate_flows(train_data, estimator=None, size=768, device=None):
         pred = hints
     else:
         with torch.no_grad():
-            pred = estimator(up(motion_rgbs(frames, size)), mask_s, hints)
+            pred = estimator(up(motion_rgbs(frames, size, resizer=resizer, device=dev)), mask_s, hints)
         if tuple(pred.shape) != tuple(hints.shape):
             raise ValueError(f"the estimator must return [{V}, 2, {size}, {size}], got {tuple(pred.shape)}")
         pred = pred.detach().to(torch.float32).contiguous()
@@ -816,14 +844,15 @@ def flow_image(flow):
 
 
 def build_stage1(input_dir, depth, flow="hints", train_iteration=200, video="none", render_poses=None, internal_poses=None, size=768,
-                 n_frames=120, video_size=1024, device=None):
+                 n_frames=120, video_size=1024, device=None, video_writer=None):
     """Stage 1 from an input folder, as train_motion.py:442-464 runs it: image.png, image_json/mask.png and the hints of image.json ->
     MOM/train_data.pth, MOM/scene_flow.pth and MOM/Flow_viz/%03d.png, what stage 2 (Trainer) reads.
     depth: float32 [H,W] or the path of a .npy holding it -- what the reference's depth network returns for the image
     (d_model.infer_pil; the network is not part of this package).  flow: "hints" (estimate_flows without an estimator: the hint
     field as the motion, a SUBSTITUTE for the reference's flow estimator) or the estimator callable of estimate_flows.
     render_poses / internal_poses: [n,3,4] world-to-camera, by default pcd_gen_poses('lookaround') / ('hemisphere').
-    video="pixels" also writes MOM/video/%06d.png with write_pixel_video (again a substitute, for the reference's GAN).
+    video="pixels" also writes MOM/video/%06d.png with write_pixel_video (again a substitute, for the reference's GAN), through its
+    writer `video_writer` ("host", the default, or "device").
     The renders, the flow arithmetic, the sampling, the fit and our_flow all run on the device (render_pcd, estimate_flows,
     optimize_motion with the device sampler and resampler).  Returns (train_data, scene_flow [3,P] CPU)."""
     from PIL import Image
@@ -860,7 +889,7 @@ def build_stage1(input_dir, depth, flow="hints", train_iteration=200, video="non
     torch.save(train_data, os.path.join(mom, "train_data.pth"))
     torch.save(scene_flow, os.path.join(mom, "scene_flow.pth"))
     if video == "pixels":
-        write_pixel_video(input_dir, n_frames, video_size)
+        write_pixel_video(input_dir, n_frames, video_size, writer=video_writer)
     return train_data, scene_flow
 
 
@@ -879,6 +908,9 @@ def main(argv=None):
                     "for the reference's StyleGAN video, which needs checkpoints; no mp4 is written")
     ap.add_argument("--n_frames", type=int, default=120, help="frames of the --video loop (the reference's option.py:35)")
     ap.add_argument("--video_size", type=int, default=1024, help="side of the square the --video warp runs at (main_jih.py:33-39)")
+    ap.add_argument("--video-writer", dest="video_writer", choices=("host", "device"), default="host", help="--video pixels: who resizes "
+                    "and encodes the frames -- the host (PIL and zlib on the calling thread), or the device as each frame is made; the "
+                    "files decode to the same pixels")
     ap.add_argument("--build", action="store_true", help="build stage 1 from the folder's image.png, image.json and image_json/mask.png "
                     "(build_stage1): writes MOM/train_data.pth, MOM/scene_flow.pth and MOM/Flow_viz; with --video pixels the frames too")
     ap.add_argument("--depth", help="--build: a .npy with the image's float32 [H,W] depth (the depth network is the user's own)")
@@ -896,12 +928,13 @@ def main(argv=None):
             np.random.seed(a.seed)
         poses = None if a.render_poses is None else pcd_gen_poses("lookaround")[:a.render_poses]
         data, flow = build_stage1(a.input_dir, a.depth, flow=a.flow, train_iteration=a.train_iteration, video=a.video,
-                                  render_poses=poses, size=a.size, n_frames=a.n_frames, video_size=a.video_size)
+                                  render_poses=poses, size=a.size, n_frames=a.n_frames, video_size=a.video_size,
+                                  video_writer=a.video_writer)
         print(f"{os.path.join(a.input_dir, 'MOM')}: {len(data['frames'])} frames; scene_flow.pth: {tuple(flow.shape)}, largest "
               f"magnitude {float(flow.abs().max()):.6g}")
         return
     if a.video == "pixels":
-        paths = write_pixel_video(a.input_dir, a.n_frames, a.video_size)
+        paths = write_pixel_video(a.input_dir, a.n_frames, a.video_size, writer=a.video_writer)
         print(f"{os.path.dirname(paths[0])}: {len(paths)} frames")
         return
     flow = refit_scene_flow(a.input_dir, a.train_iteration, sampler=a.sampler, resampler=a.resampler)

@@ -871,6 +871,87 @@ def png_encode(rgb8, out, out_size, scratch):
     return out
 
 
+# --------------------------------------------------------------------------- PIL's bicubic resize (csrc/pil_resize.hip)
+_PIL_TABLES = {}          # (device, in, out) -> (bounds [out,2], kk [out,ksize]) int32 on the device, uploaded once
+
+
+def pil_resize_coeffs(in_size, out_size):
+    """PIL's bicubic resampling tables of one axis on the host (mom_pil_resize_coeffs; no GPU): bounds [out,2] = (xmin, n) and
+    kk [out,ksize] int32, the weights in 22 fractional bits."""
+    ksize = int(N.lib().mom_pil_resize_ksize(in_size, out_size, N.RESIZE_BICUBIC))
+    if ksize < 1:
+        raise N.MomError(f"pil_resize: no bicubic tables for {in_size} -> {out_size} samples")
+    bounds, kk = np.empty((out_size, 2), np.int32), np.empty((out_size, ksize), np.int32)
+    N.check(N.lib().mom_pil_resize_coeffs(in_size, out_size, N.RESIZE_BICUBIC, bounds.ctypes.data, kk.ctypes.data), "mom_pil_resize_coeffs")
+    return bounds, kk
+
+
+def _pil_tables(in_size, out_size, dev):
+    if in_size == out_size:
+        return None, None                # the axis is skipped, its tables are not read
+    key = (dev, in_size, out_size)
+    if key not in _PIL_TABLES:
+        _PIL_TABLES[key] = tuple(torch.from_numpy(a).to(dev) for a in pil_resize_coeffs(in_size, out_size))
+    return _PIL_TABLES[key]
+
+
+def pil_resize_scratch(shape, size, device):
+    """The uint8 intermediate pil_resize needs for images of `shape` ([N,H,W,C], [H,W,C] or [H,W]) resized to size = (OW, OH), or
+    None when it needs none (the height does not change); reusable by later calls on the same stream."""
+    N_, H, W, C_ = _pil_shape(shape)
+    n = int(N.lib().mom_pil_resize_scratch_bytes(N_, H, W, C_, int(size[1]), int(size[0])))
+    return torch.empty(n, dtype=torch.uint8, device=device) if n else None
+
+
+def _pil_shape(shape):
+    shape = tuple(int(s) for s in shape)
+    if len(shape) == 2:
+        return (1,) + shape + (1,)
+    if len(shape) == 3:
+        return (1,) + shape
+    if len(shape) == 4:
+        return shape
+    raise N.MomError(f"pil_resize: images are [N,H,W,C], [H,W,C] or [H,W], got {list(shape)}")
+
+
+def pil_resize(src, size, to8b=False, out=None, scratch=None):
+    """PIL's Image.resize(size, Image.BICUBIC) of 8-bit "L" or "RGB" images, byte for byte, on the device (csrc/pil_resize.hip; the
+    arithmetic is include/mom4d.h's).  src: uint8 [N,H,W,C], [H,W,C] or [H,W] with C 1 or 3 (RGBA is refused: PIL premultiplies
+    alpha there); size = (OW, OH) as PIL takes it; returns uint8 of src's rank at [OH,OW].  to8b=True: src is float32 and every
+    sample first goes through (x * 255).astype(uint8) -- truncated, and clamped to 0..255 where numpy's cast is platform-defined.
+    out: where the result goes (uint8, contiguous, the result's shape) -- an AsyncPNGWriter's slot, say; scratch: the intermediate
+    of pil_resize_scratch, for a caller that resizes many frames of one shape.  The coefficient tables are computed on the host once
+    per (device, in, out) and stay on the device.  One launch per axis on the current stream, nothing is read back."""
+    _need_cuda(src, "pil_resize")
+    want = torch.float32 if to8b else torch.uint8
+    if src.dtype != want or not src.is_contiguous():
+        raise N.MomError(f"pil_resize: src must be a contiguous {want} tensor (to8b={bool(to8b)}), got {src.dtype} {list(src.shape)}"
+                         f"{'' if src.is_contiguous() else ', not contiguous'}")
+    N_, H, W, C_ = _pil_shape(src.shape)
+    OW, OH = int(size[0]), int(size[1])
+    if C_ not in (1, 3) or min(N_, H, W, OW, OH) < 1:
+        raise N.MomError(f"pil_resize: {N_} images of {H} x {W} x {C_} -> {OH} x {OW}: one or three channels and sizes >= 1 are needed")
+    dev = src.device
+    shape = {2: (OH, OW), 3: (OH, OW, C_), 4: (N_, OH, OW, C_)}[src.dim()]
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    else:
+        _typed("pil_resize", dev, ("out", out, shape, torch.uint8))
+    need = int(N.lib().mom_pil_resize_scratch_bytes(N_, H, W, C_, OH, OW))
+    if need and scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif need and (scratch.dtype != torch.uint8 or scratch.device != dev or not scratch.is_contiguous() or scratch.numel() < need):
+        raise N.MomError(f"pil_resize: scratch must be a contiguous uint8 tensor of at least {need} elements on {dev}, "
+                         f"got {scratch.dtype} {list(scratch.shape)} on {scratch.device}")
+    bx, kx = _pil_tables(W, OW, dev)
+    by, ky = _pil_tables(H, OH, dev)
+    fn = N.lib().mom_pil_resize_to8b if to8b else N.lib().mom_pil_resize
+    N.check(fn(N_, H, W, C_, src.data_ptr(), OH, OW, N.RESIZE_BICUBIC, N.ptr(bx), N.ptr(kx), N.ptr(by), N.ptr(ky), out.data_ptr(),
+               N.ptr(scratch) if need else None, need, N.current_stream()),
+            "mom_pil_resize_to8b" if to8b else "mom_pil_resize")
+    return out
+
+
 # --------------------------------------------------------------------------- scattered values -> the pixel grid (stage 1)
 def _tri_views(name, pts, pt_off, H, W):
     """Checks shared by tri_resample and pcd_compose; returns (V, N, device)."""

@@ -104,6 +104,33 @@ class AsyncPNGWriter:
         ev.record()
         self.futures.append(self.pool.submit(self._encode, slot, ev, path))
 
+    def submit_rgb8(self, rgb8, path):
+        """submit() without its quantisation launch, for a frame that is bytes already: rgb8 [H,W,C] uint8, contiguous, on the GPU
+        (what ops.pil_resize writes).  Everything that reads rgb8 is enqueued on the current stream before this returns, so the caller
+        may overwrite it with work enqueued on that stream afterwards.  Both encoders."""
+        if not (torch.is_tensor(rgb8) and rgb8.is_cuda and rgb8.dtype == torch.uint8 and rgb8.is_contiguous()
+                and tuple(rgb8.shape) == (self.H, self.W, self.C)):
+            raise N.MomError(f"submit_rgb8 takes a contiguous uint8 [{self.H},{self.W},{self.C}] tensor on the GPU, got "
+                             + (f"{rgb8.dtype} {list(rgb8.shape)} on {rgb8.device}" if torch.is_tensor(rgb8) else type(rgb8).__name__))
+        slot = self.free.get()
+        if self.zcap:
+            if self.zdev[slot] is None or self.zdev[slot][0].device != rgb8.device:
+                self.zdev[slot] = (torch.empty(self.zcap + 4, dtype=torch.uint8, device=rgb8.device),
+                                   torch.empty(N.lib().mom_png_scratch_bytes(self.C, self.H, self.W), dtype=torch.uint8,
+                                               device=rgb8.device))
+            z, scratch = self.zdev[slot]
+            N.check(N.lib().mom_png_encode(self.C, self.H, self.W, rgb8.data_ptr(), z.data_ptr(), self.zcap,
+                                           z.data_ptr() + self.zcap, scratch.data_ptr(), N.current_stream()), "mom_png_encode")
+            self.zhost[slot].copy_(z, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self.futures.append(self.pool.submit(self._frame, slot, ev, path))
+            return
+        self.host[slot].copy_(rgb8, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.futures.append(self.pool.submit(self._encode, slot, ev, path))
+
     def _frame(self, slot, ev, path):
         try:
             ev.synchronize()

@@ -871,6 +871,46 @@ int mom_jpeg_encode_host(int H, int W, const uint8_t* rgb8, size_t row_stride, i
                          uint32_t* out_size);
 int mom_jpeg_tables(int Q, uint8_t* quant, uint8_t* dht_counts, uint8_t* dht_symbols, int* dht_nsymbols, int* restart_interval);
 
+/* ---- PIL's 8-bit bicubic resize on the device (csrc/pil_resize.hip): the bytes of Image.resize((OW, OH), Image.BICUBIC) of an "L"
+ * (C = 1) or "RGB" (C = 3) image, what stage 1 resizes its video frames and the flow estimator's inputs with (train_motion.py:407,
+ * demo.py:109-127).  PIL resamples an axis of `in` samples to `out` with integer arithmetic on coefficients computed in double:
+ *   scale = in / out, fs = max(scale, 1), support = 2 fs, ksize = (int)ceil(support) * 2 + 1; for the output index xx:
+ *   center = (xx + 0.5) scale, xmin = max((int)(center - support + 0.5), 0), n = min((int)(center + support + 0.5), in) - xmin,
+ *   w[x] = f((x + xmin - center + 0.5) * (1 / fs)) for x < n, with f the cubic convolution kernel at a = -0.5; the weights are summed
+ *   left to right and divided by a non-zero sum; k = (int)(w 2^22 + 0.5) for w >= 0 and (int)(w 2^22 - 0.5) below; a sample is
+ *   clamp((2^21 + sum byte k) >> 22, 0, 255), the shift arithmetic on the signed 32-bit sum.
+ * The horizontal axis goes first and is rounded to bytes, the vertical axis runs on those bytes; an axis with in == out is skipped,
+ * and with both skipped the result is a copy.  "RGBA" is refused: PIL premultiplies alpha there, which is another arithmetic.
+ *   _ksize           host, no GPU: ksize of (in_size, out_size)
+ *   _coeffs          host, no GPU: bounds [out_size][2] = (xmin, n) and kk [out_size][ksize], zero behind n -- the tables a caller
+ *                    uploads once per (in_size, out_size) and keeps
+ *   _scratch_bytes   bytes of the intermediate mom_pil_resize needs: N H rows of OW C bytes at a pitch of 16; 0 when H == OH (the
+ *                    vertical axis is skipped and nothing is staged) and for a shape that is refused
+ *   mom_pil_resize   src [N,H,W,C] bytes -> out [N,OH,OW,C] bytes.  bounds_x / kk_x: the DEVICE tables of (W, OW), bounds_y / kk_y of
+ *                    (H, OH); the pair of a skipped axis is not read and may be null.  scratch: device, 16-byte aligned.  One launch
+ *                    per axis (a copy kernel when none changes) on `stream`: no allocation, no copy, no synchronisation, no atomics.
+ *                    Windows read from the tables are clamped to the image, so wrong tables give wrong pixels, never a read outside src.
+ *   _to8b            the same kernels reading src [N,H,W,C] float32: each sample first goes through (uint8)(x * 255.0f) -- the float32
+ *                    product, truncated, clamped to 0..255 -- which is numpy's (frame * 255).astype(np.uint8) of train_motion.py:407
+ *                    for x in (-1/255, 256/255); outside that interval numpy's cast is platform-defined and the clamp is this
+ *                    library's choice (a NaN gives 0)
+ *   _host            the bytes of mom_pil_resize computed on the host from host pointers, tables and all: a test seam like
+ *                    mom_png_encode_host, not a fallback -- nothing in the package calls it
+ * filter: MOM_RESIZE_BICUBIC, PIL's value.  Another filter, C other than 1 or 3, a size below 1, any of the three images at 2^31
+ * bytes or more, a null or misaligned pointer, a scratch too small: MOM_EINVAL before anything is launched or written.  So is
+ * H > 100 W with OH < H and OW != W: recent Pillow (Image.resize, its Python part) resamples such a strip vertically first, which
+ * rounds differently, and that order is not built. */
+#define MOM_RESIZE_BICUBIC 3
+int mom_pil_resize_ksize(int in_size, int out_size, int filter);
+int mom_pil_resize_coeffs(int in_size, int out_size, int filter, int* bounds, int* kk);
+size_t mom_pil_resize_scratch_bytes(int N, int H, int W, int C, int OH, int OW);
+int mom_pil_resize(int N, int H, int W, int C, const uint8_t* src, int OH, int OW, int filter, const int* bounds_x, const int* kk_x,
+                   const int* bounds_y, const int* kk_y, uint8_t* out, void* scratch, size_t scratch_bytes, mom_stream_t stream);
+int mom_pil_resize_to8b(int N, int H, int W, int C, const float* src, int OH, int OW, int filter, const int* bounds_x,
+                        const int* kk_x, const int* bounds_y, const int* kk_y, uint8_t* out, void* scratch, size_t scratch_bytes,
+                        mom_stream_t stream);
+int mom_pil_resize_host(int N, int H, int W, int C, const uint8_t* src, int OH, int OW, int filter, uint8_t* out);
+
 const char* mom_version(void);
 
 /* Per-kernel HIP-event timing (bench.py's live roofline figure).  Slots: see mom_profile_name(0..15).
