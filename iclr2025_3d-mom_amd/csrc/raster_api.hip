@@ -13,6 +13,14 @@ int mom_launch_render_bwd(const MomRasterArgs* a, const GeomView& g, const BinVi
                           const float* dL_dpix, const float* dL_ddepth, hipStream_t s);
 int mom_launch_preprocess_bwd(const MomRasterArgs* a, const int* radii, const GeomView& g, const MomRasterGrads* gr, const MomRasterAccum* acc,
                               hipStream_t s);
+// the ordered backward reduction (raster_ordered.hip; its compositing kernel: raster_render.hip)
+size_t mom_ordered_plan_view(char* base, int P, uint32_t** slot_base, unsigned long long** chunk_sums);
+int mom_launch_ordered_plan(int P, const GeomView& g, char* plan, uint32_t* total_dev, uint32_t* total_host, hipStream_t s);
+int mom_launch_render_bwd_ordered(const MomRasterArgs* a, const GeomView& g, const BinView& b, const ImageView& im, size_t capacity,
+                                  const float* dL_dpix, const float* dL_ddepth, const uint32_t* slot_base, float* partials, uint32_t slots,
+                                  uint32_t* status, hipStream_t s);
+int mom_launch_ordered_reduce(int P, const GeomView& g, const uint32_t* slot_base, const float* partials, uint32_t slots, uint32_t* status,
+                              hipStream_t s);
 
 static int check_args(const MomRasterArgs* a)
 {
@@ -245,6 +253,96 @@ int mom_raster_backward(const MomRasterArgs* a, const int* radii, void* geom, vo
     rc = mom_raster_backward_render(a, geom, binning, capacity, image, dL_dout_color, dL_dout_depth, stream);
     if (rc) return rc;
     return mom_raster_backward_geometry(a, radii, geom, gr, stream);
+}
+
+size_t mom_raster_ordered_plan_bytes(int P) { return P < 0 ? 0 : mom_ordered_plan_view(nullptr, P, nullptr, nullptr) + MOM_ALIGN; }
+size_t mom_raster_ordered_bytes(int P, size_t slots)
+{
+    (void)P;
+    return slots >= 0xFFFFFFFFull ? 0 : mom_align_up(slots * MOM_ORDERED_SLOT_BYTES) + 2 * MOM_ALIGN;
+}
+
+// what the ordered forms refuse on top of check_args (the frame's state is not what they need, or the buffers cannot hold it)
+static int check_ordered(const MomRasterArgs* a, const void* plan, const void* partials, size_t partials_bytes, size_t slots,
+                         const uint32_t* status_dev)
+{
+    if (a->forward_only) return MOM_EINVAL;                                 // no final_T / n_contrib to walk back from
+    if (a->tile_row0 != 0 || a->tile_row1 != 0) return MOM_EINVAL;          // a shard's partial record would be summed over ranks: not ordered
+    if (!plan || !partials || !status_dev) return MOM_EINVAL;
+    const size_t need = mom_raster_ordered_bytes(a->P, slots);
+    if (need == 0 || partials_bytes < need) return MOM_EINVAL;
+    return MOM_OK;
+}
+
+int mom_raster_ordered_plan(const MomRasterArgs* a, void* geom, void* plan, uint32_t* total_dev, uint32_t* total_host, mom_stream_t stream)
+{
+    int rc = check_args(a);
+    if (rc) return rc;
+    if (!plan) return MOM_EINVAL;
+    if (a->P == 0) {                            // no Gaussian, no slot: slot_base[0] = 0
+        if (hipMemsetAsync(mom_align_ptr(plan), 0, 4, (hipStream_t)stream) != hipSuccess) return MOM_ELAUNCH;
+        if (total_dev && hipMemsetAsync(total_dev, 0, 4, (hipStream_t)stream) != hipSuccess) return MOM_ELAUNCH;
+        if (total_host) *total_host = 0;
+        return MOM_OK;
+    }
+    if (!geom) return MOM_EINVAL;
+    GeomView g;
+    geom_view(mom_align_ptr(geom), a->P, &g);
+    rc = mom_launch_ordered_plan(a->P, g, mom_align_ptr(plan), total_dev, total_host, (hipStream_t)stream);
+    if (rc) return rc;
+    MOM_CHECK_LAUNCH(a, (hipStream_t)stream);
+    return MOM_OK;
+}
+
+int mom_raster_backward_render_ordered(const MomRasterArgs* a, void* geom, void* binning, size_t capacity, void* image,
+                                       const float* dL_dout_color, const float* dL_dout_depth, const void* plan, void* partials,
+                                       size_t partials_bytes, size_t slots, uint32_t* status_dev, mom_stream_t stream)
+{
+    int rc = check_args(a);
+    if (rc) return rc;
+    rc = check_ordered(a, plan, partials, partials_bytes, slots, status_dev);
+    if (rc) return rc;
+    if (a->P == 0) return MOM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (!geom || !binning || !image || !dL_dout_color) return MOM_EINVAL;
+    GeomView g; ImageView im; BinView b;
+    geom_view(mom_align_ptr(geom), a->P, &g);
+    image_view(mom_align_ptr(image), a->W, a->H, &im);
+    bin_view(mom_align_ptr(binning), capacity, &b);
+    uint32_t* slot_base;
+    mom_ordered_plan_view(mom_align_ptr(const_cast<void*>(plan)), a->P, &slot_base, nullptr);
+    float* part = reinterpret_cast<float*>(mom_align_ptr(partials));
+    rc = mom_launch_render_bwd_ordered(a, g, b, im, capacity, dL_dout_color, dL_dout_depth, slot_base, part, (uint32_t)slots, status_dev, s);
+    if (rc) return rc;
+    MOM_CHECK_LAUNCH(a, s);
+    rc = mom_launch_ordered_reduce(a->P, g, slot_base, part, (uint32_t)slots, status_dev, s);
+    if (rc) return rc;
+    MOM_CHECK_LAUNCH(a, s);
+    return MOM_OK;
+}
+
+int mom_raster_backward_ordered(const MomRasterArgs* a, const int* radii, void* geom, void* binning, size_t capacity, void* image,
+                                const float* dL_dout_color, const float* dL_dout_depth, const MomRasterGrads* gr, const void* plan,
+                                void* partials, size_t partials_bytes, size_t slots, uint32_t* status_dev, mom_stream_t stream)
+{
+    int rc = check_args(a);                     // every argument is checked before anything is launched
+    if (rc) return rc;
+    rc = check_ordered(a, plan, partials, partials_bytes, slots, status_dev);
+    if (rc) return rc;
+    if (a->P == 0) return MOM_OK;
+    if (!geom || !binning || !image || !radii || !dL_dout_color) return MOM_EINVAL;
+    rc = check_grads(a, gr);
+    if (rc) return rc;
+    rc = mom_raster_backward_render_ordered(a, geom, binning, capacity, image, dL_dout_color, dL_dout_depth, plan, partials, partials_bytes,
+                                            slots, status_dev, stream);
+    if (rc) return rc;
+    return mom_raster_backward_geometry(a, radii, geom, gr, stream);
+}
+
+int mom_raster_backward_ordered_acc(const MomRasterArgs*, const int*, void*, void*, size_t, void*, const float*, const float*,
+                                    const MomRasterGrads*, const MomRasterAccum*, const void*, void*, size_t, size_t, uint32_t*, mom_stream_t)
+{
+    return MOM_EINVAL;                          // a camera batch's accumulating backward has no ordered form
 }
 
 int mom_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,

@@ -500,12 +500,38 @@ __device__ __forceinline__ float swap_add32(float a, float b)
 // are applied; slots 2-4 the conic's, without their -1/2.  The projection backward (raster_backward.hip) applies the matrix and
 // those constants once per Gaussian instead of this loop once per (pixel, splat) pair.  The record stays linear in dL/dpixel, so
 // the ranks of a tile-row shard still sum it (mom_raster_backward_render in include/mom4d.h).
-template <bool DEPTH>
+//
+// ORDERED (mom_raster_backward_render_ordered, include/mom4d.h): the one order-dependent operation of the rasterizer is the atomicAdd in
+// `push` below.  With ORDERED the staging thread puts the entry's SLOT (ordered_slot) where the unordered form keeps the Gaussian's
+// index, and `push` stores the wave's totals at partials[slot][wave][value] -- `gacc` is that buffer -- with plain stores: every
+// (slot, wave) is written at most once, a splat being in a tile's list once.  The totals themselves do not depend on a splat's place
+// in its group of four (each is (row 0 + row 1) + (row 2 + row 3) of its own row totals) nor on the list it came from.  The
+// <DEPTH, false> instantiations are the code this kernel was before the parameter existed (OrderedArgs<false> is empty).
+template <bool ORDERED> struct OrderedArgs {};
+template <> struct OrderedArgs<true> {
+    const uint32_t* slot_base;   // [P + 1]
+    uint32_t* status;            // MOM_ORDERED_* bits
+    uint32_t slots;
+    int gy;
+};
+constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
+// Slot of (Gaussian id, tile tx ty), or kNoSlot -- with MOM_ORDERED_BAD_SLOT raised -- when the tile is not in the rectangle the
+// record describes or the slot is not below `slots`: such an entry is never stored (a plan that belongs to another frame).
+__device__ __forceinline__ uint32_t ordered_slot(const OrderedArgs<true>& oa, uint32_t id, float x, float y, int radius, int gx, int tx, int ty)
+{
+    int x0, y0, x1, y1;
+    mom_get_rect(x, y, radius, gx, oa.gy, x0, y0, x1, y1);
+    const uint32_t sl = oa.slot_base[id] + (uint32_t)((ty - y0) * (x1 - x0) + (tx - x0));
+    if (radius > 0 && tx >= x0 && tx < x1 && ty >= y0 && ty < y1 && sl < oa.slots) return sl;
+    atomicOr(oa.status, (uint32_t)MOM_ORDERED_BAD_SLOT);
+    return kNoSlot;
+}
+template <bool DEPTH, bool ORDERED>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MOM_BWD_WAVES, MOM_BWD_WAVES)))   // LDS (31 KB) allows 5 workgroups per CU
 render_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, int W, int H, int gx, int nt, int t0, int run,
                   const uint32_t* __restrict__ tile_order, const uint32_t* __restrict__ order_hdr, const float4* __restrict__ rec, const float* __restrict__ bg, const float* __restrict__ final_Ts,
                   const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpixels,
-                  const float* __restrict__ dL_dpixel_depths, float* __restrict__ gacc, uint32_t capacity)
+                  const float* __restrict__ dL_dpixel_depths, float* __restrict__ gacc, uint32_t capacity, OrderedArgs<ORDERED> oa)
 {
     __shared__ float4 s_rec[kRoundB * 3];
     __shared__ uint32_t s_id[kRoundB];
@@ -574,7 +600,14 @@ render_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__
             } else {
                 const float tot = swap_add32(h1, t);                   // row q: the totals of the group's splat q
                 const uint32_t jq = (((lane & 32) ? (uint32_t)(jp >> 32) : (uint32_t)jp) >> row_shift) & 0xFFFFu;     // two 32-bit halves: no 64-bit vector shift
-                if (vslot < kVals && (lane >> 4) < n_real) atomicAdd(&gacc[(size_t)s_id[jq] * MOM_GACC_FLOATS + vslot], tot);
+                if constexpr (ORDERED) {
+                    if (vslot < kVals && (lane >> 4) < n_real) {
+                        const uint32_t sl = s_id[jq];
+                        if (sl != kNoSlot) gacc[((size_t)sl * 4 + wv) * MOM_ORDERED_VALUES + vslot] = tot;
+                    }
+                } else {
+                    if (vslot < kVals && (lane >> 4) < n_real) atomicAdd(&gacc[(size_t)s_id[jq] * MOM_GACC_FLOATS + vslot], tot);
+                }
                 npend = 0;
             }
         }
@@ -620,14 +653,20 @@ render_bwd_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__
             const int progress = i * kRoundB + slot;
             if (range.x + progress < range.y) {
                 const uint32_t id = point_list[range.y - progress - 1];
-                s_id[slot] = id;
+                if constexpr (!ORDERED) s_id[slot] = id;
                 float4 q0 = rec[3 * (size_t)id + 0];
                 const float4 q1 = rec[3 * (size_t)id + 1];
                 q0.w = power_bound(q1.w);
                 reach = strip_reach_mask(q0, q1, (float)(tx * MOM_TILE), (float)(ty * MOM_TILE));
                 s_rec[slot * 3 + 0] = q0;
                 s_rec[slot * 3 + 1] = q1;
-                s_rec[slot * 3 + 2] = rec[3 * (size_t)id + 2];
+                if constexpr (ORDERED) {
+                    const float4 q2 = rec[3 * (size_t)id + 2];
+                    s_id[slot] = ordered_slot(oa, id, q0.x, q0.y, __float_as_int(q2.w), gx, tx, ty);
+                    s_rec[slot * 3 + 2] = q2;
+                } else {
+                    s_rec[slot * 3 + 2] = rec[3 * (size_t)id + 2];
+                }
             }
             s_mask[slot] = (uint8_t)reach;                  // slots past the end of the list: unreachable
         }
@@ -770,24 +809,50 @@ int mom_launch_render_fwd(const MomRasterArgs* a, const GeomView& g, const BinVi
     return hipGetLastError() == hipSuccess ? MOM_OK : MOM_ELAUNCH;
 }
 
-int mom_launch_render_bwd(const MomRasterArgs* a, const GeomView& g, const BinView& b, const ImageView& im, size_t capacity,
-                          const float* dL_dpix, const float* dL_ddepth, hipStream_t s)
+// ordered: null (the atomic form), or the ordered reduction's plan -- `out` is then the partials buffer instead of the accumulator record
+static int launch_render_bwd(const MomRasterArgs* a, const GeomView& g, const BinView& b, const ImageView& im, size_t capacity,
+                             const float* dL_dpix, const float* dL_ddepth, float* out, const OrderedArgs<true>* ordered, hipStream_t s)
 {
     const int gx = (a->W + MOM_TILE - 1) / MOM_TILE, gy = (a->H + MOM_TILE - 1) / MOM_TILE;
     const uint32_t cap = capacity > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)capacity;
-    if (!a->accum_cleared && hipMemsetAsync(g.gacc, 0, (size_t)a->P * MOM_GACC_FLOATS * 4, s) != hipSuccess) return MOM_ELAUNCH;
     MomProfScope ps(MOM_P_RENDER_BWD, s);
     int ry0, ry1;
     mom_tile_rows(a, gy, &ry0, &ry1);
     const int nt = gx * (ry1 - ry0);
     if (nt == 0) return MOM_OK;
-    if (dL_ddepth)
-        hipLaunchKernelGGL(render_bwd_kernel<true>, dim3(nt), dim3(256), 0, s, im.ranges, b.point_list, a->W, a->H, gx, nt, gx * ry0, tile_run(gx), im.tile_order, im.hdr,
-                           g.rec, a->background, im.final_T, im.n_contrib, dL_dpix, dL_ddepth, g.gacc, cap);
-    else
-        hipLaunchKernelGGL(render_bwd_kernel<false>, dim3(nt), dim3(256), 0, s, im.ranges, b.point_list, a->W, a->H, gx, nt, gx * ry0, tile_run(gx), im.tile_order, im.hdr,
-                           g.rec, a->background, im.final_T, im.n_contrib, dL_dpix, dL_ddepth, g.gacc, cap);
+#define MOM_BWD_LAUNCH(DEPTH, ORDERED, OA)                                                                                                          \
+    hipLaunchKernelGGL((render_bwd_kernel<DEPTH, ORDERED>), dim3(nt), dim3(256), 0, s, im.ranges, b.point_list, a->W, a->H, gx, nt, gx * ry0, tile_run(gx), \
+                       im.tile_order, im.hdr, g.rec, a->background, im.final_T, im.n_contrib, dL_dpix, dL_ddepth, out, cap, OA)
+    if (ordered) {
+        if (dL_ddepth) MOM_BWD_LAUNCH(true, true, *ordered);
+        else MOM_BWD_LAUNCH(false, true, *ordered);
+    } else {
+        if (dL_ddepth) MOM_BWD_LAUNCH(true, false, OrderedArgs<false>{});
+        else MOM_BWD_LAUNCH(false, false, OrderedArgs<false>{});
+    }
+#undef MOM_BWD_LAUNCH
     return hipGetLastError() == hipSuccess ? MOM_OK : MOM_ELAUNCH;
+}
+
+int mom_launch_render_bwd(const MomRasterArgs* a, const GeomView& g, const BinView& b, const ImageView& im, size_t capacity,
+                          const float* dL_dpix, const float* dL_ddepth, hipStream_t s)
+{
+    if (!a->accum_cleared && hipMemsetAsync(g.gacc, 0, (size_t)a->P * MOM_GACC_FLOATS * 4, s) != hipSuccess) return MOM_ELAUNCH;
+    return launch_render_bwd(a, g, b, im, capacity, dL_dpix, dL_ddepth, g.gacc, nullptr, s);
+}
+
+// The compositing backward of the ordered reduction: clears the partials (slots x MOM_ORDERED_SLOT_BYTES) and fills them.
+int mom_launch_render_bwd_ordered(const MomRasterArgs* a, const GeomView& g, const BinView& b, const ImageView& im, size_t capacity,
+                                  const float* dL_dpix, const float* dL_ddepth, const uint32_t* slot_base, float* partials, uint32_t slots,
+                                  uint32_t* status, hipStream_t s)
+{
+    if (slots && hipMemsetAsync(partials, 0, (size_t)slots * MOM_ORDERED_SLOT_BYTES, s) != hipSuccess) return MOM_ELAUNCH;
+    OrderedArgs<true> oa;
+    oa.slot_base = slot_base;
+    oa.status = status;
+    oa.slots = slots;
+    oa.gy = (a->H + MOM_TILE - 1) / MOM_TILE;
+    return launch_render_bwd(a, g, b, im, capacity, dL_dpix, dL_ddepth, partials, &oa, s);
 }
 
 #ifdef FWD_STAMPS

@@ -36,6 +36,8 @@ _state = {
     "pin_ring": None,          # pinned count words and the next one to hand out: pinned_word() (made on first use -- importing
     "pin_next": 0,             #   this module must not initialise the GPU)
     "post_ring": None,         # PostRing of the async forwards' status words: raster_forward (made on first use, likewise)
+    "deterministic": False,    # set_deterministic()
+    "ordered": None,           # the ordered backward's cached scratch, made by its first call: ordered_backward
 }
 _FLAG_LAG = 4
 
@@ -174,6 +176,62 @@ def set_keep_all_tiles(on: bool) -> None:
     alpha >= 1/255 anywhere in their tile are not binned; images and gradients are bit-identical either way
     (include/mom4d.h, MomRasterArgs.keep_all_tiles).  Forward and backward of one frame must run under the same setting."""
     _state["keep_all_tiles"] = bool(on)
+
+
+def set_deterministic(on: bool) -> None:
+    """True: the backward adds its per-(wave, tile entry) totals up in a defined order (include/mom4d.h, "ordered backward
+    reduction") instead of with float atomics -- rasterize_gaussians_backward and the one-node autograd paths (fused_autograd) then
+    return the same bits for the same inputs, run after run.  Such a backward plans its slots, SYNCHRONISES ONCE with the stream to
+    read their number, keeps a grow-only scratch of 160 bytes per slot (slots = the reference's num_rendered) and runs
+    mom_raster_backward_ordered.  The fused training steps have no ordered form and raise MomError while the switch is on.
+    False (default): the atomic form; nothing of the above is allocated or called."""
+    _state["deterministic"] = bool(on)
+
+
+def deterministic() -> bool:
+    return _state["deterministic"]
+
+
+def refuse_if_deterministic(what):
+    if _state["deterministic"]:
+        raise N.MomError(f"{what} has no ordered backward: it cannot run under diff_gaussian_rasterization._C.set_deterministic(True)")
+
+
+def ordered_status():
+    """MOM_ORDERED_* bits the ordered backwards have raised since the scratch was made (synchronises; 0: every slot was in bounds)."""
+    o = _state["ordered"]
+    return 0 if o is None else int(o["status"].item())
+
+
+def ordered_backward(lib, a, radii, geom, binning, cap, img, dcol, ddep, gr, P, dev, stream):
+    """mom_raster_backward under set_deterministic(True): plan -> grow-only cached scratch -> mom_raster_backward_ordered.  One
+    stream synchronisation, for the slot count.  The sticky status word is looked at here, behind that synchronisation, for the
+    backwards before this one (ordered_status() reads it at once): a slot out of bounds was skipped on the device and is an error."""
+    o = _state["ordered"]
+    if o is None or o["dev"] != dev:
+        o = _state["ordered"] = dict(dev=dev, P=-1, plan=None, partials=None, status=torch.zeros(1, dtype=torch.int32, device=dev),
+                                     total=torch.zeros(1, dtype=torch.int32).pin_memory())
+    if o["P"] < P:
+        o["plan"] = torch.empty(lib.mom_raster_ordered_plan_bytes(P), dtype=torch.uint8, device=dev)
+        o["P"] = P
+    N.check(lib.mom_raster_ordered_plan(C.byref(a), geom.data_ptr(), o["plan"].data_ptr(), None, o["total"].data_ptr(), stream),
+            "mom_raster_ordered_plan")
+    torch.cuda.current_stream().synchronize()
+    bits = int(o["status"].item())
+    if bits:
+        raise N.MomError(f"an ordered backward skipped slots that were out of bounds (status {bits:#x}): its gradients are incomplete")
+    slots = int(o["total"][0]) & 0xFFFFFFFF
+    need = lib.mom_raster_ordered_bytes(P, slots)
+    if need == 0:
+        raise N.MomError(f"the ordered backward cannot index {slots} slots")
+    if o["partials"] is None or o["partials"].numel() < need:
+        o["partials"] = None                                    # (freed before its successor is made)
+        o["partials"] = torch.empty(need + need // 4, dtype=torch.uint8, device=dev)
+    part = o["partials"]
+    N.check(lib.mom_raster_backward_ordered(C.byref(a), radii.data_ptr(), geom.data_ptr(), binning.data_ptr(), int(cap), img.data_ptr(),
+                                            dcol.data_ptr(), None if ddep is None else ddep.data_ptr(), C.byref(gr),
+                                            o["plan"].data_ptr(), part.data_ptr(), part.numel(), slots, o["status"].data_ptr(), stream),
+            "mom_raster_backward_ordered")
 
 
 def last_num_rendered():
@@ -364,9 +422,12 @@ def rasterize_gaussians_backward(bg, means3D, radii, colors, scales, rotations, 
     g.dL_dscales, g.dL_drotations = gsc.data_ptr(), grot.data_ptr()
     dcol = dL_dout_color.contiguous().float()
     ddep = None if dL_dout_depth is None else dL_dout_depth.contiguous().float()
-    N.check(lib.mom_raster_backward(C.byref(a), radii.data_ptr(), geomBuffer.data_ptr(), binningBuffer.data_ptr(), int(R),
-                                    imageBuffer.data_ptr(), dcol.data_ptr(), None if ddep is None else ddep.data_ptr(),
-                                    C.byref(g), N.current_stream()), "mom_raster_backward")
+    if _state["deterministic"]:
+        ordered_backward(lib, a, radii, geomBuffer, binningBuffer, R, imageBuffer, dcol, ddep, g, P, dev, N.current_stream())
+    else:
+        N.check(lib.mom_raster_backward(C.byref(a), radii.data_ptr(), geomBuffer.data_ptr(), binningBuffer.data_ptr(), int(R),
+                                        imageBuffer.data_ptr(), dcol.data_ptr(), None if ddep is None else ddep.data_ptr(),
+                                        C.byref(g), N.current_stream()), "mom_raster_backward")
     del keep
     return g2d, gcol, gop, g3d, gcov, gsh, gsc, grot
 

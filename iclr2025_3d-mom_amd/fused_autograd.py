@@ -260,9 +260,12 @@ def _backward(st, dcolor, ddepth, direct=True):
     if st.field is not None:
         # (scale / rotation / opacity gradients: through their activations inside the projection backward -- act_rotations_raw)
         gr.act_rotations_raw = st.rot_d.data_ptr()
-    N.check(lib.mom_raster_backward(C.byref(st.a), st.radii.data_ptr(), st.geom.data_ptr(), st.binning.data_ptr(), st.cap,
-                                    st.img.data_ptr(), dcol.data_ptr(), None if ddep is None else ddep.data_ptr(), C.byref(gr), s),
-            "raster_bwd")
+    if RC.deterministic():            # the ordered reduction (RC.set_deterministic): one synchronisation, the same bits every run
+        RC.ordered_backward(lib, st.a, st.radii, st.geom, st.binning, st.cap, st.img, dcol, ddep, gr, P, dev, s)
+    else:
+        N.check(lib.mom_raster_backward(C.byref(st.a), st.radii.data_ptr(), st.geom.data_ptr(), st.binning.data_ptr(), st.cap,
+                                        st.img.data_ptr(), dcol.data_ptr(), None if ddep is None else ddep.data_ptr(), C.byref(gr), s),
+                "raster_bwd")
     if st.field is None:              # coarse stage: the raw parameters' gradients are complete
         _pool_give(st.pool_key, b)
         st.bufs = None

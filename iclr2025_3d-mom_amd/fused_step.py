@@ -26,6 +26,7 @@ import torch
 
 from . import _native as N
 from . import ops
+from .diff_gaussian_rasterization import _C as RC
 
 
 class _Step:
@@ -38,6 +39,7 @@ class _Step:
     HEADROOM, MARGIN = 1.5, 65536     # binning capacity = HEADROOM x an earlier frame's instance count + MARGIN
 
     def __init__(self, gaussians, opt, hyper, background):
+        RC.refuse_if_deterministic(type(self).__name__)        # (and again in every step: _ensure)
         self.g, self.opt, self.hyper, self.bg = gaussians, opt, hyper, background
         self.P = -1
         self.lib = N.lib()
@@ -55,6 +57,7 @@ class _Step:
 
     def _ensure(self, P, W, H, dev):
         """The step's buffers: the per-frame ones when the frame changes, the per-Gaussian ones (_per_gaussian) when P does."""
+        RC.refuse_if_deterministic(type(self).__name__)
         pad = self._rows(P)
         key = (P, W, H, pad, dev)
         if key == self._key:

@@ -15,7 +15,7 @@ from .utils.loss_utils import l1_loss, psnr_from_last_l1, ssim
 
 class Trainer:
     def __init__(self, scene, gaussians, opt, hyper, pipe, stage="fine", delta_scale=1, white_background=False,
-                 sync_every_step=True, fused=False, gc_freeze=False):
+                 sync_every_step=True, fused=False, gc_freeze=False, deterministic=False):
         self.scene, self.g, self.opt, self.hyper, self.pipe, self.stage = scene, gaussians, opt, hyper, pipe, stage
         self.delta_scale = delta_scale
         dev = gaussians._xyz.device
@@ -33,6 +33,14 @@ class Trainer:
         # batch_size > 1 drops the fused step again, so that trainer is on the autograd path throughout, as it always was.
         # The fine step is fused_step.fine_step()'s choice by step_features(): FusedStep for the shipped 32 x 2 field, FusedStep16 for two
         # levels of 16-channel planes (dnerf/eulerian_150_16) on one GPU -- parallel.attach() drops the fused step of such a trainer too.
+        # deterministic=True: the rasterizer's backward adds in a defined order (RC.set_deterministic: the switch is process-wide and
+        # stays on); the coarse stage -- activations, rasterizer, L1, Adam -- then repeats bit for bit from the same state.  The fine
+        # stage's field backward still uses float atomics ("Ordered backward reduction"), and the fused steps have no ordered form.
+        if deterministic:
+            if fused:
+                raise RC.N.MomError("Trainer(fused=True, deterministic=True): the fused steps have no ordered backward "
+                                    "(diff_gaussian_rasterization._C.set_deterministic); use fused=False")
+            RC.set_deterministic(True)
         self.fused = None
         if fused and stage in ("fine", "coarse"):
             from .fused_step import FusedCoarseStep, fine_step

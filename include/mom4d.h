@@ -267,6 +267,57 @@ int mom_raster_backward_acc(const MomRasterArgs* a, const int* radii, void* geom
 int mom_raster_backward_geometry_acc(const MomRasterArgs* a, const int* radii, void* geom, const MomRasterGrads* grads,
                                      const MomRasterAccum* accum, mom_stream_t stream);
 
+/* ---- ordered backward reduction: gradients that are a function of their inputs, bit for bit ----------------------------------
+ * mom_raster_backward_render adds every (wave, list entry) total into the per-Gaussian record with float atomics, in whatever
+ * order the waves arrive: two runs differ by about 1e-6 relative.  The _ordered forms store those totals instead and add them up
+ * in a defined order; everything else of the backward is per-Gaussian arithmetic already.
+ *
+ * SLOTS.  A Gaussian g with radius > 0 owns one slot per tile of its rectangle [x0,x1) x [y0,y1) (getRect, auxiliary.h:46-56, as the
+ * projection computed it: tiles_touched of them), row-major, y outer: slot(g, tx, ty) = slot_base[g] + (ty - y0) (x1 - x0) + (tx - x0),
+ * with slot_base the exclusive scan of tiles_touched over the Gaussians.  slot_base[P] is the reference's num_rendered whether or
+ * not keep_all_tiles is set: binning and the tile lists are not involved.
+ * PARTIALS.  partials[slot][wave 0..3][MOM_ORDERED_VALUES] floats (MOM_ORDERED_SLOT_BYTES = 160 bytes per slot), wave = the 8x8 pixel
+ * block of the tile (0: left top, 1: right top, 2: left bottom, 3: right bottom), value k = float k of the accumulator record
+ * (value 9, depth, stays +0.0 without a depth gradient).  The buffer is cleared to +0.0 by the call; a (slot, wave) nothing is
+ * stored into stays +0.0: an instance the default binning culled, a wave the splat cannot reach, entries behind the last contributor.
+ * ORDER.  For value k of a Gaussian with n slots:   t[s] = (p[s][0][k] + p[s][1][k]) + (p[s][2][k] + p[s][3][k]);
+ *   a[r] = (...((+0.0 + t[r]) + t[r+4]) + t[r+8] ...) over s = r, r+4, ... < n, for r = 0..3 (a[r] = +0.0 when r >= n);
+ *   record[k] = (a[0] + a[2]) + (a[1] + a[3]);   record[10], [11] = 0;   n = 0 (radius 0): zeros.
+ * It depends on n alone -- not on the grid, the workgroup count or which lanes are active.  mom_raster_ordered_sum_host reproduces it
+ * on the host (plain C++, compiled without FMA contraction) from a copy of slot_base and partials. */
+#define MOM_ORDERED_VALUES 10
+#define MOM_ORDERED_SLOT_BYTES 160
+/* status bits of the ordered forms (OR-ed into *status_dev, which the caller zeroes): a computed slot lay outside the Gaussian's
+ * rectangle or at/after `slots` and was skipped, never stored (a plan of another frame); the reduction cut a Gaussian's slots at `slots` */
+#define MOM_ORDERED_BAD_SLOT 1
+#define MOM_ORDERED_CUT 2
+/* bytes of the plan buffer (slot_base[P+1] uint32 at its 256-byte aligned start, then the scan's block sums) and of the partials */
+size_t mom_raster_ordered_plan_bytes(int P);
+size_t mom_raster_ordered_bytes(int P, size_t slots);       /* 0: slots is not a count the ordered forms take (>= 2^32 - 1) */
+/* Scans tiles_touched of the geometry scratch a forward of `a` left (two launches) into slot_base[P+1]; the total goes to *total_dev
+ * (uint32, may be null) and, if total_host is not null (pinned host memory), there too by a system-scope store on `stream`.  A total of
+ * 2^32 - 1 or more is reported as 2^32 - 1, which mom_raster_ordered_bytes and the backward refuse. */
+int mom_raster_ordered_plan(const MomRasterArgs* a, void* geom, void* plan, uint32_t* total_dev, uint32_t* total_host,
+                            mom_stream_t stream);
+/* mom_raster_backward_render with the ordered reduction: clears partials, composites, reduces into the accumulator record; followed by
+ * the unchanged mom_raster_backward_geometry.  `plan` as mom_raster_ordered_plan left it for THIS forward, `slots` its total,
+ * partials / partials_bytes a buffer of at least mom_raster_ordered_bytes(P, slots).  MOM_EINVAL before anything is launched: plan,
+ * partials or status_dev null, partials_bytes too small, slots >= 2^32 - 1, a forward_only frame, a tile-row shard (tile_row0 / tile_row1 set). */
+int mom_raster_backward_render_ordered(const MomRasterArgs* a, void* geom, void* binning, size_t capacity, void* image,
+                                       const float* dL_dout_color, const float* dL_dout_depth, const void* plan, void* partials,
+                                       size_t partials_bytes, size_t slots, uint32_t* status_dev, mom_stream_t stream);
+/* The two halves together, mirroring mom_raster_backward. */
+int mom_raster_backward_ordered(const MomRasterArgs* a, const int* radii, void* geom, void* binning, size_t capacity, void* image,
+                                const float* dL_dout_color, const float* dL_dout_depth, const MomRasterGrads* g, const void* plan,
+                                void* partials, size_t partials_bytes, size_t slots, uint32_t* status_dev, mom_stream_t stream);
+/* A camera batch's accumulating backward has no ordered form (its sum over cameras is a separate question): always MOM_EINVAL. */
+int mom_raster_backward_ordered_acc(const MomRasterArgs* a, const int* radii, void* geom, void* binning, size_t capacity, void* image,
+                                    const float* dL_dout_color, const float* dL_dout_depth, const MomRasterGrads* g,
+                                    const MomRasterAccum* accum, const void* plan, void* partials, size_t partials_bytes, size_t slots,
+                                    uint32_t* status_dev, mom_stream_t stream);
+/* The reduction on the host (no GPU needed): slot_base [P+1], partials [slot_base[P]][4][MOM_ORDERED_VALUES] -> gacc [P][MOM_GACC_FLOATS]. */
+int mom_raster_ordered_sum_host(int P, const uint32_t* slot_base, const float* partials, float* gacc);
+
 /* checkFrustum (rasterizer_impl.cu:54-66): present[i] = p_view.z > 0.2 */
 int mom_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                      uint8_t* present, mom_stream_t stream);
