@@ -33,6 +33,10 @@
 // Gaussians): two consecutive 128-byte feature rows are ONE 256-byte load of all 64 lanes, so the trunk layer issues one operand
 // load and two MFMAs per K step where KT = 2 issues two and four, and no lane is masked.
 //
+// Ordered form (mom_deform_backward_ordered_n, include/mom4d.h "ordered MLP weight gradients"): the same two kernels instantiated with
+// ORDERED = true store per-workgroup records where the default instantiations issue float atomics, and one more kernel adds the
+// records in workgroup order; the default instantiations compile to the code they had.
+//
 // There is no bf16 one-kernel backward for 32 features (deform_bwd_b3.hip is 64 features only): such a call runs the two f32
 // kernels whatever MOM_MLP_BWD names -- unset, empty, "b3" or "split" -- and any other value is MOM_EINVAL as for 64 features.
 #include "deform_mlp_dev.h"
@@ -43,6 +47,9 @@ int mom_launch_deform_bwd_b3f(const MomDeformMLP* w, int P, const float* feat, c
 size_t mom_deform_bwd_b3f_scratch_bytes(void);
 
 namespace {
+
+constexpr int kOrdLayer = kHid * kHid + kHid;   // floats of one dW workgroup's record in the ordered form: [64][64] weights | 64 biases
+constexpr int kOrdThin = 12 * kHid + 16;   // floats of one dx workgroup's record in the ordered form: [3 heads][4][64] weights | [3][4] biases | pad
 
 // All threads of a workgroup share ONE copy of the weights in LDS (70 KB).  With 256 threads two workgroups = 8 waves fit per
 // CU although the registers allow 16: a workgroup of up to 1024 threads gets up to 16 waves for the same LDS.
@@ -120,7 +127,9 @@ deform_fwd_kernel(MlpDev m, int P, int tiles, const float* __restrict__ feat, co
 // (A) activations backward: dH for the four layers, d(features) [P][32 KT], output-layer weight gradients
 // 512 threads: two waves per SIMD share one copy of the weights (142 KB of LDS with the staging tiles), so that one wave's vector
 // and memory phases -- the thin output layers, the dH stores -- run under the other's MFMAs (4 waves: 288 us for dx + dW, 8: 276)
-template <int KT>
+// ORDERED (mom_deform_backward_ordered_n): the waves meet in LDS by taking turns in wave order and the workgroup's result is STORED
+// at m.dW2[0] + blockIdx.x * kOrdThin (the host points dW2[0] at the partials); deform_bwd_ordered_reduce_kernel adds the workgroups up.
+template <int KT, bool ORDERED = false>
 __global__ void __launch_bounds__(64 * kDxWaves)
 deform_bwd_dx_kernel(MlpDev m, int P, int tiles, const float* __restrict__ a0g, const float* __restrict__ dpts,
                      const float* __restrict__ dscales, const float* __restrict__ drots, float* __restrict__ dfeat,
@@ -220,6 +229,29 @@ deform_bwd_dx_kernel(MlpDev m, int P, int tiles, const float* __restrict__ a0g, 
     // output-layer gradients: combine the four waves in LDS, one atomic per element per workgroup
     __syncthreads();
     float* R = lds;
+    if constexpr (ORDERED) {
+#pragma unroll 1
+        for (int turn = 0; turn < kDxWaves; turn++) {
+            if (wv == turn) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+#pragma unroll
+                    for (int n = 0; n < 4; n++) {
+                        float* a = &R[(k * 4 + n) * kHid + lane];
+                        *a = (turn == 0 ? 0.f : *a) + dW2[k][n];
+                    }
+                    if (lane < 4) {
+                        float* a = &R[12 * kHid + k * 4 + lane];
+                        *a = (turn == 0 ? 0.f : *a) + db2[k];
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        float* __restrict__ out = m.dW2[0] + (size_t)blockIdx.x * kOrdThin;
+        for (int i = threadIdx.x; i < kOrdThin; i += blockDim.x) out[i] = i < 12 * kHid + 12 ? R[i] : 0.f;
+        return;
+    }
     for (int i = threadIdx.x; i < 12 * kHid + 16; i += blockDim.x) R[i] = 0.f;
     __syncthreads();
 #pragma unroll
@@ -248,7 +280,7 @@ deform_bwd_dx_kernel(MlpDev m, int P, int tiles, const float* __restrict__ a0g, 
 // KT = tiles of 32 input features: 2 for the heads (X = a0 [P,64], as deform_bwd_dw_kernel), 1 for the trunk (X = feat [P,32]).
 // The B operand's lane half is the K slot, a Gaussian of the pair g0 + 2u + {0,1}: with KT = 1 the two halves read two consecutive
 // 128-byte rows, one 256-byte load of the whole wave.
-template <int KT>
+template <int KT, bool ORDERED = false>
 __device__ __forceinline__ void dw_layer(const float* __restrict__ xa, const float* __restrict__ dHl, int g_begin, int g_end,
                                          float* __restrict__ dst, float* __restrict__ dbs, float* __restrict__ R)
 {
@@ -329,6 +361,12 @@ __device__ __forceinline__ void dw_layer(const float* __restrict__ xa, const flo
         }
     }
     __syncthreads();
+    if constexpr (ORDERED) {
+        // dst / dbs: this workgroup's record of the partials
+        for (int i = threadIdx.x; i < kHid * kIn; i += 256) dst[i] = R[i];
+        if (threadIdx.x < kHid) dbs[threadIdx.x] = R[kHid * kIn + threadIdx.x];
+        return;
+    }
     for (int i = threadIdx.x; i < kHid * kIn; i += 256) {
         const float v = R[i];
         if (v != 0.f) atomicAdd(&dst[i], v);
@@ -351,7 +389,9 @@ __device__ __forceinline__ void dw_layer(const float* __restrict__ xa, const flo
 // 1..3 at two.  The two forms stay side by side because the body does not survive being called: as a __forceinline__ function or
 // a generic lambda, at KT = 2, it compiles to 895 instructions where it has 991 here -- the same loop, another reduction (LDS stores
 // merged in pairs, half the exec-mask regions) -- the way its NL comment warns, and the timings of this file are of these 991.
-template <int KT>
+// ORDERED: a workgroup STORES its tile as record (layer, range) of the partials at m.dW0 (the host points it there), kOrdLayer floats
+// each: [64][32 KT'] weights from the record's start, the 64 biases at kHid * kHid; deform_bwd_ordered_reduce_kernel adds the ranges up.
+template <int KT, bool ORDERED = false>
 __global__ void __launch_bounds__(256)
 deform_bwd_dw_kernel(MlpDev m, int P, int chunk, const float* __restrict__ feat, const float* __restrict__ a0g,
                      const float* __restrict__ dH, int ny)
@@ -467,6 +507,11 @@ deform_bwd_dw_kernel(MlpDev m, int P, int chunk, const float* __restrict__ feat,
                 }
             }
             __syncthreads();
+            if constexpr (ORDERED) {
+                float* __restrict__ rec = m.dW0 + ((size_t)L * (gridDim.x / ny) + bx) * kOrdLayer;
+                for (int i = threadIdx.x; i < kOrdLayer; i += 256) rec[i] = R[i];
+                continue;
+            }
             float* dst = L == 0 ? m.dW0 : m.dW1[L - 1];
             float* dbs = L == 0 ? m.db0 : m.db1[L - 1];
             for (int i = threadIdx.x; i < kHid * kHid; i += 256) {
@@ -484,10 +529,18 @@ deform_bwd_dw_kernel(MlpDev m, int P, int chunk, const float* __restrict__ feat,
         const int wave = (bx * 256 + threadIdx.x) >> 6;
         const int g_begin = wave * chunk, g_end = min(P, g_begin + chunk);   // chunk is even
         const float* __restrict__ dHl = dH + (size_t)L * P * kHid;
-        if (L == 0)
-            dw_layer<1>(feat, dHl, g_begin, g_end, m.dW0, m.db0, lds);
-        else
-            dw_layer<2>(a0g, dHl, g_begin, g_end, m.dW1[L - 1], m.db1[L - 1], lds);
+        if constexpr (ORDERED) {
+            float* __restrict__ rec = m.dW0 + ((size_t)L * (gridDim.x / ny) + bx) * kOrdLayer;
+            if (L == 0)
+                dw_layer<1, true>(feat, dHl, g_begin, g_end, rec, rec + kHid * kHid, lds);
+            else
+                dw_layer<2, true>(a0g, dHl, g_begin, g_end, rec, rec + kHid * kHid, lds);
+        } else {
+            if (L == 0)
+                dw_layer<1>(feat, dHl, g_begin, g_end, m.dW0, m.db0, lds);
+            else
+                dw_layer<2>(a0g, dHl, g_begin, g_end, m.dW1[L - 1], m.db1[L - 1], lds);
+        }
     }
 }
 
@@ -497,6 +550,7 @@ deform_bwd_dw_kernel(MlpDev m, int P, int chunk, const float* __restrict__ feat,
 // workgroup: 5 times at 33 Gaussians, ~200 at 8 k -- and once more per camera of a batch.)
 //   [4 layers (W0, W1_0..2)][64*64 weights + 64 biases]  then  [3 heads][4*64 weights + 4 biases]
 constexpr int kStgLayer = kHid * kHid + kHid;
+static_assert(kStgLayer == kOrdLayer, "the ordered form's records have the staging area's layer layout");
 constexpr int kStgThin = 4 * kHid + 4;
 constexpr int kStgUsed = 4 * kStgLayer + 3 * kStgThin;
 constexpr int kStgFloats = (kStgUsed + 63) / 64 * 64;            // dH behind it stays 256-byte aligned
@@ -523,6 +577,52 @@ __global__ void __launch_bounds__(256) deform_bwd_add_kernel(MlpDev m, const flo
         } else if (j - 4 * kHid < nout) dst = m.db2[k] + (j - 4 * kHid);
     }
     if (dst) *dst += v;
+}
+
+// The ordered form's reduction (include/mom4d.h, "ordered MLP weight gradients"): element i of the map above (first .. first + count - 1)
+// takes the `nparts` workgroups' partials in ascending workgroup index, left to right from +0.0, then dst[i] += total -- ONE thread
+// per element, so nothing but `nparts` decides the order.  Records are `stride` floats apart: element (layer L, j) lies at j of record
+// (L, workgroup) [kOrdLayer floats], weight j of head k at 256 k + j and its bias n at 768 + 4 k + n of the workgroup's thin record [kOrdThin].
+__global__ void __launch_bounds__(256)
+deform_bwd_ordered_reduce_kernel(MlpDev m, const float* __restrict__ parts, int nparts, int n_in, int first, int count)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= count) return;
+    const int i = first + t;
+    if (i >= kStgUsed) return;
+    float* dst = nullptr;
+    const float* src;
+    size_t stride;
+    if (i < 4 * kStgLayer) {
+        const int L = i / kStgLayer, j = i - L * kStgLayer;
+        if (j >= kHid * kHid) dst = (L == 0 ? m.db0 : m.db1[L - 1]) + (j - kHid * kHid);
+        else if (L > 0) dst = m.dW1[L - 1] + j;
+        else if (j < kHid * n_in) dst = m.dW0 + j;
+        src = parts + (size_t)L * nparts * kStgLayer + j;
+        stride = kStgLayer;
+    } else {
+        const int k = (i - 4 * kStgLayer) / kStgThin, j = (i - 4 * kStgLayer) - k * kStgThin;
+        const int nout = k == 2 ? 4 : 3;
+        if (j < 4 * kHid) {
+            if ((j >> 6) < nout) dst = m.dW2[k] + j;
+            src = parts + k * 4 * kHid + j;
+        } else {
+            if (j - 4 * kHid < nout) dst = m.db2[k] + (j - 4 * kHid);
+            src = parts + 12 * kHid + k * 4 + (j - 4 * kHid);
+        }
+        stride = kOrdThin;
+    }
+    if (!dst) return;
+    float total = 0.f;
+    for (int w0 = 0; w0 < nparts; w0 += 8) {               // eight loads in flight; the additions stay in record order
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = src[(size_t)min(w0 + u, nparts - 1) * stride];
+#pragma unroll
+        for (int u = 0; u < 8; u++)
+            if (w0 + u < nparts) total = total + v[u];
+    }
+    *dst = *dst + total;
 }
 
 template <int KT>
@@ -631,7 +731,80 @@ int backward(const MomDeformMLP* w, int P, const float* feat, const float* a0, c
     return hipGetLastError() == hipSuccess ? MOM_OK : MOM_ELAUNCH;
 }
 
+// scratch of the ordered form: dH [4][P][64] | the dx workgroups' records [256][kOrdThin] | the dW workgroups' records [4][256][kStgLayer]
+constexpr int kOrdDxParts = 256, kOrdDwParts = 256;
+size_t ordered_scratch_floats(int P, size_t* o_dx, size_t* o_dw)
+{
+    size_t off = ((size_t)4 * (size_t)(P > 0 ? P : 1) * kHid + 63) / 64 * 64;
+    if (o_dx) *o_dx = off;
+    off += (size_t)kOrdDxParts * kOrdThin;
+    if (o_dw) *o_dw = off;
+    off += (size_t)4 * kOrdDwParts * kStgLayer;
+    return off;
+}
+
+// mom_deform_backward_ordered_n: the two f32 kernels in their ORDERED instantiations on one stream, then the reduction.  The grids are
+// those of backward<KT>: min(tiles, 256) persistent workgroups, each a contiguous share of the tiles dealt to its waves by index, and
+// 1024 wave ranges of a chunk that P alone fixes -- both mappings are arithmetic on blockIdx / threadIdx (deform_bwd_dx_kernel's t_begin /
+// t_first, deform_bwd_dw_kernel's bx / wave), nothing is claimed at run time.
+template <int KT>
+int backward_ordered(const MomDeformMLP* w, int P, const float* feat, const float* a0, const float* dpts, const float* dscales,
+                     const float* drots, float* dfeat, void* scratch, size_t scratch_bytes, mom_stream_t stream)
+{
+    if (P < 0) return MOM_EINVAL;
+    if (P == 0) return MOM_OK;
+    if (!feat || !a0 || !dpts || !dscales || !drots || !dfeat || !scratch) return MOM_EINVAL;
+    size_t o_dx, o_dw;
+    if (scratch_bytes < ordered_scratch_floats(P, &o_dx, &o_dw) * sizeof(float)) return MOM_EINVAL;
+    MlpDev d;
+    int rc = fill_dev(w, &d);
+    if (rc) return rc;
+    if (!d.dW0 || !d.db0) return MOM_EINVAL;
+    for (int i = 0; i < 3; i++)
+        if (!d.dW1[i] || !d.db1[i] || !d.dW2[i] || !d.db2[i]) return MOM_EINVAL;
+    float* dH = (float*)scratch;
+    float* parts_dx = dH + o_dx;
+    float* parts_dw = dH + o_dw;
+    MlpDev g = d;                                       // the ORDERED kernels read two of the gradient pointers only: their partials
+    g.dW2[0] = parts_dx;
+    g.dW0 = parts_dw;
+    const int tiles = (P + 31) / 32;
+    const int blocks = tiles < kOrdDxParts ? tiles : kOrdDxParts;
+    const size_t lds_a = sizeof(float) * kLBwdTotal;
+    const size_t lds_b = sizeof(float) * (kHid * kHid + kHid);
+    if (!mom_lds_limit<deform_bwd_dx_kernel<KT, true>>(lds_a)) return MOM_ELAUNCH;
+    hipStream_t s = (hipStream_t)stream;
+    MomProfScope ps(MOM_P_MLP_BWD, s);
+    hipLaunchKernelGGL((deform_bwd_dx_kernel<KT, true>), dim3(blocks), dim3(64 * kDxWaves), lds_a, s, g, P, tiles, a0, dpts, dscales, drots,
+                       dfeat, dH);
+    if (hipGetLastError() != hipSuccess) return MOM_ELAUNCH;
+    const int waves = 4 * kOrdDwParts, layers = 4;
+    int chunk = (P + waves - 1) / waves;
+    chunk += chunk & 1;
+    hipLaunchKernelGGL((deform_bwd_dw_kernel<KT, true>), dim3(kOrdDwParts * layers), dim3(256), lds_b, s, g, P, chunk, feat, a0, dH, layers);
+    if (hipGetLastError() != hipSuccess) return MOM_ELAUNCH;
+    hipLaunchKernelGGL(deform_bwd_ordered_reduce_kernel, dim3((3 * kStgThin + 255) / 256), dim3(256), 0, s, d, parts_dx, blocks, 32 * KT,
+                       4 * kStgLayer, 3 * kStgThin);
+    hipLaunchKernelGGL(deform_bwd_ordered_reduce_kernel, dim3((4 * kStgLayer + 255) / 256), dim3(256), 0, s, d, parts_dw, kOrdDwParts, 32 * KT, 0,
+                       4 * kStgLayer);
+    return hipGetLastError() == hipSuccess ? MOM_OK : MOM_ELAUNCH;
+}
+
 }  // namespace
+
+extern "C" size_t mom_deform_backward_ordered_scratch_bytes(int P)
+{
+    return P < 0 ? 0 : ordered_scratch_floats(P, nullptr, nullptr) * sizeof(float);
+}
+
+extern "C" int mom_deform_backward_ordered_n(const MomDeformMLP* w, int P, int in_features, const float* feat, const float* a0,
+                                             const float* dpts, const float* dscales, const float* drots, float* dfeat, void* scratch,
+                                             size_t scratch_bytes, mom_stream_t stream)
+{
+    if (in_features != 64 && in_features != 32) return MOM_EINVAL;
+    return (in_features == 64 ? backward_ordered<2> : backward_ordered<1>)(w, P, feat, a0, dpts, dscales, drots, dfeat, scratch,
+                                                                           scratch_bytes, stream);
+}
 
 // The entry points with in_features (include/mom4d.h) are the ones that launch: 64 and 32 are the trunks there are.
 extern "C" int mom_deform_forward_activated_n(const MomDeformMLP* w, int P, int in_features, const float* feat, const float* xyz,

@@ -38,6 +38,7 @@ _state = {
     "post_ring": None,         # PostRing of the async forwards' status words: raster_forward (made on first use, likewise)
     "deterministic": False,    # set_deterministic()
     "ordered": None,           # the ordered backward's cached scratch, made by its first call: ordered_backward
+    "field_ordered": None,     # the ordered field backwards' cached scratch (HexPlane, MLP), made by their first call: field_ordered_scratch
 }
 _FLAG_LAG = 4
 
@@ -183,7 +184,10 @@ def set_deterministic(on: bool) -> None:
     reduction") instead of with float atomics -- rasterize_gaussians_backward and the one-node autograd paths (fused_autograd) then
     return the same bits for the same inputs, run after run.  Such a backward plans its slots, SYNCHRONISES ONCE with the stream to
     read their number, keeps a grow-only scratch of 160 bytes per slot (slots = the reference's num_rendered) and runs
-    mom_raster_backward_ordered.  The fused training steps have no ordered form and raise MomError while the switch is on.
+    mom_raster_backward_ordered.  The field's backward follows the switch too: ops.HexPlaneFunction, ops.DeformMLPFunction and the
+    one-node paths run mom_hexplane_backward_ordered (one shared timestamp; per-point timestamps raise MomError) and, for the f32
+    MLP backward, mom_deform_backward_ordered_n, out of a second grow-only scratch (field_ordered_scratch).  The fused training
+    steps have no ordered form and raise MomError while the switch is on.
     False (default): the atomic form; nothing of the above is allocated or called."""
     _state["deterministic"] = bool(on)
 
@@ -195,6 +199,19 @@ def deterministic() -> bool:
 def refuse_if_deterministic(what):
     if _state["deterministic"]:
         raise N.MomError(f"{what} has no ordered backward: it cannot run under diff_gaussian_rasterization._C.set_deterministic(True)")
+
+
+def field_ordered_scratch(which, need, dev):
+    """The ordered field backwards' scratch (`which`: "hex" or "mlp"), grow-only, one per process like _state["ordered"]: every use is
+    enqueued on the caller's current stream, so a call may overwrite what the call before it left."""
+    o = _state["field_ordered"]
+    if o is None or o["dev"] != dev:
+        o = _state["field_ordered"] = dict(dev=dev, hex=None, mlp=None)
+    t = o[which]
+    if t is None or t.numel() < need:
+        o[which] = None                                         # (freed before its successor is made)
+        t = o[which] = torch.empty(need + need // 4, dtype=torch.uint8, device=dev)
+    return t
 
 
 def ordered_status():

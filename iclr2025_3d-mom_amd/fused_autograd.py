@@ -272,7 +272,8 @@ def _backward(st, dcolor, ddepth, direct=True):
         return g2d, (gxyz, gdc, grest, gsc, grot, gop)
     if "dfeat" not in b:              # the deformation backward's intermediate gradient and scratch
         b.update(dfeat=e(P, st.F), scratch=torch.empty(lib.mom_deform_backward_scratch_bytes(P), dtype=torch.uint8, device=dev))
-    overlap = ops.API_OVERLAP and direct
+    det = RC.deterministic()
+    overlap = ops.API_OVERLAP and direct and not det          # (the ordered field backward is one stream)
     ready = side = None
     if overlap:
         # the appearance parameters' gradients (SH, scaling, rotation, opacity) are final here: FusedAdam.step() may start their
@@ -282,7 +283,9 @@ def _backward(st, dcolor, ddepth, direct=True):
     gplanes, gmlp, hp, md, in_place = _field_grads(st, f, direct)
     dfeat, scratch = b["dfeat"], b["scratch"]
     # pts = xyz + dx(...): d xyz starts as d pts (already in gxyz); scale / rotation residuals likewise
-    if overlap:
+    if det:
+        ops.deform_backward_ordered(lib, md, P, st.F, st.feat, st.a0, gxyz, gsc, grot, dfeat, s)
+    elif overlap:
         # with a second stream the MLP backward leaves an eighth of the chip free (for that Adam launch) and its partial-sum
         # reduction goes there too (csrc/deform_bwd_b3.hip; on 32 features: the weight-gradient kernel of csrc/deform_mlp.hip);
         # joined below
@@ -293,18 +296,21 @@ def _backward(st, dcolor, ddepth, direct=True):
         N.check(lib.mom_deform_backward_n(C.byref(md), P, st.F, st.feat.data_ptr(), st.a0.data_ptr(), gxyz.data_ptr(), gsc.data_ptr(),
                                           grot.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), s), "deform_bwd")
     ops.wait_reg_pending(dev)          # the regulariser's gradient kernel (second stream) adds into the plane gradients too
-    porders = st.porders
+    porders = None if det else st.porders
     hscratch = None
     if porders is not None:
         need = lib.mom_hexplane_backward_scratch_bytes(C.byref(hp), P)
         hscratch = b.get("hscratch")
         if hscratch is None or hscratch.numel() < need:
             hscratch = b["hscratch"] = torch.empty(need, dtype=torch.uint8, device=dev)
-    N.check(lib.mom_hexplane_backward(C.byref(hp), P, st.xyz.data_ptr(), None, st.cam_time,
-                                      None if st.order is None else st.order.data_ptr(), dfeat.data_ptr(), gxyz.data_ptr(),
-                                      None if porders is None else porders[0].data_ptr(),
-                                      None if porders is None else porders[1].data_ptr(),
-                                      None if hscratch is None else hscratch.data_ptr(), s), "hexplane_bwd")
+    if det:
+        ops.hexplane_backward_ordered(lib, hp, P, st.xyz, st.cam_time, st.order, dfeat, gxyz, s)
+    else:
+        N.check(lib.mom_hexplane_backward(C.byref(hp), P, st.xyz.data_ptr(), None, st.cam_time,
+                                          None if st.order is None else st.order.data_ptr(), dfeat.data_ptr(), gxyz.data_ptr(),
+                                          None if porders is None else porders[0].data_ptr(),
+                                          None if porders is None else porders[1].data_ptr(),
+                                          None if hscratch is None else hscratch.data_ptr(), s), "hexplane_bwd")
     if overlap:
         ops.stream_wait_stream(s, side)                    # the MLP weight gradients are complete for whoever reads them next
     st.ready, st.side = ready, side

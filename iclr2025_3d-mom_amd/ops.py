@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .diff_gaussian_rasterization import _C as _RC          # the process-wide switches (set_deterministic) and their scratch
 
 
 def _need_cuda(t, what):
@@ -68,6 +69,38 @@ def _hexplane_desc(planes_by_level, aabb, grads_by_level=None, aabb_host=None):
     return d, keep
 
 
+def hexplane_backward_ordered(lib, hp, P, xyz, time, order, dfeat, dxyz, s):
+    """mom_hexplane_backward under set_deterministic(True): the pull form out of the cached scratch (one shared timestamp)."""
+    need = lib.mom_hexplane_ordered_scratch_bytes(C.byref(hp), P)
+    if need == 0:
+        raise N.MomError("the ordered HexPlane backward (set_deterministic) does not take this field: "
+                         f"{hp.levels} levels of {hp.channels} channels, P = {P} (include/mom4d.h, LIMITS)")
+    scratch = _RC.field_ordered_scratch("hex", need, xyz.device)
+    N.check(lib.mom_hexplane_backward_ordered(C.byref(hp), P, xyz.data_ptr(), float(time), None if order is None else order.data_ptr(),
+                                              dfeat.data_ptr(), None if dxyz is None else dxyz.data_ptr(), scratch.data_ptr(),
+                                              scratch.numel(), s), "mom_hexplane_backward_ordered")
+
+
+def mlp_backward_is_ordered(n_in):
+    """Which MLP backward set_deterministic(True) selects: the ordered f32 form for a 32-feature trunk and, at 64 features, under
+    MOM_MLP_BWD=split; the default 64-feature form (csrc/deform_bwd_b3.hip) already adds its partials in a fixed order and stays
+    (tests/test_field_ordered_gpu.py pins that it repeats)."""
+    return n_in == 32 or _os.environ.get("MOM_MLP_BWD") == "split"
+
+
+def deform_backward_ordered(lib, md, P, n_in, feat, a0, dpts, dsc, dro, dfeat, s):
+    """mom_deform_backward_n under set_deterministic(True): one stream; ordered weight gradients where the form has atomics."""
+    if not mlp_backward_is_ordered(n_in):
+        scratch = _RC.field_ordered_scratch("mlp", lib.mom_deform_backward_scratch_bytes(P), feat.device)
+        N.check(lib.mom_deform_backward_n(C.byref(md), P, n_in, feat.data_ptr(), a0.data_ptr(), dpts.data_ptr(), dsc.data_ptr(),
+                                          dro.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), s), "mom_deform_backward_n")
+        return
+    scratch = _RC.field_ordered_scratch("mlp", lib.mom_deform_backward_ordered_scratch_bytes(P), feat.device)
+    N.check(lib.mom_deform_backward_ordered_n(C.byref(md), P, n_in, feat.data_ptr(), a0.data_ptr(), dpts.data_ptr(), dsc.data_ptr(),
+                                              dro.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), scratch.numel(), s),
+            "mom_deform_backward_ordered_n")
+
+
 class HexPlaneFunction(torch.autograd.Function):
     """features[P, L*C] = HexPlaneField(xyz, t) (reference scene/hexplane.py:160-183), level-major; C = the planes' channel
     count, 32 or 16 (csrc/hexplane.hip, one template instantiated for both; any other count is a MomError from the library)."""
@@ -94,6 +127,10 @@ class HexPlaneFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dfeat):
+        ordered = _RC.deterministic()
+        if ordered and ctx.times is not None:
+            raise N.MomError("hexplane backward with per-point timestamps has no ordered form: it cannot run under "
+                             "diff_gaussian_rasterization._C.set_deterministic(True)")
         xyz_c, aabb, *planes = ctx.saved_tensors
         n_levels = ctx.n_levels
         wait_reg_pending_all()         # (AccumulateGrad adds what this returns to plane gradients the second stream may be writing)
@@ -104,6 +141,9 @@ class HexPlaneFunction(torch.autograd.Function):
         dxyz = torch.zeros_like(xyz_c) if ctx.needs_input_grad[0] else None
         dfeat = dfeat.contiguous()
         lib = N.lib()
+        if ordered:
+            hexplane_backward_ordered(lib, d, P, xyz_c, ctx.time, ctx.order, dfeat, dxyz, N.current_stream())
+            return (dxyz, None, None, None, None, None, None, *[g for level in grads for g in level])
         po, scratch = ctx.plane_orders, None
         if po is not None and ctx.times is None:        # two-pass backward: per-plane orders + the gradient-row scratch
             scratch = torch.empty(lib.mom_hexplane_backward_scratch_bytes(C.byref(d), P), dtype=torch.uint8, device=xyz_c.device)
@@ -331,6 +371,9 @@ class DeformMLPFunction(torch.autograd.Function):
         d = DeformMLPFunction._desc(ps, grads)
         dpts, dsc, dro = dpts.contiguous(), dsc.contiguous(), dro.contiguous()
         dfeat = torch.empty_like(feat_c)                # [P,32] or [P,64]: the trunk's width
+        if _RC.deterministic():
+            deform_backward_ordered(lib, d, P, feat_c.shape[1], feat_c, a0, dpts, dsc, dro, dfeat, N.current_stream())
+            return (dfeat, dpts, dsc, dro, None, None, *grads)
         scratch = torch.empty(lib.mom_deform_backward_scratch_bytes(P), dtype=torch.uint8, device=feat_c.device)
         N.check(lib.mom_deform_backward_n(C.byref(d), P, feat_c.shape[1], feat_c.data_ptr(), a0.data_ptr(), dpts.data_ptr(),
                                           dsc.data_ptr(), dro.data_ptr(), dfeat.data_ptr(), scratch.data_ptr(), N.current_stream()),

@@ -34,8 +34,9 @@ class Trainer:
         # The fine step is fused_step.fine_step()'s choice by step_features(): FusedStep for the shipped 32 x 2 field, FusedStep16 for two
         # levels of 16-channel planes (dnerf/eulerian_150_16) on one GPU -- parallel.attach() drops the fused step of such a trainer too.
         # deterministic=True: the rasterizer's backward adds in a defined order (RC.set_deterministic: the switch is process-wide and
-        # stays on); the coarse stage -- activations, rasterizer, L1, Adam -- then repeats bit for bit from the same state.  The fine
-        # stage's field backward still uses float atomics ("Ordered backward reduction"), and the fused steps have no ordered form.
+        # stays on) and so does the field's (HexPlane pull form, ordered MLP weight gradients: DESIGN.md 3.23); the coarse and the fine
+        # stage -- activations, field, rasterizer, L1, regularisers, Adam -- then repeat bit for bit from the same state.  The fused steps
+        # have no ordered form.
         if deterministic:
             if fused:
                 raise RC.N.MomError("Trainer(fused=True, deterministic=True): the fused steps have no ordered backward "

@@ -400,6 +400,49 @@ int mom_hexplane_orders(const MomHexPlane* hp, int P, const float* xyz, uint32_t
 size_t mom_morton_order_scratch_bytes(int P);
 int mom_morton_order(int P, const float* points /* [P,3] */, uint32_t* order /* [P] */, void* scratch, mom_stream_t stream);
 
+/* ---- ordered HexPlane backward: plane and position gradients that are a function of their inputs, bit for bit ------------------
+ * mom_hexplane_backward adds into the plane gradients with float atomics, in whatever order the waves arrive, and the levels add
+ * into one dxyz slot the same way.  The ordered form is a PULL: a texel's gradient is computed by the texel's owner from the points
+ * of the four cells around it, with no float atomic anywhere (csrc/hexplane_ordered.hip).  One shared timestamp only (per-point
+ * timestamps have no ordered form: the entry takes none); 32 or 16 channels, 1..4 levels.  The call is self-contained and
+ * stream-ordered: it sorts the points of every (level, plane) by the cell of their CURRENT position itself and takes no plane
+ * orders.  `order` (may be null) is the gather's processing order as in mom_hexplane_backward; no result depends on it.
+ *
+ * TERMS.  Per (point g, level l): the six samples and gv(g,l,p,c) = dfeat * (product of the other five), formed as
+ * (dfeat * pre[p]) * suf[p+1] like the generic backward, in uncontracted fp32; the level's share of the position gradient is
+ * reduced over the channels by the gathers' xor butterflies.  A point lies in cell (y0, x0) of plane p (W along its first axis):
+ * x0 = floor of the clipped unnormalised coordinate exactly as the plane-order keys form it; for a space-time plane y0 is the cell
+ * of the shared timestamp.  Its corner weights w00 (nw), w01 (ne), w10 (sw), w11 (se) are ATen's, (x1 - ix) (y1 - iy) etc.
+ * ORDER.  Texel (y, x) of plane p, level l, channel c receives four classes:
+ *   k = 0  nw: the points of cell (y, x),     weight w00        k = 1  ne: cell (y, x-1),   weight w01
+ *   k = 2  sw: cell (y-1, x),                 weight w10        k = 3  se: cell (y-1, x-1), weight w11
+ * (a cell outside the plane has no points; a corner outside the plane is no texel and receives nothing).  Within a class the cell's
+ * n points are taken in ascending g; the term is e = gv * w, one fp32 multiply.  The terms are cut into blocks of 64 from the first:
+ *   b_j = (...((+0.0 + e_64j) + e_64j+1) + ...)  left to right;      s_k = (...((+0.0 + b_0) + b_1) + ...)  left to right;
+ *   T = (s_0 + s_1) + (s_2 + s_3)  (s_k = +0.0 for a class without terms);      grad = grad_in + T,
+ * one add onto whatever the buffer held (the regulariser's gradient arrives there first).  A texel without a term in any class is not
+ * written.  dxyz[g][k] = dxyz_in[g][k] + (((part_0 + part_1) + part_2) + part_3) over the levels there are, part_l the level's share.
+ * The order is a function of the positions, the timestamp and the descriptor alone -- not of the grid, an environment switch, the
+ * `order` argument or which wave arrives first.  mom_hexplane_ordered_sum_host reproduces it on the host (plain C++, no contraction).
+ *
+ * SCRATCH (mom_hexplane_ordered_scratch_bytes; 0 for a descriptor or P the call refuses).  From its 256-byte aligned start: the gv rows
+ * [levels][6][P][channels] floats in POINT order, then at the next multiple of 256 bytes the position shares dxyz_part[levels][P][3]
+ * (written when dxyz is given); behind them the sort buffers, per-point weights, per-cell segment and block tables and the block sums
+ * of the plane being reduced.  Every byte the call reads it has written first.
+ * LIMITS.  Cells and texels are indexed with int: W * H * (4 * channels) bytes must stay below 2^31 for each of the six planes of
+ * each level (which keeps the cell key y0 W + x0 inside 32 bits), every resolution within 1 .. 65536; everything indexed by the
+ * point is addressed with size_t, and P <= 2^30 keeps the point index (workgroup * 256 + thread) an int.  MOM_EINVAL before anything is
+ * launched: hp null, channels other than 16 / 32, levels outside 1..4, P < 0 or above 2^30, a resolution or plane outside those limits; then P == 0 returns MOM_OK; then xyz, dfeat, scratch, a plane or a gradient
+ * pointer null, scratch_bytes below mom_hexplane_ordered_scratch_bytes(hp, P).  dxyz may be null. */
+size_t mom_hexplane_ordered_scratch_bytes(const MomHexPlane* hp, int P);
+int mom_hexplane_backward_ordered(const MomHexPlane* hp, int P, const float* xyz, float time, const uint32_t* order,
+                                  const float* dfeat, float* dxyz, void* scratch, size_t scratch_bytes, mom_stream_t stream);
+/* The reduction on the host (no GPU needed).  hp: levels, channels, res, aabb as for the call and grads pointing at HOST buffers in
+ * the planes' layout, added onto (planes are not read); xyz [P,3], gv and dxyz_part as the call leaves them in its scratch; dxyz
+ * (may be null, with dxyz_part) is added onto. */
+int mom_hexplane_ordered_sum_host(const MomHexPlane* hp, int P, const float* xyz, float time, const float* gv,
+                                  const float* dxyz_part, float* dxyz);
+
 /* ---- activations of render() (gaussian_renderer/__init__.py:130-132) and their backward, one launch each ----
  * scales = exp(scales_raw), rots = rots_raw / max(|rots_raw|, 1e-12) (F.normalize), opac = sigmoid(opac_raw) */
 int mom_activations_forward(int P, const float* scales_raw, const float* rots_raw, const float* opac_raw, float* scales,
@@ -608,6 +651,22 @@ int mom_deform_backward_n(const MomDeformMLP* w, int P, int in_features, const f
 int mom_deform_backward_split_n(const MomDeformMLP* w, int P, int in_features, const float* feat, const float* a0, const float* dpts,
                                 const float* dscales, const float* drots, float* dfeat, void* scratch, mom_stream_t stream,
                                 mom_stream_t dw_stream);
+/* ---- ordered MLP weight gradients: mom_deform_backward_n whose weight and bias gradients are a function of their inputs ----------
+ * The two-kernel f32 form at either width (32 or 64 features, whatever MOM_MLP_BWD says), on ONE stream, with stores where that
+ * form has float atomics (dfeat never had any).  Workgroup b of the first kernel -- min(ceil(P / 32), 256) of them, each a fixed
+ * contiguous share of the 32-point tiles, dealt to its 8 waves by index -- adds its waves' output-layer sums in wave order,
+ * ((+0.0 + wave_0) + wave_1) + ..., and stores record b; workgroup (layer L, range r) of the second -- 256 ranges of four consecutive
+ * wave ranges of ceil(P / 1024) points rounded up to even -- adds its four waves' 64 x 64 tile the same way and stores record
+ * (L, r).  Then every element takes its records in ascending index, total = (...((+0.0 + rec_0) + rec_1) + ...), and dst += total.
+ * Both mappings are arithmetic on the workgroup and wave index: the order depends on P alone.
+ * SCRATCH (mom_deform_backward_ordered_scratch_bytes(P); 0 for P < 0), in floats: dH [4][P][64], rounded up to a multiple of 64; then
+ * the first kernel's records [256][784]: [3 heads][4][64] weights, [3][4] biases at 768, of which the first min(ceil(P / 32), 256)
+ * are written; then the second kernel's records [4 layers][256][4160]: [64][in] weights ([64][32] for layer 0 at 32 features),
+ * the 64 biases at 4096.  MOM_EINVAL as mom_deform_backward_n, and for scratch_bytes below that size. */
+size_t mom_deform_backward_ordered_scratch_bytes(int P);
+int mom_deform_backward_ordered_n(const MomDeformMLP* w, int P, int in_features, const float* feat, const float* a0, const float* dpts,
+                                  const float* dscales, const float* drots, float* dfeat, void* scratch, size_t scratch_bytes,
+                                  mom_stream_t stream);
 
 /* ---- deformation field in one pass (the render() case: ONE timestamp for every point) ----
  * deform_network.forward = HexPlaneField lookup + trunk + heads (scene/deformation.py:97-153, scene/hexplane.py:160-183) as a
