@@ -42,10 +42,10 @@ SMALL_C_FORM = "channels"
 class _FunctionSoftsplat(torch.autograd.Function):
     """The summation splat (softmax_splatting.py:236-269) on ops.softsplat_sum."""
     @staticmethod
-    def forward(ctx, input, flow):
+    def forward(ctx, input, flow, ordered=None):
         assert flow.shape[1] == 2 and input.shape[2:] == flow.shape[2:]
         assert input.is_contiguous() and flow.is_contiguous()
-        return ops.softsplat_sum(input.detach(), flow.detach())
+        return ops.softsplat_sum(input.detach(), flow.detach(), ordered=ordered)
 
     @staticmethod
     def backward(ctx, gradOutput):
@@ -53,7 +53,9 @@ class _FunctionSoftsplat(torch.autograd.Function):
                                   "warp under torch.no_grad() only")
 
 
-def FunctionSoftsplat(tensorInput, tensorFlow, tensorMetric, strType, output_size=None):
+def FunctionSoftsplat(tensorInput, tensorFlow, tensorMetric, strType, output_size=None, ordered=None):
+    """softmax_splatting.py:325-349.  ordered: ops.softsplat_sum's (None follows _C.set_deterministic); the reference's signature
+    stays callable as it is."""
     assert tensorMetric is None or tensorMetric.shape[1] == 1
     assert strType in ['summation', 'average', 'linear', 'softmax']
     if strType == 'average':
@@ -62,7 +64,7 @@ def FunctionSoftsplat(tensorInput, tensorFlow, tensorMetric, strType, output_siz
         tensorInput = torch.cat([tensorInput * tensorMetric, tensorMetric], 1)
     elif strType == 'softmax':
         tensorInput = torch.cat([tensorInput * tensorMetric.exp(), tensorMetric.exp()], 1)
-    tensorOutput = _FunctionSoftsplat.apply(tensorInput.contiguous(), tensorFlow.contiguous())
+    tensorOutput = _FunctionSoftsplat.apply(tensorInput.contiguous(), tensorFlow.contiguous(), ordered)
     if strType != 'summation':
         metric = tensorOutput[:, -1:, :, :]
         metric[metric == 0] = 1
@@ -77,8 +79,8 @@ class ModuleSoftsplat(torch.nn.Module):
         super().__init__()
         self.strType = strType
 
-    def forward(self, tensorInput, tensorFlow, tensorMetric, output_size=None):
-        return FunctionSoftsplat(tensorInput, tensorFlow, tensorMetric, self.strType, output_size)
+    def forward(self, tensorInput, tensorFlow, tensorMetric, output_size=None, ordered=None):
+        return FunctionSoftsplat(tensorInput, tensorFlow, tensorMetric, self.strType, output_size, ordered=ordered)
 
 
 # ----------------------------------------------------------------------------------------------- utils/joint_splatting.py
@@ -97,7 +99,7 @@ def backwarp(tenIn, tenFlow):
                          padding_mode='zeros', align_corners=False)
 
 
-def joint_splatting(feature_map1, weights1, flow1, feature_map2, weights2, flow2, mode="full", output_size=None):
+def joint_splatting(feature_map1, weights1, flow1, feature_map2, weights2, flow2, mode="full", output_size=None, ordered=None):
     assert feature_map1.shape == feature_map2.shape
     assert flow1.shape == flow2.shape
     assert feature_map1.shape[-2:] == flow1.shape[-2:]
@@ -108,7 +110,7 @@ def joint_splatting(feature_map1, weights1, flow1, feature_map2, weights2, flow2
     blending_weights = torch.cat([weights1, weights2], dim=-1)
     if mode == "full":
         return FunctionSoftsplat(tensorInput=feature_map, tensorFlow=flow, tensorMetric=blending_weights, strType='linear',
-                                 output_size=output_size)
+                                 output_size=output_size, ordered=ordered)
     if mode == "no_forward_warping":
         result = backwarp(feature_map, flow)
         if output_size is not None:
@@ -184,7 +186,7 @@ def resize_flow(flow, size):
     return flow
 
 
-def _blend_ops(feature, flow, idx, n_frames):
+def _blend_ops(feature, flow, idx, n_frames, ordered=None):
     """blend_feature as the reference's own op sequence (cinemagraph_utils.py:131-178) on the device's euler_integration and splat."""
     size = feature.size(2)
     alpha = idx / (n_frames - 1)
@@ -202,7 +204,7 @@ def _blend_ops(feature, flow, idx, n_frames):
     past_Z = pad_tensor(Z, mode="reflect") * alpha
     feature = pad_tensor(feature.to(dev), mode="reflect").float()
     return joint_splatting(feature, future_Z, future_flow, feature, past_Z, past_flow, mode="full",
-                           output_size=feature.shape[-2:]).float()
+                           output_size=feature.shape[-2:], ordered=ordered).float()
 
 
 def _fused_args(feature, flow):
@@ -217,22 +219,22 @@ def _form(channels):
     return SMALL_C_FORM if channels <= 3 else "channels"
 
 
-def blend_feature(feature, flow, idx, n_frames, fused=None):
+def blend_feature(feature, flow, idx, n_frames, fused=None, ordered=None):
     """cinemagraph_utils.py:131-178: the feature [1,C,S,S] warped to frame idx of n_frames along flow [1,2,S,S] from both ends of the
     loop and blended, on the cut and reflection-padded domain: [1,C,P,P].  fused (default FUSED_DEFAULT): one blend launch and one
-    finish launch; otherwise the reference's sequence of ops."""
+    finish launch; otherwise the reference's sequence of ops.  ordered: as warp_one_level's."""
     if not (FUSED_DEFAULT if fused is None else fused):
-        return _blend_ops(feature, flow, idx, n_frames)
+        return _blend_ops(feature, flow, idx, n_frames, ordered=ordered)
     f, m = _fused_args(feature, flow)
-    acc = ops.eulerian_blend(f, m, idx, n_frames, form=_form(f.shape[0]))
+    acc = ops.eulerian_blend(f, m, idx, n_frames, form=_form(f.shape[0]), ordered=ordered)
     return ops.eulerian_finish(acc, f.shape[1], full=True).unsqueeze(0)
 
 
-def feature_inpaint_conv(feature, flow, idx, n_frames, fused=None):
+def feature_inpaint_conv(feature, flow, idx, n_frames, fused=None, ordered=None):
     """cinemagraph_utils.py:498-531: the padded blended map with its blank pixels -- those no splat reached -- replaced by the 7 x 7
     box mean.  The reference's sequence: a second blend of a tensor of ones tells the blank pixels apart."""
     bn_feature = torch.ones(1, 1, flow.size(2), flow.size(3), device=feature.device)
-    warped_bn_feature = blend_feature(bn_feature, flow, idx, n_frames, fused=fused)
+    warped_bn_feature = blend_feature(bn_feature, flow, idx, n_frames, fused=fused, ordered=ordered)
     blank_mask = torch.where(warped_bn_feature == 0, 1, 0)
     full_mask = 1 - blank_mask
     if blank_mask.max() == 1:
@@ -244,18 +246,23 @@ def feature_inpaint_conv(feature, flow, idx, n_frames, fused=None):
     return feature
 
 
-def warp_one_level(out, flow, idx, n_frames, fused=None):
+def warp_one_level(out, flow, idx, n_frames, fused=None, ordered=None):
     """cinemagraph_utils.py:181-190: one level's features [1,C,S,S] at frame idx of n_frames.  fused (default FUSED_DEFAULT): after
     the flow resize, ops.eulerian_blend and ops.eulerian_finish -- the blank mask is the weight accumulator's zeros, the box mean is
-    computed at those pixels only, only the crop is written.  fused=False: the reference's sequence of ops on ops.softsplat_sum."""
+    computed at those pixels only, only the crop is written.  fused=False: the reference's sequence of ops on ops.softsplat_sum.
+    ordered (None: as diff_gaussian_rasterization._C.deterministic() says): the splat of either route adds in the order
+    include/mom4d.h defines ("ordered splat of the video generator's warp") instead of with float atomics, and the result is the same
+    bits run after run.  The two routes have different entry orders -- the op-by-op route splats the concatenated double canvas, whose
+    entries run row by row over both halves, the fused route takes all of the future half first -- so they need not agree with each
+    other in bits, only each with itself."""
     orig_size = out.size(2)
     flow = resize_flow(flow, orig_size)
     if not (FUSED_DEFAULT if fused is None else fused):
-        out = _blend_ops(out, flow, idx, n_frames)
-        out = feature_inpaint_conv(out, flow, idx, n_frames, fused=False)
+        out = _blend_ops(out, flow, idx, n_frames, ordered=ordered)
+        out = feature_inpaint_conv(out, flow, idx, n_frames, fused=False, ordered=ordered)
         return crop_padded_tensor(out, orig_size)
     f, m = _fused_args(out, flow)
-    acc = ops.eulerian_blend(f, m, idx, n_frames, form=_form(f.shape[0]))
+    acc = ops.eulerian_blend(f, m, idx, n_frames, form=_form(f.shape[0]), ordered=ordered)
     return ops.eulerian_finish(acc, orig_size).unsqueeze(0)
 
 
@@ -277,9 +284,10 @@ def _as_uint8_hwc(image, size, what):
     return np.array(image.resize((size, size)))
 
 
-def pixel_video_frames(image, our_flow, mask, n_frames=120, size=1024, device=None):
+def pixel_video_frames(image, our_flow, mask, n_frames=120, size=1024, device=None, ordered=None):
     """pixel_video's frames one at a time, where they are made: a generator of n_frames contiguous [size,size,3] float32 tensors in
-    [0, 1] on the device, so that a consumer on the device (save_video(writer="device")) never holds the video."""
+    [0, 1] on the device, so that a consumer on the device (save_video(writer="device")) never holds the video.  ordered:
+    warp_one_level's."""
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     rgb = _as_uint8_hwc(image, size, "image")
     if rgb.ndim != 3 or rgb.shape[2] < 3:
@@ -292,13 +300,13 @@ def pixel_video_frames(image, our_flow, mask, n_frames=120, size=1024, device=No
         up_mask = resize_feature((torch.from_numpy(np.array(m) / 255).unsqueeze(0).unsqueeze(0).to(dev)).float(), size)
     for idx in range(n_frames):
         with torch.no_grad():                       # per frame: a generator must not leave the caller's grad mode switched off
-            result = warp_one_level(x, flow, idx, n_frames)
+            result = warp_one_level(x, flow, idx, n_frames, ordered=ordered)
             result = result * up_mask + x * (1 - up_mask)
             frame = ((result + 1) / 2).permute(0, 2, 3, 1)[0].contiguous()                                      # ip_utils.to_numpy
         yield frame
 
 
-def pixel_video(image, our_flow, mask, n_frames=120, size=1024, device=None):
+def pixel_video(image, our_flow, mask, n_frames=120, size=1024, device=None, ordered=None):
     """A looping video from one image and its Eulerian flow WITHOUT the reference's StyleGAN: the frames of the reference's
     VideoGenerator (thirdparty/StyleCineGAN/main_jih.py) with the input image standing where the GAN's result would.  This is a
     substitute that warps pixels, not the reference's deep-feature output.
@@ -306,8 +314,10 @@ def pixel_video(image, our_flow, mask, n_frames=120, size=1024, device=None):
     image: PIL image or uint8 [H,W,3]; our_flow [1,2,h,w] (stage 1's, pixels per frame); mask: PIL image or uint8 [H,W], 255 where
     the scene moves.  As main_jih.py:33-39 all three are resized to size x size (the flow bilinearly, its values unscaled, as
     there).  Per frame idx: warp_one_level(image, flow, idx, n_frames), then result mask + image (1 - mask) (:160-161).
+    ordered: warp_one_level's (None follows _C.set_deterministic): the same frames, bit for bit, run after run.
     Returns n_frames arrays [size,size,3] float32 in [0, 1], as VideoGenerator does (to_numpy)."""
-    return [f.cpu().numpy() for f in pixel_video_frames(image, our_flow, mask, n_frames=n_frames, size=size, device=device)]
+    return [f.cpu().numpy() for f in pixel_video_frames(image, our_flow, mask, n_frames=n_frames, size=size, device=device,
+                                                        ordered=ordered)]
 
 
 VIDEO_WRITERS = ("host", "device")

@@ -17,50 +17,13 @@
 //
 // The accumulator is channel-last so that the lanes of a wave add to contiguous bytes of one target texel: a wave-instruction of the
 // blend covers runs of n consecutive floats, n = C+1 up to 64 channels and a balanced share of C+1 above (33 for C = 64: 132-byte runs).
-#include "mom_common.h"
+#include "eulerian_dev.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kChunk = 32;            // channels the finish pass transposes at a time
 constexpr int kBlendChunk = 64;       // the most accumulator channels the blend handles per pass (passes are balanced: 33 -> 33, 65 -> 33 + 32)
-constexpr float kMaxCoord = 1073741824.0f;   // 2^30: the splat converts only coordinates below this in magnitude
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// index of ReflectionPad2d: i in [-pad, n + pad) with pad < n -> [0, n)
-__device__ __forceinline__ int reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
-
-// One pixel's chain (cinemagraph_utils.py:42-57).  fetch(ix, iy, &mx, &my) reads the motion at an in-range integer position.
-// Returns the displacement after `steps` steps; `all` (or null) receives every step's, `stride` floats apart, x then y at +plane.
-template <typename Fetch>
-__device__ __forceinline__ float2 walk_chain(int px, int py, int W, int H, int steps, Fetch fetch, float* all, size_t stride,
-                                             size_t plane)
-{
-#pragma clang fp contract(off)
-    const float cx = (float)px, cy = (float)py, xmax = (float)(W - 1), ymax = (float)(H - 1);
-    float x = cx, y = cy;
-    bool invalid = false;
-    float2 d = {0.0f, 0.0f};
-    for (int s = 1; s <= steps; s++) {
-        if (!invalid) {
-            // x, y lie in [0, W-1] x [0, H-1] here; the clamp costs two instructions and makes that independent of the reasoning
-            const int ix = clampi((int)rintf(x), 0, W - 1), iy = clampi((int)rintf(y), 0, H - 1);
-            float mx, my;
-            fetch(ix, iy, mx, my);
-            x = x + mx;
-            y = y + my;
-            // the reference: x > W-1 || x < 0 (false for a NaN); here a NaN is out of bounds too
-            invalid = !(x <= xmax && x >= 0.0f && y <= ymax && y >= 0.0f);
-            d = invalid ? float2{0.0f, 0.0f} : float2{x - cx, y - cy};
-        }
-        if (all) {
-            all[(size_t)s * stride] = d.x;
-            all[(size_t)s * stride + plane] = d.y;
-        }
-    }
-    return d;
-}
 
 __global__ void __launch_bounds__(kThreads)
 euler_integrate_kernel(int H, int W, int steps, int all_frames, const float* __restrict__ motion, float* __restrict__ disp)
@@ -85,32 +48,6 @@ euler_integrate_kernel(int H, int W, int steps, int all_frames, const float* __r
     }
 }
 
-// The four targets of one source position (softmax_splatting.py:20-35): texel offsets (y * W + x, or -1 when dropped) and weights.
-struct Corners { int at[4]; float w[4]; };
-
-__device__ __forceinline__ Corners corners(float ox, float oy, int W, int H)
-{
-#pragma clang fp contract(off)
-    Corners c;
-    if (!(fabsf(ox) < kMaxCoord && fabsf(oy) < kMaxCoord)) {     // huge or NaN: dropped, never converted
-        for (int k = 0; k < 4; k++) { c.at[k] = -1; c.w[k] = 0.0f; }
-        return c;
-    }
-    const int nwx = (int)floorf(ox), nwy = (int)floorf(oy);
-    const int sex = nwx + 1, sey = nwy + 1;
-    c.w[0] = ((float)sex - ox) * ((float)sey - oy);             // northwest
-    c.w[1] = (ox - (float)nwx) * ((float)sey - oy);             // northeast
-    c.w[2] = ((float)sex - ox) * (oy - (float)nwy);             // southwest
-    c.w[3] = (ox - (float)nwx) * (oy - (float)nwy);             // southeast
-    const int tx = nwx, ty = nwy;
-    const bool x0 = tx >= 0 && tx < W, x1 = tx + 1 >= 0 && tx + 1 < W, y0 = ty >= 0 && ty < H, y1 = ty + 1 >= 0 && ty + 1 < H;
-    c.at[0] = x0 && y0 ? ty * W + tx : -1;
-    c.at[1] = x1 && y0 ? ty * W + tx + 1 : -1;
-    c.at[2] = x0 && y1 ? (ty + 1) * W + tx : -1;
-    c.at[3] = x1 && y1 ? (ty + 1) * W + tx + 1 : -1;
-    return c;
-}
-
 __global__ void __launch_bounds__(kThreads)
 softsplat_sum_kernel(size_t total, int C, int H, int W, const float* __restrict__ input, const float* __restrict__ flow,
                      float* __restrict__ output)
@@ -131,23 +68,7 @@ softsplat_sum_kernel(size_t total, int C, int H, int W, const float* __restrict_
 }
 
 // ---- the fused blend -------------------------------------------------------------------------------------------------------------
-// Geometry of blend_feature for a square feature of size S: the cut, the padding of the cut size s, the padded size P, where
-// crop_padded_tensor starts.
-struct Geometry { int cut, s, pad, P, crop0; };
-
-inline bool geometry(int S, Geometry* g)
-{
-    if (S < 1) return false;
-    g->cut = S == 1024 ? 3 : S == 512 ? 2 : S == 256 ? 1 : 0;
-    g->s = S - 2 * g->cut;
-    g->pad = g->s / 4 + g->s / 8;
-    if (g->s < 1 || g->pad >= g->s) return false;
-    g->P = g->s + 2 * g->pad;
-    g->crop0 = (g->P - S) / 2;
-    if ((size_t)g->P * g->P >= ((size_t)1 << 31)) return false;
-    return g->crop0 >= 0 && g->crop0 + S <= g->P;
-}
-
+// Geometry (eulerian_dev.h): the cut, the padding of the cut size s, the padded size P, where crop_padded_tensor starts.
 struct Entry { int at[4]; float w[4]; float z; int src; };       // one (source pixel, half): 40 bytes
 
 // Workgroup: kThreads / 2 consecutive source pixels of the padded domain, both halves; thread t walks the chain of pixel t / 2,
@@ -172,19 +93,11 @@ eulerian_blend_kernel(int C, int S, Geometry g, int idx, int n_frames, float z_f
     e.src = 0;
     if (pix < npix) {
         const int px = (int)(pix % P), py = (int)(pix / P);
-        const float sign = half ? -1.0f : 1.0f;                   // the past half integrates pad(-flow) = -pad(flow)
-        auto fetch = [&](int ix, int iy, float& mx, float& my) {
-            const size_t at = (size_t)(reflect(iy - g.pad, g.s) + g.cut) * S + (reflect(ix - g.pad, g.s) + g.cut);
-            mx = sign * motion[at];
-            my = sign * motion[plane + at];
-        };
-        const float2 d = walk_chain(px, py, P, P, half ? n_frames - idx - 1 : idx, fetch, (float*)nullptr, 0, 0);
         // joint_splatting.py:30-33: the second half's SOURCES lie P columns to the right with P taken off their x flow, so both halves
-        // aim at columns [0, P) of the double canvas; the two fp32 roundings are reproduced.  What lands in columns [P, 2P) the
-        // reference crops away (output_size): dropped here like any target outside the canvas
-        const float ox = half ? (float)(px + P) + (d.x - (float)P) : (float)px + d.x;
-        const float oy = (float)py + d.y;
-        const Corners c = corners(ox, oy, P, P);
+        // aim at columns [0, P) of the double canvas (blend_target reproduces the two fp32 roundings).  What lands in columns [P, 2P)
+        // the reference crops away (output_size): dropped here like any target outside the canvas
+        const float2 o = blend_target(px, py, half, S, g, idx, n_frames, motion);
+        const Corners c = corners(o.x, o.y, P, P);
         for (int k = 0; k < 4; k++) { e.at[k] = c.at[k]; e.w[k] = c.w[k]; }
         e.src = (reflect(py - g.pad, g.s) + g.cut) * S + (reflect(px - g.pad, g.s) + g.cut);
     }
@@ -314,9 +227,8 @@ extern "C" int mom_eulerian_blend(int C, int H, int W, int idx, int n_frames, in
     const size_t npix = (size_t)g.P * g.P;
     if (npix * (size_t)(C + 1) >= ((size_t)1 << 40)) return MOM_EINVAL;
     if (hipMemsetAsync(acc, 0, npix * (size_t)(C + 1) * sizeof(float), (hipStream_t)stream) != hipSuccess) return MOM_ELAUNCH;
-    // cinemagraph_utils.py:135,163,166: alpha is a Python float; the products with the fp32 ones round it to fp32
-    const double alpha = (double)idx / (double)(n_frames - 1);
-    const float z_future = (float)(1.0 - alpha), z_past = (float)alpha;
+    float z_future, z_past;
+    blend_z(idx, n_frames, &z_future, &z_past);
     const size_t blocks = (npix + kThreads / 2 - 1) / (kThreads / 2);
     if (form == 1)
         hipLaunchKernelGGL(eulerian_blend_kernel<1>, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, C, H, g, idx,

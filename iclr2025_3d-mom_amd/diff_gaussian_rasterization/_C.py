@@ -39,6 +39,7 @@ _state = {
     "deterministic": False,    # set_deterministic()
     "ordered": None,           # the ordered backward's cached scratch, made by its first call: ordered_backward
     "field_ordered": None,     # the ordered field backwards' cached scratch (HexPlane, MLP), made by their first call: field_ordered_scratch
+    "warp_ordered": None,      # the ordered warp's cached scratch (stage 1's video), made by its first call: warp_ordered_scratch
 }
 _FLAG_LAG = 4
 
@@ -187,7 +188,10 @@ def set_deterministic(on: bool) -> None:
     mom_raster_backward_ordered.  The field's backward follows the switch too: ops.HexPlaneFunction, ops.DeformMLPFunction and the
     one-node paths run mom_hexplane_backward_ordered (one shared timestamp; per-point timestamps raise MomError) and, for the f32
     MLP backward, mom_deform_backward_ordered_n, out of a second grow-only scratch (field_ordered_scratch).  The fused training
-    steps have no ordered form and raise MomError while the switch is on.
+    steps have no ordered form and raise MomError while the switch is on.  Stage 1's video follows it as well: the warp of
+    cinemagraph (warp_one_level, pixel_video, the splat of FunctionSoftsplat; ops.eulerian_blend and ops.softsplat_sum with
+    ordered=None) runs mom_eulerian_blend_ordered / mom_softsplat_sum_ordered out of a third grow-only scratch
+    (warp_ordered_scratch), so the frames stage 2 trains on are the same bits run after run.
     False (default): the atomic form; nothing of the above is allocated or called."""
     _state["deterministic"] = bool(on)
 
@@ -212,6 +216,19 @@ def field_ordered_scratch(which, need, dev):
         o[which] = None                                         # (freed before its successor is made)
         t = o[which] = torch.empty(need + need // 4, dtype=torch.uint8, device=dev)
     return t
+
+
+def warp_ordered_scratch(need, dev):
+    """The ordered warp's scratch (ops.eulerian_blend and ops.softsplat_sum with ordered on), grow-only and one per process like
+    field_ordered_scratch's, in a slot of its own: stage 1 makes it, a training run never does.  ONE buffer, on the device of the
+    latest call (a call on another device frees it and makes its own), and the same assumption as field_ordered_scratch's: every
+    use is enqueued on the caller's current stream, so a call may overwrite what the call before it left -- ordered warps issued
+    from two streams at once would share it and must not be (mom_eulerian_blend_ordered itself takes whatever scratch its caller hands it)."""
+    o = _state["warp_ordered"]
+    if o is None or o["dev"] != dev or o["scratch"].numel() < need:
+        _state["warp_ordered"] = None                           # (freed before its successor is made)
+        o = _state["warp_ordered"] = dict(dev=dev, scratch=torch.empty(need + need // 4, dtype=torch.uint8, device=dev))
+    return o["scratch"]
 
 
 def ordered_status():

@@ -624,12 +624,14 @@ def refit_scene_flow(input_dir, train_iteration=200, device=None, sampler="gridd
     return flow
 
 
-def write_pixel_video(input_dir, n_frames=120, size=1024, center_idx=2, writer=None):
+def write_pixel_video(input_dir, n_frames=120, size=1024, center_idx=2, writer=None, ordered=None):
     """MOM/video/%06d.png of a stage-1 directory from the centre frame of its MOM/train_data.pth -- image, our_flow[0] and mask, what
     the reference hands its VideoGenerator (main_jih.py:27-39) -- by cinemagraph.pixel_video, saved at the data's W x H as
     train_motion.save_video names the frames (train_motion.py:402-412).  A pixel warp, not the reference's StyleGAN output.
     writer: cinemagraph.save_video's -- "host" (the default) copies every frame to the host and resizes and deflates it there; "device"
-    resizes and deflates each frame on the GPU as it is made; the files decode to the same pixels."""
+    resizes and deflates each frame on the GPU as it is made; the files decode to the same pixels.
+    ordered: cinemagraph.warp_one_level's -- None follows diff_gaussian_rasterization._C.set_deterministic; True: the warp adds in a
+    defined order and the frames are the same bits run after run."""
     from . import cinemagraph
     from .scene.dataset_readers import load_train_data
     mom = os.path.join(input_dir, "MOM")
@@ -641,7 +643,7 @@ def write_pixel_video(input_dir, n_frames=120, size=1024, center_idx=2, writer=N
     if writer not in (None,) + cinemagraph.VIDEO_WRITERS:
         raise ValueError(f"writer must be one of {cinemagraph.VIDEO_WRITERS}, got {writer!r}")
     make = cinemagraph.pixel_video_frames if writer == "device" else cinemagraph.pixel_video
-    frames = make(frame["image"], frame["our_flow"][0], frame["mask"], n_frames=n_frames, size=size)
+    frames = make(frame["image"], frame["our_flow"][0], frame["mask"], n_frames=n_frames, size=size, ordered=ordered)
     return cinemagraph.save_video(frames, mom, int(data["W"]), int(data["H"]), writer=writer)
 
 
@@ -844,7 +846,7 @@ def flow_image(flow):
 
 
 def build_stage1(input_dir, depth, flow="hints", train_iteration=200, video="none", render_poses=None, internal_poses=None, size=768,
-                 n_frames=120, video_size=1024, device=None, video_writer=None):
+                 n_frames=120, video_size=1024, device=None, video_writer=None, ordered=None):
     """Stage 1 from an input folder, as train_motion.py:442-464 runs it: image.png, image_json/mask.png and the hints of image.json ->
     MOM/train_data.pth, MOM/scene_flow.pth and MOM/Flow_viz/%03d.png, what stage 2 (Trainer) reads.
     depth: float32 [H,W] or the path of a .npy holding it -- what the reference's depth network returns for the image
@@ -852,7 +854,8 @@ def build_stage1(input_dir, depth, flow="hints", train_iteration=200, video="non
     field as the motion, a SUBSTITUTE for the reference's flow estimator) or the estimator callable of estimate_flows.
     render_poses / internal_poses: [n,3,4] world-to-camera, by default pcd_gen_poses('lookaround') / ('hemisphere').
     video="pixels" also writes MOM/video/%06d.png with write_pixel_video (again a substitute, for the reference's GAN), through its
-    writer `video_writer` ("host", the default, or "device").
+    writer `video_writer` ("host", the default, or "device"); ordered: write_pixel_video's (the video's warp is the one stage-1 kernel
+    with float atomics: with ordered=True, or under _C.set_deterministic(True), the whole folder is a function of the input).
     The renders, the flow arithmetic, the sampling, the fit and our_flow all run on the device (render_pcd, estimate_flows,
     optimize_motion with the device sampler and resampler).  Returns (train_data, scene_flow [3,P] CPU)."""
     from PIL import Image
@@ -889,7 +892,7 @@ def build_stage1(input_dir, depth, flow="hints", train_iteration=200, video="non
     torch.save(train_data, os.path.join(mom, "train_data.pth"))
     torch.save(scene_flow, os.path.join(mom, "scene_flow.pth"))
     if video == "pixels":
-        write_pixel_video(input_dir, n_frames, video_size, writer=video_writer)
+        write_pixel_video(input_dir, n_frames, video_size, writer=video_writer, ordered=ordered)
     return train_data, scene_flow
 
 
@@ -920,7 +923,12 @@ def main(argv=None):
     ap.add_argument("--size", type=int, default=768, help="--build: the flow estimator's working size (config.yaml's data.W)")
     ap.add_argument("--render_poses", type=int, default=None, help="--build: use only the first N of the five 'lookaround' poses")
     ap.add_argument("--seed", type=int, default=None, help="--build: seed numpy's global generator, which draws every view's sigma")
+    ap.add_argument("--deterministic", action="store_true", help="diff_gaussian_rasterization._C.set_deterministic(True) before any work: "
+                    "the --video warp adds in a defined order, so the frames are the same bits run after run")
     a = ap.parse_args(argv)
+    if a.deterministic:
+        from .diff_gaussian_rasterization import _C
+        _C.set_deterministic(True)
     if a.build:
         if not a.depth:
             ap.error("--build needs --depth FILE")

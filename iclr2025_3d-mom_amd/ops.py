@@ -690,9 +690,16 @@ def euler_integrate(motion, steps, all_frames=False):
     return disp
 
 
-def softsplat_sum(input, flow):
+def _warp_ordered(ordered):
+    """The `ordered` argument of the warp's ops: None follows the process-wide switch (_RC.set_deterministic)."""
+    return _RC.deterministic() if ordered is None else bool(ordered)
+
+
+def softsplat_sum(input, flow, ordered=None):
     """The forward of the reference's _FunctionSoftsplat (softmax_splatting.py:8-53, 236-269): input [N,C,H,W] splatted along
-    flow [N,2,H,W] with bilinear weights into a new [N,C,H,W]; targets outside the canvas are dropped."""
+    flow [N,2,H,W] with bilinear weights into a new [N,C,H,W]; targets outside the canvas are dropped.
+    ordered (None: as diff_gaussian_rasterization._C.deterministic() says): mom_softsplat_sum_ordered, the sums in the order
+    include/mom4d.h defines, out of the grow-only scratch _RC.warp_ordered_scratch; False: float atomics, no scratch."""
     if input.dim() != 4 or flow.dim() != 4 or flow.shape[1] != 2 or flow.shape[0] != input.shape[0] \
             or flow.shape[2:] != input.shape[2:] or 0 in input.shape:
         raise N.MomError(f"softsplat_sum: input [N,C,H,W] and flow [N,2,H,W] are needed, got {tuple(input.shape)} and "
@@ -700,6 +707,14 @@ def softsplat_sum(input, flow):
     _f32_device("softsplat_sum", input=input, flow=flow)
     n, c, H, W = input.shape
     out = torch.zeros_like(input)
+    if _warp_ordered(ordered):
+        need = N.lib().mom_softsplat_ordered_scratch_bytes(n, c, H, W)
+        if need == 0:
+            raise N.MomError(f"softsplat_sum: the ordered splat does not take {tuple(input.shape)} (include/mom4d.h has its limits)")
+        scratch = _RC.warp_ordered_scratch(need, input.device)
+        N.check(N.lib().mom_softsplat_sum_ordered(n, c, H, W, N.ptr(input), N.ptr(flow), N.ptr(out), N.ptr(scratch), scratch.numel(),
+                                                  N.current_stream()), "mom_softsplat_sum_ordered")
+        return out
     N.check(N.lib().mom_softsplat_sum(n, c, H, W, N.ptr(input), N.ptr(flow), N.ptr(out), N.current_stream()), "mom_softsplat_sum")
     return out
 
@@ -707,10 +722,13 @@ def softsplat_sum(input, flow):
 EULERIAN_FORM = {"channels": 0, "pixels": 1}     # mom_eulerian_blend's `form`: which index runs on the fastest lanes
 
 
-def eulerian_blend(feature, motion, idx, n_frames, acc=None, form="channels"):
+def eulerian_blend(feature, motion, idx, n_frames, acc=None, form="channels", ordered=None):
     """blend_feature's cut, reflection padding, two Euler chains and joint splat (cinemagraph_utils.py:131-178) as one launch
     into the channel-last accumulator acc [padded,padded,C+1] (feature Z in the first C channels, Z in the last), which is
-    cleared first and returned.  feature [C,S,S], motion [2,S,S]."""
+    cleared first and returned.  feature [C,S,S], motion [2,S,S].
+    ordered (None: as diff_gaussian_rasterization._C.deterministic() says): mom_eulerian_blend_ordered -- entries sorted by cell and
+    every texel's sum pulled in the order include/mom4d.h defines, the same bits run after run, whatever `form` says -- out of the
+    grow-only scratch _RC.warp_ordered_scratch; False: float atomics, no scratch."""
     if feature.dim() != 3 or motion.dim() != 3 or motion.shape[0] != 2 or feature.shape[0] < 1:
         raise N.MomError(f"eulerian_blend: feature [C,S,S] and motion [2,S,S] are needed, got {tuple(feature.shape)} and "
                          f"{tuple(motion.shape)}")
@@ -732,6 +750,14 @@ def eulerian_blend(feature, motion, idx, n_frames, acc=None, form="channels"):
     _f32_device("eulerian_blend", **tensors)
     if acc is None:
         acc = torch.empty((padded, padded, c + 1), dtype=torch.float32, device=feature.device)
+    if _warp_ordered(ordered):
+        need = N.lib().mom_eulerian_ordered_scratch_bytes(c, H)
+        if need == 0:
+            raise N.MomError(f"eulerian_blend: the ordered blend does not take {tuple(feature.shape)} (include/mom4d.h has its limits)")
+        scratch = _RC.warp_ordered_scratch(need, feature.device)
+        N.check(N.lib().mom_eulerian_blend_ordered(c, H, W, idx, n_frames, N.ptr(feature), N.ptr(motion), N.ptr(acc), N.ptr(scratch),
+                                                   scratch.numel(), N.current_stream()), "mom_eulerian_blend_ordered")
+        return acc
     N.check(N.lib().mom_eulerian_blend(c, H, W, idx, n_frames, EULERIAN_FORM[form], N.ptr(feature), N.ptr(motion), N.ptr(acc),
                                        N.current_stream()), "mom_eulerian_blend")
     return acc

@@ -851,6 +851,53 @@ int mom_eulerian_blend(int C, int H, int W, int idx, int n_frames, int form, con
                        mom_stream_t stream);
 int mom_eulerian_finish(int C, int S, int full, const float* acc, float* out, uint8_t* blank, mom_stream_t stream);
 
+/* ---- ordered splat of the video generator's warp: an accumulator that is a function of its inputs, bit for bit -------------------
+ * mom_eulerian_blend and mom_softsplat_sum add with float atomics, in whatever order the waves arrive.  The ordered forms are a PULL:
+ * a texel's sum is formed by the texel's owner from the entries of the four cells around it, with no float atomic anywhere
+ * (csrc/eulerian_ordered.hip).  Same contract as the atomic entries: stream-ordered, no allocation, copy or synchronisation,
+ * MOM_EINVAL before anything is launched; acc is [padded,padded,C+1] channel-last and mom_eulerian_finish takes it unchanged (the
+ * ordered blend stores every element of it: no memset node); mom_softsplat_sum_ordered adds onto `output`.
+ *
+ * ENTRIES.  The blend: e = h padded^2 + (y padded + x), h = 0 the future half, h = 1 the past half, (y, x) the source pixel of the
+ * cut, reflection-padded domain.  The splat: e = y W + x, per image.  An entry's target (ox, oy) is what the atomic form computes, bit
+ * for bit (the same chain walk; for the past half the two roundings (float)(x + padded) + (d - (float)padded)).  It lies in cell
+ * (y0, x0) = (floor oy, floor ox); its four weights are those of softmax_splatting.py:32-35 as formed there.  An entry the atomic form
+ * drops whole (a NaN target, or a magnitude not below 2^30) has no terms.  A corner outside the canvas is no term; a corner inside
+ * the canvas with weight 0 is one.
+ * TERMS.  The products the atomic form adds, each one fp32 multiply: the blend's (feature[c] Z_h) w for the C channels and Z_h w
+ * (formed as (1.0f Z_h) w) for the metric; the splat's input[c] w.
+ * ORDER.  Texel (y, x), channel c receives four classes:
+ *   k = 0  nw: the entries of cell (y, x)        k = 1  ne: cell (y, x-1)
+ *   k = 2  sw: cell (y-1, x)                     k = 3  se: cell (y-1, x-1)
+ * with cells running over [-1, H-1] x [-1, W-1] (H = W = padded for the blend).  Within a class the cell's entries are taken in
+ * ascending e.  The terms are cut into blocks of 64 from the first:
+ *   b_j = (...((+0.0 + e_64j) + e_64j+1) + ...)  left to right;      s_k = (...((+0.0 + b_0) + b_1) + ...)  left to right;
+ *   T = (s_0 + s_1) + (s_2 + s_3)  (s_k = +0.0 for a class without terms).
+ * The blend stores acc = T for every texel and channel: a texel nothing reaches holds +0.0, which mom_eulerian_finish reads as
+ * blank.  The splat stores out = out_in + T, one add onto whatever the buffer held; a texel without a term in any class is not
+ * written.  The result is a function of the feature (input), the motion (flow), idx and n_frames alone -- not of a grid size, a
+ * `form`, an environment switch or which wave arrives first.  The _host entries reproduce it on the host (plain C++, no GPU, no
+ * contraction) from HOST pointers.
+ *
+ * SCRATCH (mom_eulerian_ordered_scratch_bytes(C, S), mom_softsplat_ordered_scratch_bytes(N, C, H, W); 0 for a shape the call
+ * refuses).  n entries and m cells (blend: n = 2 padded^2, m = (padded+1)^2; splat: n = H W, m = (H+1)(W+1), one image after the
+ * other out of the same buffers), every part at the next multiple of 256 bytes: the entries' records {ox, oy, Z, source index}
+ * (16 n bytes), the sort's two key and two value buffers (4 n bytes each) and its counters, the cells' segment table (4 (m + 1)
+ * bytes) and, for the blend at C >= 16, a channel-last copy of the feature (4 S S C bytes).  Every byte a call reads it has written
+ * first.
+ * LIMITS.  The sort's keys and values are 32 bits and its positions ints: n <= 2^30 and m < 2^31.  MOM_EINVAL before anything is
+ * launched: everything mom_eulerian_blend (without `form`) or mom_softsplat_sum refuses; n or m beyond those limits; scratch null or
+ * not aligned to 256 bytes; scratch_bytes below the sizing function's value.  The _host entries refuse the same shapes and null
+ * pointers. */
+size_t mom_eulerian_ordered_scratch_bytes(int C, int S);
+int mom_eulerian_blend_ordered(int C, int H, int W, int idx, int n_frames, const float* feature, const float* motion, float* acc,
+                               void* scratch, size_t scratch_bytes, mom_stream_t stream);
+size_t mom_softsplat_ordered_scratch_bytes(int N, int C, int H, int W);
+int mom_softsplat_sum_ordered(int N, int C, int H, int W, const float* input, const float* flow, float* output, void* scratch,
+                              size_t scratch_bytes, mom_stream_t stream);
+int mom_eulerian_blend_ordered_host(int C, int H, int W, int idx, int n_frames, const float* feature, const float* motion, float* acc);
+int mom_softsplat_sum_ordered_host(int N, int C, int H, int W, const float* input, const float* flow, float* output);
+
 /* ---- the native ops of the StyleGAN2 under that generator (thirdparty/StyleCineGAN/models/stylegan2/op, and the encoder's copy under
  * external_modules/feature_style_encoder/pixel2style2pixel; csrc/stylegan_ops.hip) ----
  * The reference compiles both from CUDA sources when the package is imported and has no other path.  fp32, caller-allocated outputs,
