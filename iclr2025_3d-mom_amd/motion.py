@@ -38,6 +38,7 @@ the reference's output -- `--flow hints` takes the dense hint field itself as th
 looping video with the video generator's warp (cinemagraph.py) from the image's pixels instead of StyleGAN features.
 
     python -m iclr2025_3d-mom_amd.motion --input_dir DIR [--train_iteration N] [--sampler device] [--resampler device]
+                                          [--triangulator device]
     python -m iclr2025_3d-mom_amd.motion --input_dir DIR --video pixels [--n_frames 120] [--video_size 1024] [--video-writer device]
     python -m iclr2025_3d-mom_amd.motion --input_dir DIR --build --depth FILE [--flow hints] [--video pixels]
 """
@@ -61,7 +62,8 @@ class ViewSet:
     valid[j]: the indices of view j's valid set, ascending (:173-177); pix0[j]: [2, n_j] float32, the unflowed pixels (:180,183);
     pix64[j]: the same pixels before that cast, as the reference hands them to griddata (:115,120) -- prepare_views fills it.
     simplices[j]: int32 [T_j, 3], view j's Delaunay triangulation (triangulate_views fills and keeps it); packed: what
-    upload_views put on a device, kept for the next use on that device."""
+    upload_views put on a device, kept for the next use on that device; fallbacks: after an upload with the device triangulator
+    the (view, status) pairs the device refused and scipy triangulated instead."""
     P: int
     H: int
     W: int
@@ -72,6 +74,7 @@ class ViewSet:
     pix64: Optional[List[np.ndarray]] = None
     simplices: Optional[List[np.ndarray]] = None
     packed: Optional[dict] = None
+    fallbacks: Optional[list] = None
 
     @property
     def V(self):
@@ -306,19 +309,44 @@ def sample_flow_images(views, flow_images, diagonals=None, device=None):
 
 SAMPLERS = ("griddata", "device")
 RESAMPLERS = ("griddata", "device")
+TRIANGULATORS = ("host", "device")
 MAX_WORKERS = 16
+DELAUNAY_SCRATCH_BYTES = 1 << 30          # the device triangulator takes the views in chunks whose scratch stays below this
 
 
-def triangulate_views(views, workers=8):
+def _triangulator(triangulator):
+    """The switch, checked: None means "host"."""
+    triangulator = "host" if triangulator is None else triangulator
+    if triangulator not in TRIANGULATORS:
+        raise ValueError(f"triangulator must be one of {TRIANGULATORS}, got {triangulator!r}")
+    return triangulator
+
+
+def triangulate_views(views, workers=8, triangulator="host"):
     """Per view of a ViewSet the simplices of scipy.spatial.Delaunay over pix64[j].T -- exactly the points, and the Qhull options,
     griddata triangulates (train_motion.py:198,304,319) -- as int32 [T_j, 3], in a pool of `workers` threads (Qhull releases the
     GIL; at most 16, never sized by the machine).  The list is kept on the ViewSet: every later consumer of the same views
     (render_pcd, optimize_motion's our_flow, resample_to_grid) finds it there.  A view with fewer than 3 valid points, or one
-    Qhull rejects (collinear points, say), raises ValueError naming the view."""
+    Qhull rejects (collinear points, say), raises ValueError naming the view.
+    triangulator="device": the views are uploaded and triangulated there (upload_views; ops.delaunay, csrc/delaunay.hip) and the
+    list is what comes back: the same triangles in the canonical order of include/mom4d.h, scipy's own for a view the device refused."""
+    triangulator = _triangulator(triangulator)
     if views.simplices is not None:
         return views.simplices
     if views.pix64 is None:
         raise ValueError("the ViewSet carries no float64 pixels (pix64): build it with prepare_views")
+    if triangulator == "device":
+        pk = upload_views(views, workers=workers, triangulator="device")
+        tris, off = pk["tris"].cpu().numpy(), pk["tri_off"].cpu().numpy()
+        views.simplices = [np.ascontiguousarray(tris[off[j]:off[j + 1]]) for j in range(views.V)]
+        return views.simplices
+    views.simplices = _qhull_views(views, range(views.V), workers)
+    return views.simplices
+
+
+def _qhull_views(views, which, workers):
+    """scipy.spatial.Delaunay's simplices of the views `which`, in the thread pool."""
+    which = list(which)
     try:
         from scipy.spatial import Delaunay, QhullError
     except ImportError as e:
@@ -334,14 +362,48 @@ def triangulate_views(views, workers=8):
         except QhullError as e:
             raise ValueError(f"view {j}: Qhull cannot triangulate its {pts.shape[0]} points ({str(e).strip().splitlines()[0]})") from e
 
-    workers = max(1, min(int(workers), MAX_WORKERS, views.V))
+    workers = max(1, min(int(workers), MAX_WORKERS, len(which)))
     if workers == 1:
-        tris = [one(j) for j in range(views.V)]
-    else:
-        with ThreadPoolExecutor(max_workers=workers) as pool:
-            tris = list(pool.map(one, range(views.V)))
-    views.simplices = tris
-    return tris
+        return [one(j) for j in which]
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        return list(pool.map(one, which))
+
+
+def _delaunay_chunks(counts, H, W):
+    """Runs of views [j0, j1) whose ops.delaunay scratch stays below DELAUNAY_SCRATCH_BYTES (a run has at least one view)."""
+    runs, j0, n = [], 0, 0
+    for j, c in enumerate(counts):
+        if j > j0 and 4 * ops.delaunay_scratch_elements(j + 1 - j0, H, W, n + c) > DELAUNAY_SCRATCH_BYTES:
+            runs.append((j0, j))
+            j0, n = j, 0
+        n += c
+    return runs + [(j0, len(counts))]
+
+
+def _device_triangulation(views, pts, counts, dev, workers):
+    """(tris [T,3] int32, tri_off [V+1] int32) on the device for points already there: ops.delaunay per chunk of views, only status
+    and tri_off read back; a view the device refuses is triangulated by scipy and spliced in (views.fallbacks names it)."""
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    parts, fallbacks = [None] * views.V, []
+    for j0, j1 in _delaunay_chunks(counts, views.H, views.W):
+        local = _upload((off[j0:j1 + 1] - off[j0]).astype(np.int32), dev)
+        tris, tri_off_dev, status = ops.delaunay(pts[off[j0]:off[j1]], local, views.H, views.W)
+        tri_off, status = tri_off_dev.cpu().numpy(), status.cpu().numpy()
+        for j in range(j0, j1):
+            st = int(status[j - j0])
+            if st == ops.N.DELAUNAY_FEW:
+                raise ValueError(f"view {j} has {counts[j]} valid points: a triangulation needs at least 3")
+            if st != ops.N.DELAUNAY_OK:
+                fallbacks.append((j, st))
+            else:
+                parts[j] = tris[tri_off[j - j0]:tri_off[j - j0 + 1]]
+        if j0 == 0 and j1 == views.V and not fallbacks:
+            views.fallbacks = []
+            return tris[:tri_off[-1]], tri_off_dev
+    for (j, _), t in zip(fallbacks, _qhull_views(views, [j for j, _ in fallbacks], workers)):
+        parts[j] = _upload(t.astype(np.int32).reshape(-1, 3), dev)
+    views.fallbacks = fallbacks
+    return torch.cat(parts).contiguous(), _upload(_offsets([len(t) for t in parts]), dev)
 
 
 def _offsets(counts):
@@ -352,15 +414,29 @@ def _offsets(counts):
     return off.astype(np.int32)
 
 
-def upload_views(views, device=None, workers=8):
+def upload_views(views, device=None, workers=8, triangulator="host"):
     """What ops.tri_resample and ops.pcd_compose read of a ViewSet, on the device: pts [N,2] float64 (the views' pixels
     concatenated), pt_off, tris [T,3] int32, tri_off, and `gather` [N] int64 = j P + valid[j], the rows of a dense [V,P,C] tensor in
-    that order.  Triangulates first when the ViewSet has no simplices yet; kept on the ViewSet per device."""
+    that order.  Triangulates first when the ViewSet has no simplices yet; kept on the ViewSet per device.
+    triangulator="device" (and no simplices yet): the points are uploaded, ops.delaunay triangulates them there and only its status
+    and tri_off are read back; a view with fewer than 3 points raises as on the host route, a view the device refuses for any other
+    reason (an exact grid, say) is triangulated by scipy in the thread pool and listed in views.fallbacks with its status.  Without
+    such a view scipy is not needed.  views.simplices stays empty until triangulate_views is asked for it."""
+    triangulator = _triangulator(triangulator)
     dev = torch.device("cuda" if device is None else device)
     if views.packed is not None and views.packed["device"] == dev:
         return views.packed
-    tris = triangulate_views(views, workers)
     up = lambda a: _upload(a, dev)
+    if triangulator == "device" and views.simplices is None:
+        if views.pix64 is None:
+            raise ValueError("the ViewSet carries no float64 pixels (pix64): build it with prepare_views")
+        counts = [len(v) for v in views.valid]
+        pts = up(np.concatenate([p.T for p in views.pix64]).astype(np.float64))
+        tris, tri_off = _device_triangulation(views, pts, counts, dev, workers)
+        views.packed = dict(device=dev, pts=pts, pt_off=up(_offsets(counts)), tris=tris, tri_off=tri_off,
+                            gather=up(np.concatenate([j * views.P + np.asarray(v, np.int64) for j, v in enumerate(views.valid)])))
+        return views.packed
+    tris = triangulate_views(views, workers)
     views.packed = dict(device=dev,
                         pts=up(np.concatenate([p.T for p in views.pix64]).astype(np.float64)),
                         pt_off=up(_offsets([len(v) for v in views.valid])),
@@ -382,14 +458,15 @@ def upload_values(views, values, device=None):
     return _upload(np.concatenate(rows), dev)
 
 
-def resample_to_grid(views, values, fill=0.0, device=None, workers=8):
+def resample_to_grid(views, values, fill=0.0, device=None, workers=8, triangulator="host"):
     """Values given at every view's valid points, linearly interpolated at every pixel centre: what
     griddata(pix64[j].T, values[j], pixel grid, method="linear", fill_value=fill) gives per view, for all views in one call of
     ops.tri_resample.  values: per view an [n_j, C] array or tensor (read as float32), what upload_values made of such a list, or
     one dense [V,P,C] device tensor such as fit_scene_flow's flow2d, whose valid rows are gathered on the device.  Returns
-    [V,H,W,C] float64 on the device; with the views uploaded (upload_views) and the values on the device it only enqueues."""
+    [V,H,W,C] float64 on the device; with the views uploaded (upload_views) and the values on the device it only enqueues.
+    triangulator: where views that are not uploaded yet are triangulated (upload_views)."""
     dev = torch.device("cuda" if device is None else device)
-    pk = upload_views(views, dev, workers)
+    pk = upload_views(views, dev, workers, triangulator)
     if torch.is_tensor(values) and values.dim() == 3:
         if values.shape[:2] != (views.V, views.P):
             raise ValueError(f"dense values must be [{views.V}, {views.P}, C], got {tuple(values.shape)}")
@@ -468,16 +545,16 @@ def pcd_values(views, colors, mask_colors):
     return [rgbm[v] for v in views.valid]
 
 
-def render_pcd_device(views, values, device=None, workers=8):
+def render_pcd_device(views, values, device=None, workers=8, triangulator="host"):
     """The device part of render_pcd: (image [V,H,W,3], mask [V,H,W]) uint8 on the device for a ViewSet of the point cloud and its
     (r, g, b, m) values (pcd_values, or what upload_values made of them).  One tri_resample and one pcd_compose: eight launches for
     all views; with the views and the values uploaded it only enqueues."""
     dev = torch.device("cuda" if device is None else device)
-    pk = upload_views(views, dev, workers)
+    pk = upload_views(views, dev, workers, triangulator)
     return ops.pcd_compose(resample_to_grid(views, values, fill=0.0, device=dev), pk["pts"], pk["pt_off"])
 
 
-def render_pcd(src_img, src_mask, depth, hints, render_poses, internal_poses, device=None, workers=8, K=None):
+def render_pcd(src_img, src_mask, depth, hints, render_poses, internal_poses, device=None, workers=8, K=None, triangulator="host"):
     """MotionOptimization.render_PCD (train_motion.py:211-366): the renders of the source image's point cloud from
     len(render_poses) x len(internal_poses) views, which stage 2 trains on.  src_img, src_mask: PIL images (or arrays) of one size;
     depth [H,W]: the source depth (the reference's self.src_depth; the depth network is not part of this package); hints: four lists
@@ -486,8 +563,10 @@ def render_pcd(src_img, src_mask, depth, hints, render_poses, internal_poses, de
     view is triangulated once (triangulate_views, `workers` threads) and the resampling, the border, the mask morphology and the
     8-bit cast run on the device for all views at once (render_pcd_device).  The reference's depth image (:307-308) is never used
     and is not computed.  Returns (train_data, none_idx) in the reference's layout (:251-260,354-364): `image` and `mask` are PIL
-    images, T2C_flow and our_flow empty lists; a slot that sees no point is in none_idx and has no frame."""
+    images, T2C_flow and our_flow empty lists; a slot that sees no point is in none_idx and has no frame.
+    triangulator: "host" (scipy, `workers` threads) or "device" (upload_views: ops.delaunay, scipy only for a view it refuses)."""
     from PIL import Image
+    triangulator = _triangulator(triangulator)
     depth = np.asarray(depth)
     H, W = depth.shape
     if K is None:
@@ -505,7 +584,7 @@ def render_pcd(src_img, src_mask, depth, hints, render_poses, internal_poses, de
                   "W": W, "H": H, "pcd_points": world.copy(), "pcd_colors": colors.copy(), "pcd_masks": mask_colors.copy(), "frames": []}
     slots = compose_slots(render_poses, internal_poses)
     views, present, none_idx = pcd_views(world, K, slots, H, W)
-    image, mask = (t.cpu().numpy() for t in render_pcd_device(views, pcd_values(views, colors, mask_colors), device, workers))
+    image, mask = (t.cpu().numpy() for t in render_pcd_device(views, pcd_values(views, colors, mask_colors), device, workers, triangulator))
     for k, idx in enumerate(present):
         R, T = slots[idx]
         sx, sy = _project_hints(starts, K, R, T)
@@ -545,20 +624,22 @@ def _fit_slots(train_data, slots, K, H, W, train_iteration, device=None, sampler
 
 
 def optimize_motion(train_data, render_poses, internal_poses, K, H, W, non_frame_idx=(), train_iteration=200, device=None,
-                    sampler="griddata", resampler="griddata", workers=8):
+                    sampler="griddata", resampler="griddata", workers=8, triangulator="host"):
     """MotionOptimization.optimize_motion (train_motion.py:65-207) without its unused arguments: view slot idx = i * len(internal)
     + j has the pose internal[j] o render[i] (:91-97); slots in non_frame_idx have no flow; the k-th remaining slot takes
     train_data['frames'][k]['T2C_flow'][0].  After the fit each fitted slot's last-epoch 2D flow is resampled onto the pixel
     grid and appended to train_data['frames'][idx]['our_flow'] -- indexed by the SLOT, as the reference does (:200) -- as a
     [1,2,H,W] float64 CPU tensor.  resampler: "griddata" does that with one scipy griddata per view on the host, as the reference
     does; "device" triangulates each view once on `workers` host threads (triangulate_views) and resamples all views in one call
-    (resample_to_grid) from the flow the fit left on the device.  Returns (train_data, scene_flow [3,P] on the device)."""
+    (resample_to_grid) from the flow the fit left on the device; triangulator="device" triangulates them there as well
+    (upload_views).  Returns (train_data, scene_flow [3,P] on the device)."""
     if resampler not in RESAMPLERS:
         raise ValueError(f"resampler must be one of {RESAMPLERS}, got {resampler!r}")
+    triangulator = _triangulator(triangulator)
     slots = [None if idx in non_frame_idx else s for idx, s in enumerate(compose_slots(render_poses, internal_poses))]
     views, present, _, flow, _, flow2d = _fit_slots(train_data, slots, K, H, W, train_iteration, device, sampler)
     if train_iteration > 0 and resampler == "device":
-        final = resample_to_grid(views, flow2d, fill=0.0, device=flow2d.device, workers=workers).permute(0, 3, 1, 2).cpu()
+        final = resample_to_grid(views, flow2d, fill=0.0, device=flow2d.device, workers=workers, triangulator=triangulator).permute(0, 3, 1, 2).cpu()
         for k, idx in enumerate(present):
             train_data["frames"][idx]["our_flow"].append(final[k].contiguous().unsqueeze(0))
     elif train_iteration > 0:
@@ -597,13 +678,14 @@ def stage1_intrinsics(H, W):
     return np.array([[FOCAL * (W / H), 0., W / 2], [0., FOCAL, H / 2], [0., 0., 1.]]).astype(np.float32)
 
 
-def refit_scene_flow(input_dir, train_iteration=200, device=None, sampler="griddata", resampler="griddata"):
+def refit_scene_flow(input_dir, train_iteration=200, device=None, sampler="griddata", resampler="griddata", triangulator="host"):
     """Fits the scene flow of a stage-1 directory again from what MOM/train_data.pth holds -- the point cloud, every frame's pose
     (its transform_matrix) and 2D flow (T2C_flow) -- and writes MOM/scene_flow.pth.  A frame with an empty T2C_flow list is a view
     without a flow.  sampler: "griddata" (one scipy call per view on the host) or "device" (_fit_slots).  resampler: checked like
     optimize_motion's and otherwise without effect here -- the refit writes the scene flow alone, and our_flow, the one thing the
-    resampler makes, is not part of it.  Returns the [3,P] flow (a CPU tensor, what is written)."""
+    resampler makes, is not part of it; triangulator likewise.  Returns the [3,P] flow (a CPU tensor, what is written)."""
     from .scene.dataset_readers import load_train_data
+    _triangulator(triangulator)
     if sampler not in SAMPLERS:
         raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
     if resampler not in RESAMPLERS:
@@ -846,7 +928,7 @@ def flow_image(flow):
 
 
 def build_stage1(input_dir, depth, flow="hints", train_iteration=200, video="none", render_poses=None, internal_poses=None, size=768,
-                 n_frames=120, video_size=1024, device=None, video_writer=None, ordered=None):
+                 n_frames=120, video_size=1024, device=None, video_writer=None, triangulator="host", ordered=None):
     """Stage 1 from an input folder, as train_motion.py:442-464 runs it: image.png, image_json/mask.png and the hints of image.json ->
     MOM/train_data.pth, MOM/scene_flow.pth and MOM/Flow_viz/%03d.png, what stage 2 (Trainer) reads.
     depth: float32 [H,W] or the path of a .npy holding it -- what the reference's depth network returns for the image
@@ -857,8 +939,10 @@ def build_stage1(input_dir, depth, flow="hints", train_iteration=200, video="non
     writer `video_writer` ("host", the default, or "device"); ordered: write_pixel_video's (the video's warp is the one stage-1 kernel
     with float atomics: with ordered=True, or under _C.set_deterministic(True), the whole folder is a function of the input).
     The renders, the flow arithmetic, the sampling, the fit and our_flow all run on the device (render_pcd, estimate_flows,
-    optimize_motion with the device sampler and resampler).  Returns (train_data, scene_flow [3,P] CPU)."""
+    optimize_motion with the device sampler and resampler); triangulator: where their views are triangulated, "host" (scipy's
+    thread pool, the default) or "device" (upload_views).  Returns (train_data, scene_flow [3,P] CPU)."""
     from PIL import Image
+    triangulator = _triangulator(triangulator)
     if video not in ("none", "pixels"):
         raise ValueError(f"video must be 'none' or 'pixels', got {video!r}")
     if not (flow == "hints" or callable(flow)):
@@ -879,10 +963,12 @@ def build_stage1(input_dir, depth, flow="hints", train_iteration=200, video="non
     internal_poses = pcd_gen_poses("hemisphere") if internal_poses is None else np.asarray(internal_poses)
     mom = os.path.join(input_dir, "MOM")
     os.makedirs(mom, exist_ok=True)
-    train_data, none_idx = render_pcd(src_img, src_mask, depth.astype(np.float32), hints, render_poses, internal_poses, device=device)
+    train_data, none_idx = render_pcd(src_img, src_mask, depth.astype(np.float32), hints, render_poses, internal_poses, device=device,
+                                      triangulator=triangulator)
     train_data = estimate_flows(train_data, None if flow == "hints" else flow, size=size, device=device)
     train_data, scene_flow = optimize_motion(train_data, render_poses, internal_poses, K, H, W, non_frame_idx=none_idx,
-                                             train_iteration=train_iteration, device=device, sampler="device", resampler="device")
+                                             train_iteration=train_iteration, device=device, sampler="device", resampler="device",
+                                             triangulator=triangulator)
     scene_flow = scene_flow.cpu()
     viz = os.path.join(mom, "Flow_viz")
     os.makedirs(viz, exist_ok=True)
@@ -906,6 +992,8 @@ def main(argv=None):
     ap.add_argument("--resampler", choices=RESAMPLERS, default="griddata", help="where optimize_motion resamples our_flow onto the "
                     "pixel grid: scipy's griddata per view on the host, or one triangulation per view and the device for the rest; "
                     "scene_flow.pth does not depend on it")
+    ap.add_argument("--triangulator", choices=TRIANGULATORS, default="host", help="where each view's scattered points are triangulated: "
+                    "scipy's Delaunay on host threads, or the device (scipy then only for a view the device refuses)")
     ap.add_argument("--video", choices=("none", "pixels"), default="none", help="pixels: instead of the fit, write MOM/video/%%06d.png "
                     "from frame 2's image, our_flow and mask by warping the image's PIXELS (cinemagraph.pixel_video) -- a substitute "
                     "for the reference's StyleGAN video, which needs checkpoints; no mp4 is written")
@@ -937,7 +1025,7 @@ def main(argv=None):
         poses = None if a.render_poses is None else pcd_gen_poses("lookaround")[:a.render_poses]
         data, flow = build_stage1(a.input_dir, a.depth, flow=a.flow, train_iteration=a.train_iteration, video=a.video,
                                   render_poses=poses, size=a.size, n_frames=a.n_frames, video_size=a.video_size,
-                                  video_writer=a.video_writer)
+                                  video_writer=a.video_writer, triangulator=a.triangulator)
         print(f"{os.path.join(a.input_dir, 'MOM')}: {len(data['frames'])} frames; scene_flow.pth: {tuple(flow.shape)}, largest "
               f"magnitude {float(flow.abs().max()):.6g}")
         return
@@ -945,7 +1033,7 @@ def main(argv=None):
         paths = write_pixel_video(a.input_dir, a.n_frames, a.video_size, writer=a.video_writer)
         print(f"{os.path.dirname(paths[0])}: {len(paths)} frames")
         return
-    flow = refit_scene_flow(a.input_dir, a.train_iteration, sampler=a.sampler, resampler=a.resampler)
+    flow = refit_scene_flow(a.input_dir, a.train_iteration, sampler=a.sampler, resampler=a.resampler, triangulator=a.triangulator)
     print(f"scene_flow.pth: {tuple(flow.shape)}, largest magnitude {float(flow.abs().max()):.6g}")
 
 

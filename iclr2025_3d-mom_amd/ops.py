@@ -1037,6 +1037,40 @@ def _tri_views(name, pts, pt_off, H, W):
     return V, pts.shape[0], dev
 
 
+def delaunay_scratch_elements(V, H, W, n):
+    """int32 elements of scratch ops.delaunay needs for V views of H x W with n points in all (0: a shape it refuses)."""
+    return (N.lib().mom_delaunay_scratch_bytes(int(V), int(H), int(W), int(n)) + 3) // 4
+
+
+def delaunay(pts, pt_off, H, W, tris=None, tri_off=None, status=None, scratch=None):
+    """The Delaunay triangulation of every view's points, on the device (csrc/delaunay.hip; include/mom4d.h has the canonical
+    form, the predicates and the status codes).  Enqueued on the current stream; nothing is read back.
+
+    pts [N,2] float64, the views' points concatenated; pt_off [V+1] int32 (not read on the host): as for tri_resample.  Returns
+    (tris [2N,3] int32, indices local to the view, of which the first tri_off[V] rows are written; tri_off [V+1] int32;
+    status [V] int32, N.DELAUNAY_OK or why the view has no triangles).  tris[:tri_off[V]] and tri_off go to tri_resample as they
+    are.  tris, tri_off, status: tensors to write into, or None; scratch: an int32 tensor of at least
+    delaunay_scratch_elements(V, H, W, N) elements to reuse, or None.  Afterwards scratch[0] is the number of deferred points and
+    scratch[1] the largest star of the call."""
+    V, n, dev = _tri_views("delaunay", pts, pt_off, H, W)
+    need = delaunay_scratch_elements(V, H, W, n)
+    if need == 0:
+        raise N.MomError(f"delaunay: unsupported shape V {V}, H {H}, W {W}, N {n}")
+    given = [("tris", tris, (2 * n, 3)), ("tri_off", tri_off, (V + 1,)), ("status", status, (V,))]
+    for name, t_, shape in given:
+        if t_ is not None and (tuple(t_.shape) != shape or t_.dtype != torch.int32 or t_.device != dev or not t_.is_contiguous()):
+            raise N.MomError(f"delaunay: {name} must be a contiguous torch.int32 {list(shape)} tensor on {dev}, "
+                             f"got {t_.dtype} {list(t_.shape)} on {t_.device}")
+    tris, tri_off, status = (torch.empty(shape, dtype=torch.int32, device=dev) if t_ is None else t_ for _, t_, shape in given)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.int32, device=dev)
+    elif scratch.dtype != torch.int32 or scratch.device != dev or not scratch.is_contiguous() or scratch.numel() < need:
+        raise N.MomError(f"delaunay: scratch must be a contiguous torch.int32 tensor of at least {need} elements on {dev}")
+    N.check(N.lib().mom_delaunay(V, H, W, n, N.ptr(pts), pt_off.data_ptr(), N.ptr(tris), tri_off.data_ptr(), status.data_ptr(),
+                                 scratch.data_ptr(), scratch.numel() * 4, N.current_stream()), "mom_delaunay")
+    return tris, tri_off, status
+
+
 def tri_resample(pts, pt_off, tris, tri_off, values, H, W, fill=0.0, out=None, scratch=None):
     """Linear interpolation of values given at each view's projected points, at every pixel centre: what
     scipy.interpolate.griddata(points, values, pixel grid, "linear", fill_value=fill) gives (train_motion.py:198,304,319), for all

@@ -800,6 +800,71 @@ size_t mom_pcd_compose_scratch_bytes(int V, int H, int W);
 int mom_pcd_compose(int V, int H, int W, int N, const double* resampled, const double* pts, const int* pt_off, uint8_t* image,
                     uint8_t* mask, void* scratch, size_t scratch_bytes, mom_stream_t stream);
 
+/* ---- the Delaunay triangulation of every view's points, on the device (csrc/delaunay.hip) ----
+ * What mom_tri_resample needs between upload_views' points and its own call: pts / pt_off in, tris / tri_off out, no triangle
+ * crosses the host.  Where a view's Delaunay triangulation is unique -- no predicate below falls inside its filter bound -- the result
+ * is that triangulation, the set of triangles scipy.spatial.Delaunay gives; anything else is refused per view by a status code, never
+ * guessed.
+ *   pts [N,2] float64 (16-byte aligned), pt_off [V+1] int32 DEVICE: mom_tri_resample's layout and rules (not read on the host; a
+ *           range read from pt_off is used only when it lies inside [0, N], any other makes the view MOM_DELAUNAY_FEW).  The device
+ *           finds a point's view by a search of pt_off: with ranges that overlap (a pt_off that decreases somewhere) a point counts
+ *           for one of them only, and the agreement with the twin below holds for a non-decreasing pt_off alone; memory stays safe
+ *   tris    capacity [2N,3] int32, indices LOCAL to the view, packed view after view;  tri_off [V+1] int32, written on the device:
+ *           both can be handed to mom_tri_resample unchanged
+ *   status  [V] int32, per view the LARGEST code any of its points raised (no order decides it):
+ *           MOM_DELAUNAY_OK            triangulated
+ *           MOM_DELAUNAY_FEW           n_j < 3
+ *           MOM_DELAUNAY_UNCERTAIN     a predicate fell inside its filter bound: duplicate, collinear or cocircular points, or
+ *                                      anything too close to call (the exact pixel grid is all of these)
+ *           MOM_DELAUNAY_OVERFLOW      a star outgrew MOM_DELAUNAY_MAX_STAR neighbours; or more points were deferred than the
+ *                                      scratch's list holds (N / 8 + 4096), or their finished stars hold more than 16 words per
+ *                                      entry of that list on average: then every view with a deferred point
+ *           MOM_DELAUNAY_RANGE         a non-finite point, or one outside [0, W-1] x [0, H-1]
+ *           MOM_DELAUNAY_INCONSISTENT  the count check below failed
+ *           A view whose status is not 0 contributes no triangles and does not disturb any other view.
+ * CANONICAL FORM: a function of the input, the same bits on every run.  Each triangle (i, j, k) has i as its smallest index and is
+ *   counter-clockwise, orient(p_i, p_j, p_k) > 0 in the (u, v) coordinates as given; a view's triangles are sorted by (i, j); an OK
+ *   view has T_j = 2 n_j - 2 - h_j triangles, h_j the number of points with an unbounded cell -- checked on the device.
+ * PREDICATES, float64 without contraction, eps = 2^-53 (Shewchuk's first-stage bounds); the twin uses the same expressions:
+ *   orient(a, b, c):      l = (ax-cx)(by-cy); r = (ay-cy)(bx-cx); det = l - r; certain iff |det| > (3 + 16 eps) eps (|l| + |r|)
+ *   incircle(a, b, c, d): adx = ax-dx, ... cdy = cy-dy; alift = adx^2 + ady^2, likewise blift, clift;
+ *                         det  = alift (bdx cdy - bdy cdx) + blift (cdx ady - cdy adx) + clift (adx bdy - ady bdx)
+ *                         perm = alift (|bdx cdy| + |bdy cdx|) + blift (|cdx ady| + |cdy adx|) + clift (|adx bdy| + |ady bdx|)
+ *                         certain iff |det| > (10 + 96 eps) eps perm
+ *   An uncertain predicate makes the view MOM_DELAUNAY_UNCERTAIN; there is no exact-arithmetic stage.
+ * THE STAR of p: its neighbours counter-clockwise around it; a consecutive pair (a, b) is a finite vertex if orient(p, a, b) > 0,
+ *   otherwise the gap (p is on the hull).  A candidate q is a neighbour iff incircle(p, a, b, q) > 0 for a finite vertex or q lies in
+ *   the gap's wedge, orient(p, a, q) > 0 or orient(p, q, b) > 0.  The vertices q cuts are a run of the cyclic list and q takes the place
+ *   of the neighbours inside the run, so in a closed cell the in-circle tests alone place q: three points in a line that form no
+ *   triangle make nothing uncertain there (while the cell is still open, such a triple with an end of the gap does).  A q that enters
+ *   the gap removes the neighbours on either side while its pair with them is finite and the vertex beyond them holds q in its circle;
+ *   a walk stops at a gap and does not start across one.  Candidates come from the image's pixel cells (cell (X, Y): floor(u) = X, floor(v) = Y,
+ *   a cell's points by index): the rings around p's cell until the cell is closed and every circle lies within the rings, one lane
+ *   per point with MOM_DELAUNAY_LANE_STAR neighbours in LDS; a point that outgrows that, lies on the hull or keeps a large circle
+ *   after ring 3 is deferred to a second launch, one WAVE per point with MOM_DELAUNAY_MAX_STAR neighbours in LDS, which then visits
+ *   for every vertex the rows of cells its circle -- grown by 2^-20, so that rounding can only add cells -- or the gap's wedge meets,
+ *   until a pass inserts nothing; its lanes test 64 candidates of a row at a time, insertions are serial and in the candidates'
+ *   order, and the finished star goes to a pool in scratch sized by the deferred list.  p writes the triangles (p, a, b) of its finite vertices with p < a and p < b.
+ *   scratch mom_delaunay_scratch_bytes(V, H, W, N) bytes, 4-byte aligned; after the call its first two int32 words hold the number of
+ *           deferred points and the largest star of the call.
+ * Ten launches on `stream`; no allocation, no copy, no synchronisation, no float atomics.  V <= 0, V > 65535, H < 1, W < 1,
+ * V H W >= 2^31, N < 0, N > 2^30, a null pointer that would be read or written, a misaligned pts / scratch or a scratch_bytes below the
+ * sizing function's value (0 for an unsupported shape): MOM_EINVAL before anything is launched.  mom_delaunay_host is the twin: host
+ * pointers, plain C++, the same decisions -- tris, tri_off and status equal the device's integer for integer; a test seam, not a
+ * fallback. */
+#define MOM_DELAUNAY_OK 0
+#define MOM_DELAUNAY_FEW 1
+#define MOM_DELAUNAY_UNCERTAIN 2
+#define MOM_DELAUNAY_OVERFLOW 3
+#define MOM_DELAUNAY_RANGE 4
+#define MOM_DELAUNAY_INCONSISTENT 5
+#define MOM_DELAUNAY_LANE_STAR 12
+#define MOM_DELAUNAY_MAX_STAR 1020
+size_t mom_delaunay_scratch_bytes(int V, int H, int W, int N);
+int mom_delaunay(int V, int H, int W, int N, const double* pts, const int* pt_off, int* tris, int* tri_off, int* status,
+                 void* scratch, size_t scratch_bytes, mom_stream_t stream);
+int mom_delaunay_host(int V, int H, int W, int N, const double* pts, const int* pt_off, int* tris, int* tri_off, int* status);
+
 /* ---- the warp of the reference's video generator (thirdparty/StyleCineGAN; csrc/eulerian_warp.hip) ----
  * The part of that generator that is neither a network nor a checkpoint.  All arithmetic is fp32 without contraction, operation by
  * operation what the reference's torch ops and its CUDA string compute.  Every call is stream-ordered on `stream`, allocates nothing,
