@@ -36,9 +36,13 @@ __device__ __forceinline__ float block_sum_256(float v, float* s_part)
     return s_part[0] + s_part[1] + s_part[2] + s_part[3];
 }
 
+// Sum = double: the atomic form, `sum` the MOM_SSIM_SUM_SLOTS accumulators.  Sum = float: the ordered form, `sum` one float per
+// workgroup that receives the workgroup's total with a plain store (mom_ssim_forward_ordered); everything before the last four lines
+// is the same code.
+template <typename Sum>
 __global__ void __launch_bounds__(256)
 ssim_fwd_kernel(Window win, int H, int W, size_t chan_stride, int sum_row0, int sum_row1, int dm_row0, int dm_row1,
-                const float* __restrict__ img1, const float* __restrict__ img2, float* __restrict__ dm, double* __restrict__ sum)
+                const float* __restrict__ img1, const float* __restrict__ img2, float* __restrict__ dm, Sum* __restrict__ sum)
 {
     // The images are H rows of W pixels per channel, channels chan_stride elements apart (a row slab of a taller image has
     // chan_stride > H W).  Map rows in [sum_row0, sum_row1) count toward the sum; derivative maps are written for rows in
@@ -101,7 +105,8 @@ ssim_fwd_kernel(Window win, int H, int W, size_t chan_stride, int sum_row0, int 
     const float tot = block_sum_256((in && gy >= sum_row0 && gy < sum_row1) ? map : 0.f, s_part);
     if (threadIdx.x == 0) {
         const unsigned b = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        atomicAdd(&sum[1 + b % (kSsimSlots - 1)], (double)tot);
+        if constexpr (sizeof(Sum) == sizeof(double)) atomicAdd(&sum[1 + b % (kSsimSlots - 1)], (double)tot);
+        else sum[b] = tot;
     }
 }
 
@@ -171,7 +176,7 @@ extern "C" int mom_ssim_forward_slab(int C, int H, int W, size_t chan_stride, in
     if (!img1 || !img2) return MOM_EINVAL;
     Window win;
     for (int k = 0; k <= 2 * kR; k++) win.w[k] = window11[k];
-    hipLaunchKernelGGL(ssim_fwd_kernel, dim3((W + kT - 1) / kT, (H + kT - 1) / kT, C), dim3(256), 0, s, win, H, W, chan_stride,
+    hipLaunchKernelGGL(ssim_fwd_kernel<double>, dim3((W + kT - 1) / kT, (H + kT - 1) / kT, C), dim3(256), 0, s, win, H, W, chan_stride,
                        sum_row0, sum_row1, dm_row0, dm_row1, img1, img2, dm, sum);
     if (hipGetLastError() != hipSuccess) return MOM_ELAUNCH;
     hipLaunchKernelGGL(ssim_sum_kernel, dim3(1), dim3(64), 0, s, sum);
@@ -183,6 +188,25 @@ extern "C" int mom_ssim_forward(int C, int H, int W, const float* window11, cons
 {
     return mom_ssim_forward_slab(C, H, W, (size_t)(H > 0 ? H : 0) * (size_t)(W > 0 ? W : 0), 0, H, 0, H, window11, img1, img2, dm,
                                  sum, stream);
+}
+
+// The ordered form: the same kernel with a store per workgroup where the atomic form adds, then the fold of the stored totals in the
+// documented order (values_ordered.hip).  No memset: every total the fold reads this call has written.
+extern "C" int mom_ssim_forward_ordered(int C, int H, int W, const float* window11, const float* img1, const float* img2, float* dm,
+                                        double* sum, void* scratch, size_t scratch_bytes, mom_stream_t stream)
+{
+    if (C < 0 || H < 0 || W < 0 || !window11 || !sum) return MOM_EINVAL;
+    if (C == 0 || H == 0 || W == 0) return mom_ssim_sum_ordered(0, nullptr, sum, stream);
+    const size_t need = mom_ssim_ordered_scratch_bytes(C, H, W);
+    if (!img1 || !img2 || !scratch || (reinterpret_cast<uintptr_t>(scratch) & 3) || scratch_bytes < need) return MOM_EINVAL;
+    if (C > 65535 || (H + kT - 1) / kT > 65535) return MOM_EINVAL;       // (the grid's y and z)
+    Window win;
+    for (int k = 0; k <= 2 * kR; k++) win.w[k] = window11[k];
+    float* totals = static_cast<float*>(scratch);
+    hipLaunchKernelGGL(ssim_fwd_kernel<float>, dim3((W + kT - 1) / kT, (H + kT - 1) / kT, C), dim3(256), 0, (hipStream_t)stream, win, H,
+                       W, (size_t)H * (size_t)W, 0, H, 0, H, img1, img2, dm, totals);
+    if (hipGetLastError() != hipSuccess) return MOM_ELAUNCH;
+    return mom_ssim_sum_ordered(need / sizeof(float), totals, sum, stream);
 }
 
 extern "C" int mom_ssim_backward_slab(int C, int H, int W, size_t chan_stride, const float* window11, const float* img1,

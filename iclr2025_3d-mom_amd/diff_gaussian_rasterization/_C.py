@@ -40,6 +40,7 @@ _state = {
     "ordered": None,           # the ordered backward's cached scratch, made by its first call: ordered_backward
     "field_ordered": None,     # the ordered field backwards' cached scratch (HexPlane, MLP), made by their first call: field_ordered_scratch
     "warp_ordered": None,      # the ordered warp's cached scratch (stage 1's video), made by its first call: warp_ordered_scratch
+    "value_ordered": None,     # the ordered loss values' cached scratch (L1, SSIM, regularisers), made by their first call: value_ordered_scratch
 }
 _FLAG_LAG = 4
 
@@ -191,7 +192,10 @@ def set_deterministic(on: bool) -> None:
     steps have no ordered form and raise MomError while the switch is on.  Stage 1's video follows it as well: the warp of
     cinemagraph (warp_one_level, pixel_video, the splat of FunctionSoftsplat; ops.eulerian_blend and ops.softsplat_sum with
     ordered=None) runs mom_eulerian_blend_ordered / mom_softsplat_sum_ordered out of a third grow-only scratch
-    (warp_ordered_scratch), so the frames stage 2 trains on are the same bits run after run.
+    (warp_ordered_scratch), so the frames stage 2 trains on are the same bits run after run.  And so do the loss VALUES:
+    ops.L1LossFunction, ops.SSIMFunction and ops.PlaneRegFunction run mom_l1_loss_ordered, mom_ssim_forward_ordered and
+    mom_plane_regulation_ordered (per-workgroup partials in value_ordered_scratch, added in the order include/mom4d.h documents), so
+    the loss, the PSNR and the EMAs a run logs repeat as well -- their gradients never depended on the switch.
     False (default): the atomic form; nothing of the above is allocated or called."""
     _state["deterministic"] = bool(on)
 
@@ -215,6 +219,20 @@ def field_ordered_scratch(which, need, dev):
     if t is None or t.numel() < need:
         o[which] = None                                         # (freed before its successor is made)
         t = o[which] = torch.empty(need + need // 4, dtype=torch.uint8, device=dev)
+    return t
+
+
+def value_ordered_scratch(which, need, dev):
+    """The ordered loss values' scratch (`which`: "l1", "ssim" or "reg": a buffer each, the regulariser's call may run on a second
+    stream), grow-only and one per process like field_ordered_scratch's, under the same assumption: the uses of one buffer are
+    enqueued on one stream, so a call may overwrite what the call before it left."""
+    o = _state["value_ordered"]
+    if o is None or o["dev"] != dev:
+        o = _state["value_ordered"] = dict(dev=dev, l1=None, ssim=None, reg=None)
+    t = o[which]
+    if t is None or t.numel() < need:
+        o[which] = None                                         # (freed before its successor is made)
+        t = o[which] = torch.empty(need + need // 4 + 4, dtype=torch.uint8, device=dev)
     return t
 
 

@@ -398,8 +398,14 @@ class L1LossFunction(torch.autograd.Function):
         b = gt.detach().contiguous().float()
         dimg = torch.empty_like(a)
         sums = torch.empty(2, dtype=torch.float32, device=a.device)
-        N.check(N.lib().mom_l1_loss(a.numel(), a.data_ptr(), b.data_ptr(), dimg.data_ptr(), sums.data_ptr(),
-                                    N.current_stream()), "mom_l1_loss")
+        if _RC.deterministic():        # the two sums in the documented order (include/mom4d.h, "ordered loss values"); dimg is the same bits
+            lib = N.lib()
+            scratch = _RC.value_ordered_scratch("l1", lib.mom_l1_loss_ordered_scratch_bytes(a.numel()), a.device)
+            N.check(lib.mom_l1_loss_ordered(a.numel(), a.data_ptr(), b.data_ptr(), dimg.data_ptr(), sums.data_ptr(), scratch.data_ptr(),
+                                            scratch.numel(), N.current_stream()), "mom_l1_loss_ordered")
+        else:
+            N.check(N.lib().mom_l1_loss(a.numel(), a.data_ptr(), b.data_ptr(), dimg.data_ptr(), sums.data_ptr(),
+                                        N.current_stream()), "mom_l1_loss")
         ctx.save_for_backward(dimg)
         ctx.mark_non_differentiable(sums)
         return sums[0] / a.numel(), sums
@@ -1186,9 +1192,16 @@ class SSIMFunction(torch.autograd.Function):
         need_grad = ctx.needs_input_grad[0]
         dm = torch.empty((3,) + tuple(a.shape), dtype=torch.float32, device=a.device) if need_grad else None
         total = torch.empty(N.SSIM_SUM_SLOTS, dtype=torch.float64, device=a.device)      # [0] = the sum, the rest scratch
-        N.check(N.lib().mom_ssim_forward(Cn, H, W, _ssim_window(), a.data_ptr(), b.data_ptr(),
-                                         None if dm is None else dm.data_ptr(), total.data_ptr(), N.current_stream()),
-                "mom_ssim_forward")
+        if _RC.deterministic() and a.numel():      # the workgroup totals stored and folded in the documented order; dm is the same bits
+            lib = N.lib()
+            scratch = _RC.value_ordered_scratch("ssim", lib.mom_ssim_ordered_scratch_bytes(Cn, H, W), a.device)
+            N.check(lib.mom_ssim_forward_ordered(Cn, H, W, _ssim_window(), a.data_ptr(), b.data_ptr(),
+                                                 None if dm is None else dm.data_ptr(), total.data_ptr(), scratch.data_ptr(),
+                                                 scratch.numel(), N.current_stream()), "mom_ssim_forward_ordered")
+        else:
+            N.check(N.lib().mom_ssim_forward(Cn, H, W, _ssim_window(), a.data_ptr(), b.data_ptr(),
+                                             None if dm is None else dm.data_ptr(), total.data_ptr(), N.current_stream()),
+                    "mom_ssim_forward")
         if need_grad:
             ctx.save_for_backward(a, b, dm)
         ctx.dims = (Cn, H, W)
@@ -1345,6 +1358,16 @@ class PlaneRegFunction(torch.autograd.Function):
         arr = c[1]
         dev = planes[0].device
         val = torch.empty(1, dtype=torch.float32, device=dev)
+
+        def value(stream):
+            lib = N.lib()
+            if _RC.deterministic():    # one partial per workgroup, folded in the documented order (include/mom4d.h, "ordered loss values")
+                scratch = _RC.value_ordered_scratch("reg", lib.mom_plane_regulation_ordered_scratch_bytes(arr, len(planes)), dev)
+                N.check(lib.mom_plane_regulation_ordered(arr, len(planes), val.data_ptr(), scratch.data_ptr(), scratch.numel(), stream),
+                        "mom_plane_regulation_ordered")
+            else:
+                N.check(lib.mom_plane_regulation(arr, len(planes), val.data_ptr(), stream), "mom_plane_regulation")
+
         if API_OVERLAP:
             # the value depends on the planes only: on the second stream it runs beside the compositing the caller's stream is
             # still busy with (the loop calls this right after render()); the caller's stream waits for it before it reads `val`.
@@ -1357,10 +1380,10 @@ class PlaneRegFunction(torch.autograd.Function):
                 stream_wait_mark(side, MARK_PARAMS)
             else:
                 stream_wait_stream(side, cur)
-            N.check(N.lib().mom_plane_regulation(arr, len(planes), val.data_ptr(), side), "mom_plane_regulation")
+            value(side)
             stream_wait_stream(cur, side)
         else:
-            N.check(N.lib().mom_plane_regulation(arr, len(planes), val.data_ptr(), N.current_stream()), "mom_plane_regulation")
+            value(N.current_stream())
         ctx.save_for_backward(*planes)
         ctx.w = (list(w_smooth), list(w_l1))
         return val[0]

@@ -5,6 +5,7 @@ dataset_readers.py:994-1002 derive them, a point cloud unprojected from a depth 
 F video frames from the centre view (time = f/(F-1), frame_num = f; dataset_readers.py:802-869) and a few
 multi-view frames at time 0."""
 import math
+import os
 
 import numpy as np
 import torch
@@ -118,7 +119,15 @@ class SyntheticScene:
         """What Scene.__init__ does with a fresh model (scene/__init__.py:78-89)."""
         gaussians._deformation.deformation_net.set_aabb(self.xyz_max, self.xyz_min)
         gaussians.create_from_pcd(self.point_cloud, self.cameras_extent, self.F, "", flow_scale, scene_flow=self.scene_flow)
+        self.gaussians = gaussians
         return gaussians
+
+    def save(self, iteration, stage):
+        """Scene.save (scene/__init__.py:57-60) for the model init_gaussians() was given: the PLY and the deformation bundle
+        under model_path/point_cloud/iteration_{iteration}."""
+        folder = os.path.join(self.model_path, "point_cloud/iteration_{}".format(iteration))
+        self.gaussians.save_ply(os.path.join(folder, "point_cloud.ply"))
+        self.gaussians.save_deformation(folder)
 
     def make_trained_like(self, gaussians, seed=6666):
         """The benchmark state of SURVEY 8(d): perturb the initial model so that it looks like a partly trained one."""

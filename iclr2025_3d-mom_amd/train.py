@@ -2,6 +2,8 @@
 LR update -> SH-degree bump -> camera draw -> render -> loss -> backward -> densification statistics ->
 densify / prune / opacity reset -> Adam step.  Host syncs the reference pays every iteration (loss.item(),
 isnan, the num_rendered read-back, H2D of matrices and ground truth) are optional here."""
+import os
+import random
 from collections import deque
 from random import randint
 
@@ -35,7 +37,8 @@ class Trainer:
         # levels of 16-channel planes (dnerf/eulerian_150_16) on one GPU -- parallel.attach() drops the fused step of such a trainer too.
         # deterministic=True: the rasterizer's backward adds in a defined order (RC.set_deterministic: the switch is process-wide and
         # stays on) and so does the field's (HexPlane pull form, ordered MLP weight gradients: DESIGN.md 3.23); the coarse and the fine
-        # stage -- activations, field, rasterizer, L1, regularisers, Adam -- then repeat bit for bit from the same state.  The fused steps
+        # stage -- activations, field, rasterizer, L1, regularisers, Adam -- then repeat bit for bit from the same state, and so do
+        # the numbers they log (the L1 sums and the PSNR, the SSIM value, the regulariser's value: DESIGN.md 3.26).  The fused steps
         # have no ordered form.
         if deterministic:
             if fused:
@@ -103,14 +106,82 @@ class Trainer:
         elif RC._state["mode"] == "async" and self._alog:
             self.drain_autograd()
 
-    def save(self, iteration, stage=None):
+    def save(self, iteration, stage=None, trainer_state=False):
         """scene.save() behind drain(): a fused (or async) run may hold a few iterations the device skipped after a binning
         overflow until the host replays them -- anything that reads the model between steps (checkpoints, evaluation renders)
-        drains first.  Trainer.step() does so itself at every iteration that restructures the model."""
+        drains first.  Trainer.step() does so itself at every iteration that restructures the model.
+        trainer_state=True: also what a run needs to be CONTINUED, as two more files in scene.model_path -- the reference's
+        checkpoint chkpnt_{stage}_{iteration}.pth = (GaussianModel.capture(), iteration) (train_4DGS.py:301: the model with its
+        optimizer) and trainer_state_{stage}_{iteration}.pth = state_dict(iteration); returns the latter's path (resume() takes it)."""
         self.drain()
         if self.fused is not None:
             self.fused.gather_moments()
-        self.scene.save(iteration, stage or self.stage)
+        stage = stage or self.stage
+        self.scene.save(iteration, stage)
+        if not trainer_state:
+            return None
+        folder = self.scene.model_path
+        torch.save((self.g.capture(), iteration), os.path.join(folder, f"chkpnt_{stage}_{iteration}.pth"))
+        path = os.path.join(folder, f"trainer_state_{stage}_{iteration}.pth")
+        torch.save(self.state_dict(iteration), path)
+        return path
+
+    def state_dict(self, iteration=0):
+        """What the iterations after `iteration` read of this trainer and of the process, beyond the model and its optimizer (those
+        are GaussianModel.capture()'s: parameters, both Adam moments and their step counts, the densification statistics,
+        active_sh_degree): the camera stack _draw() pops from (as indices into self.cams), Python's generator (_draw's randint),
+        torch's CPU generator and the model's device generator (densify_and_split's torch.normal, the one-pass round's normals), the
+        two EMAs, the stage, the iteration, and the rasterizer's sync mode and deterministic switch (checked, not set, on load).
+        NOT carried, because no result depends on them: the binning capacity hints, the Morton and plane orders of the field
+        (rebuilt from the positions), the descriptor, gradient-buffer and scratch caches of ops and of the rasterizer module, the
+        fused steps' buffers.  numpy's generator is not carried either: nothing in an iteration draws from it.  Pending work is
+        drained first, so the state describes a model every enqueued step has reached."""
+        self.drain()
+        index = {id(c): i for i, c in enumerate(self.cams)}
+        dev = self.g._xyz.device
+        return {"version": 1, "stage": self.stage, "iteration": int(iteration), "n_cams": len(self.cams),
+                "stack": [index[id(c)] for c in self.stack], "python_rng": random.getstate(), "torch_cpu_rng": torch.get_rng_state(),
+                "torch_device_rng": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None,
+                "ema_loss": self.ema_loss, "ema_psnr": self.ema_psnr, "sync_mode": RC._state["mode"],
+                "deterministic": RC.deterministic(), "fused": self.fused is not None}
+
+    def load_state_dict(self, state):
+        """The inverse of state_dict(), on a trainer built over the same scene, stage and switches (a mismatch raises: another
+        camera list, stage, sync mode, deterministic switch or fused setting would continue a different run); returns the iteration
+        the state was taken after.  The model itself is restored before: resume()."""
+        for key, have in (("version", 1), ("stage", self.stage), ("n_cams", len(self.cams)), ("sync_mode", RC._state["mode"]),
+                          ("deterministic", RC.deterministic()), ("fused", self.fused is not None)):
+            if state.get(key) != have:
+                raise RC.N.MomError(f"Trainer.load_state_dict: the state was saved with {key} = {state.get(key)!r}, this trainer has {have!r}")
+        if any(not 0 <= i < len(self.cams) for i in state["stack"]) or not state["stack"]:
+            raise RC.N.MomError("Trainer.load_state_dict: the camera stack does not index this trainer's cameras")
+        self.stack = [self.cams[i] for i in state["stack"]]
+        self.ema_loss, self.ema_psnr = float(state["ema_loss"]), float(state["ema_psnr"])
+        random.setstate(state["python_rng"])
+        torch.set_rng_state(state["torch_cpu_rng"].cpu())
+        dev = self.g._xyz.device
+        if dev.type == "cuda":
+            torch.cuda.set_rng_state(state["torch_device_rng"].cpu(), dev)
+        return int(state["iteration"])
+
+    def resume(self, path):
+        """Continue the run save(iteration, trainer_state=True) left: `path` is the trainer_state_*.pth it returned; the
+        chkpnt_*.pth beside it goes through GaussianModel.restore() (which sets the optimizer up again and loads its state), then
+        load_state_dict().  In this process or a fresh one, on a trainer built like the saved one; returns the iteration to
+        continue after.  A fused trainer is refused (its step holds views of the tensors restore() replaces).  Under
+        deterministic=True the continued run equals the uninterrupted one bit for bit; without the switch up to the atomics' noise."""
+        if self.fused is not None:
+            # (a fused step keeps views of the parameters and moments it was built over; restore() replaces them)
+            raise RC.N.MomError("Trainer.resume: a fused trainer cannot take a restored model; resume with fused=False")
+        state = torch.load(path, map_location="cpu", weights_only=False)
+        ck =os.path.join(os.path.dirname(path), f"chkpnt_{state['stage']}_{state['iteration']}.pth")
+        model_params, first_iter = torch.load(ck, map_location=self.g._xyz.device, weights_only=False)
+        if first_iter != state["iteration"]:
+            raise RC.N.MomError(f"Trainer.resume: {ck} was written after iteration {first_iter}, the trainer state after {state['iteration']}")
+        self.drain()
+        self.g.restore(model_params, self.opt)
+        self._log.clear(); self._checks.clear(); self._alog.clear()
+        return self.load_state_dict(state)
 
     def _recover(self, tag):
         torch.cuda.synchronize()
@@ -223,10 +294,13 @@ class Trainer:
 
         Ll1 = l1_loss(image, gt[:, :3, :, :])
         loss = Ll1
+        reg = ssim_value = None
         if self.stage == "fine" and hyper.time_smoothness_weight != 0:
-            loss = loss + g.compute_regulation(hyper.time_smoothness_weight, hyper.l1_time_planes, hyper.plane_tv_weight)
+            reg = g.compute_regulation(hyper.time_smoothness_weight, hyper.l1_time_planes, hyper.plane_tv_weight)
+            loss = loss + reg
         if opt.lambda_dssim != 0:
-            loss = loss + opt.lambda_dssim * (1.0 - ssim(image, gt))
+            ssim_value = ssim(image, gt)
+            loss = loss + opt.lambda_dssim * (1.0 - ssim_value)
         loss.backward()
 
         vsp_grad = torch.zeros_like(vsp_l[0])
@@ -247,7 +321,9 @@ class Trainer:
                 # squared error of the fused L1 pass only equals for a batch of one
                 ps = psnr_from_last_l1() if image.shape[0] == 1 else psnr(image.detach(), gt).mean()
                 self.ema_psnr = 0.4 * float(ps) + 0.6 * self.ema_psnr
-            self.last = {"loss": loss.detach(), "l1": Ll1.detach(), "points": g._xyz.shape[0]}
+            # (the terms as device scalars, None for one the loss does not have: what a log or a test of the ordered values reads)
+            self.last = {"loss": loss.detach(), "l1": Ll1.detach(), "points": g._xyz.shape[0],
+                         "reg": None if reg is None else reg.detach(), "ssim": None if ssim_value is None else ssim_value.detach()}
         loss = self._after_backward(iteration, loss.detach(), radii, visibility, vsp_grad)
         self._skip = None
         return loss

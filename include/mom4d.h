@@ -591,6 +591,56 @@ int mom_plane_regulation_acc(const MomRegPlane* planes, int count, float* value,
  * regulariser's backward, without reading it back to the host first. */
 int mom_plane_regulation_grad(const MomRegPlane* planes, int count, float* value, const float* upstream, mom_stream_t stream);
 
+/* ---- ordered loss values: the L1 sums, the SSIM sum and the regularisers' value as functions of their inputs, bit for bit ----------
+ * mom_l1_loss, mom_ssim_forward and mom_plane_regulation end every workgroup with an atomicAdd into one or a few words, so the value
+ * they return depends on the order the workgroups arrive in (the gradients behind them are formed per element and never did).  The
+ * ordered forms STORE one partial per workgroup into caller-owned scratch and add the partials up in one more launch; there is no
+ * float atomic anywhere in them (csrc/values_ordered.hip, the ordered instantiation of the SSIM kernel in csrc/ssim.hip).  Same
+ * contract as the atomic entries: stream-ordered, no allocation, copy or synchronisation.  They store their results (nothing is
+ * zeroed first and nothing is accumulated onto), and they compute VALUES only: the gradient image of the L1 pass and the SSIM
+ * derivative maps are those of the atomic entries bit for bit, the regulariser's gradient stays with mom_plane_regulation_grad.
+ *
+ * FOLD.  fold(v_0 .. v_{m-1}) cuts the terms into blocks of 64 from the first, adds each block left to right from +0.0,
+ *   b_j = (...((+0.0 + v_64j) + v_64j+1) + ...),  and then the block sums left to right,  fold = (...((+0.0 + b_0) + b_1) + ...);
+ * fold of no term is +0.0.  Every order below is this one rule applied to a list that depends on the problem size alone -- not on a
+ * grid chosen at launch, an environment switch, the pointers' alignment or which wave arrives first.
+ * L1 (n elements, terms |d_i| and d_i * d_i with d_i = img[i] - gt[i], the product rounded on its own).  Workgroup g of
+ *   ceil(n / 4096) owns elements [4096 g, 4096 g + 4096); its lane t of 256 owns the sixteen elements 4096 g + 1024 r + 4 t + j
+ *   (r = 0..3 outer, j = 0..3 inner) and adds those below n in that -- ascending -- order from +0.0: lane_t.  The workgroup's partial
+ *   is fold(lane_0 .. lane_255), and sums2[k] = fold(partial_0 .. partial_{G-1}), for k = 0 (|d|) and k = 1 (d * d) alike.
+ *   dimg (may be null) = sign(d_i) * (1.0f / (float)n), mom_l1_loss's bits.  n == 0: both sums +0.0.
+ * REGULARISERS (value of mom_plane_regulation; the planes' grad pointers are ignored).  The workgroups are mom_plane_regulation's:
+ *   plane after plane in the order given, and within a [H][W * 32 floats] plane workgroup `local` covers the sixteen rows from
+ *   16 (local / cb) and the 256 float columns from 256 (local % cb), cb = ceil(W * 32 / 256).  Lane t owns one column: for its rows h
+ *   in ascending order it adds, from +0.0, first cs * s_h * s_h (s_h = p[h+2] - 2 p[h+1] + p[h], 0 where h + 2 >= H; the product formed
+ *   as (cs * s_h) * s_h; cs = w_smooth / ((float)(H - 2) * (float)(W * 32)), 0 if H <= 2 or w_smooth == 0) and then, if w_l1 != 0,
+ *   cl * |1 - p[h]| (cl = w_l1 / ((float)H * (float)(W * 32))); a lane whose column lies outside the plane holds +0.0.  The
+ *   workgroup's partial is fold(lane_0 .. lane_255) and value = fold(all partials).  Every multiply and add is rounded on its own.
+ * SSIM.  The map, the derivative maps dm and the workgroup totals are mom_ssim_forward's (one 16 x 16 tile of one channel per
+ *   workgroup; its float total is the xor butterfly of each wave, offsets 32, 16, .. 1, then ((w_0 + w_1) + w_2) + w_3 over its
+ *   four waves -- a fixed order).  The ordered form stores total_b at b = tile_x + tiles_x * (tile_y + tiles_y * channel) and
+ *   sum[0] = fold(total_0 .. total_{B-1}) with every add in DOUBLE; only sum[0] is written (one double suffices).
+ *   mom_ssim_sum_ordered is that fold alone, on `blocks` floats on the device.  The row slabs of a tile-row shard have no ordered form.
+ * SCRATCH (the *_scratch_bytes queries; 0 for a size the call refuses or that needs none).  L1: the partials [2][G] floats.  SSIM:
+ *   the totals [B] floats.  Regularisers: the partials, one float per workgroup.  Every byte a call reads it has written first.
+ * MOM_EINVAL before anything is launched: a null image, target, result, window or plane pointer; n above 2^40; C above 65535 or more
+ * than 65535 tile rows; a plane with H or W outside 1 .. 2^24, more than MOM_REG_MAX_PLANES planes or 2^30 workgroups; scratch
+ * null or not 4-byte aligned where any is needed, scratch_bytes below the query's answer.
+ * The *_host entries are the same sums in plain C++ (no contraction, no GPU; host pointers): what the device returns, bit for bit. */
+size_t mom_l1_loss_ordered_scratch_bytes(size_t n);
+int mom_l1_loss_ordered(size_t n, const float* img, const float* gt, float* dimg, float* sums2, void* scratch, size_t scratch_bytes,
+                        mom_stream_t stream);
+int mom_l1_loss_ordered_host(size_t n, const float* img, const float* gt, float* dimg, float* sums2);
+size_t mom_ssim_ordered_scratch_bytes(int C, int H, int W);
+int mom_ssim_forward_ordered(int C, int H, int W, const float* window11, const float* img1, const float* img2, float* dm,
+                             double* sum, void* scratch, size_t scratch_bytes, mom_stream_t stream);
+int mom_ssim_sum_ordered(size_t blocks, const float* totals, double* sum, mom_stream_t stream);
+int mom_ssim_sum_ordered_host(size_t blocks, const float* totals, double* sum);
+size_t mom_plane_regulation_ordered_scratch_bytes(const MomRegPlane* planes, int count);
+int mom_plane_regulation_ordered(const MomRegPlane* planes, int count, float* value, void* scratch, size_t scratch_bytes,
+                                 mom_stream_t stream);
+int mom_plane_regulation_ordered_host(const MomRegPlane* planes, int count, float* value);
+
 /* ---- fused deformation MLP (scene/deformation.py:53-65,97-135; W = 64, defor_depth = 0, heads pos/scales/rot) ----
  *   h0 = W0 feat + b0 ;  o_k = W2_k relu(W1_k relu(h0) + b1_k) + b2_k  for k in {pos, scales, rot}
  *   pts = xyz + o_pos + flow_coef * scene_flow ; scales = scaling + o_scales ; rots = rotation + o_rot
